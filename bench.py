@@ -8,9 +8,14 @@ GPU at N = 8 -- `value`); the same line carries a `weak_scaling` object, 65536 s
 (per-GPU work fixed: what the kernels are priced on) -- never under the configs[2] label.  --batch-per-gpu B makes the
 weak-scaling variant the line's `value` instead (labelled as such).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figures, `roofline` from the HIP events of
+those steps).  --full adds the informational legs after the timed region: `config.kappa`, `parity_sample`, `gappy`,
+`gappy_all`, `coefficient_level`, `long_series`, `cpu_baseline` and, for N > 1, `weak_scaling` (each still switched off
+by its own --no-* option).  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 
 A "step" = one pass of the hot path (fused log-lik + reverse-mode gradient w.r.t. t, c, a, U, V, y)
 over the rank's shard of independent series, inputs already resident in HBM, followed for N>1 by the one
@@ -128,6 +133,37 @@ def cpu_baseline(N, J, grad, seconds):
 
 
 PARITY_NAMES = ("bt", "bc", "ba", "bU", "bV", "by")
+DUMP_BYTES = 56 * 2**20   # what --dump-outputs writes at most (all files together)
+
+
+def dump_outputs(path, ll, flag, grads, seed=0):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float64 .npy files under `path`:
+    ll.npy (the whole, gathered log-likelihood vector) and flag.npy (the per-series failure flags of this rank's shard);
+    with the gradient, bt / bc / ba / bU / bV / by.npy hold the rows of a fixed sample of this rank's series (drawn with
+    `seed`, in increasing order, as many as fit in DUMP_BYTES; every series when they all fit).  The inputs are seeded, so
+    two runs with the same arguments write outputs of the same series.  (Beyond 2^20 series ll and flag are sampled too.)"""
+    import numpy as np
+    import torch
+
+    def vec(x):
+        x = x.detach().double().cpu().numpy()
+        if x.shape[0] > 2**20:
+            x = x[np.sort(np.random.default_rng(seed).choice(x.shape[0], size=2**20, replace=False))]
+        return x
+
+    os.makedirs(path, exist_ok=True)
+    host = {"ll": vec(ll), "flag": vec(flag)}
+    if grads is not None:
+        B = int(grads[0].shape[0])
+        per_series = sum(g[0].numel() for g in grads) * 8
+        left = DUMP_BYTES - sum(v.nbytes for v in host.values())
+        count = max(1, min(B, left // per_series))
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=count, replace=False)) if count < B else np.arange(B)
+        sel = torch.from_numpy(idx).to(grads[0].device)
+        for name, g in zip(PARITY_NAMES, grads):
+            host[name] = g.index_select(0, sel).detach().double().cpu().numpy()
+    for name, v in host.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def take_sample(inputs, ll, grads, count, seed):
@@ -438,6 +474,11 @@ def main():
     ap.add_argument("--no-coefficient-level", action="store_true",
                     help="skip the extra (informational) measurement of c2_loglik_terms_grad on the same series")
     ap.add_argument("--dump-ll", default="", help="rank 0 saves the gathered log-likelihood vector here (.npy)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informational legs after the timed region (kappa, parity_sample, gappy, gappy_all, "
+                         "coefficient_level, long_series, cpu_baseline, weak_scaling); a plain run only times the steps")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -592,11 +633,13 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax[0])
         kernel_ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
-        return dict(Btot=Btot, first=first, Bp=Bp, elapsed=elapsed, kernel_ms=kernel_ms, ll=ll, nfail=nfail, prewarm=pre,
-                    placement=placement, work=work, out=out, inputs=(t, c, a, U, V, y))
+        return dict(Btot=Btot, first=first, Bp=Bp, elapsed=elapsed, kernel_ms=kernel_ms, ll=ll, flag=flag, nfail=nfail,
+                    prewarm=pre, placement=placement, work=work, out=out, inputs=(t, c, a, U, V, y))
 
     Btot = args.batch_per_gpu * world if weak else args.global_batch
     m = measure(Btot, args.placement_search)
+    if rank == 0 and args.dump_outputs:   # (before anything below reuses the step's arrays)
+        dump_outputs(args.dump_outputs, m["ll"], m["flag"], m["out"] if grad else None)
     first, Bp, elapsed, kernel_ms, ll, nfail, placement = m["first"], m["Bp"], m["elapsed"], m["kernel_ms"], m["ll"], m["nfail"], m["placement"]
     prewarm = m["prewarm"]
     work, out = m["work"], m["out"]
@@ -606,11 +649,11 @@ def main():
     # parity of the TIMED work: 32 series drawn from the batch the timed steps ran on, with the outputs of the last timed
     # step, set aside now and checked against the CPU oracle in the cpu_baseline leg (after every timed region)
     samples, coeff_sample = {}, None
-    want_parity = rank == 0 and grad and not args.no_cpu_baseline and not args.no_parity_sample
+    want_parity = rank == 0 and grad and args.full and not args.no_cpu_baseline and not args.no_parity_sample
     # conditioning of the timed batch (c2_condition: kappa = max a_n / d_n per series; untimed, after the timed region):
     # any float64 evaluation order carries ~0.4 eps kappa^2 of the largest gradient entry -- what the 1e-10 claim rests on
     kappa_obj = kap = None
-    if rank == 0 and J <= 32:
+    if rank == 0 and J <= 32 and args.full:
         try:
             kap, _kf = ops.condition(t, c, a, U, V)
             fin = kap[torch.isfinite(kap)]
@@ -641,7 +684,7 @@ def main():
         ranks = [None] * world
         dist.all_gather_object(ranks, me)
     weak_obj = None
-    if world > 1 and not weak and not args.no_weak_object and args.N == 4096:
+    if world > 1 and not weak and args.full and not args.no_weak_object and args.N == 4096:
         work = out = t = c = a = U = V = y = None
         torch.cuda.empty_cache()
         mw = measure(args.weak_batch_per_gpu * world, 1)
@@ -698,7 +741,7 @@ def main():
             line["weak_scaling"] = weak_obj
         if placement is not None:
             line["config"]["placement_search"] = placement
-        if world == 1 and grad and not args.exact_synth and not args.no_gappy:
+        if world == 1 and grad and args.full and not args.exact_synth and not args.no_gappy:
             del t, c, a, U, V, y   # (regenerated with gaps; the workspace and the gradient arrays are reused)
             torch.cuda.empty_cache()
             ll_keep = ll[:Bp].clone()
@@ -713,14 +756,14 @@ def main():
                 line["gappy_all"] = {"error": repr(e)[:200]}
             t = c = a = U = V = y = None
             ll = ll_keep
-        if world == 1 and grad and J == 8 and not args.exact_synth and not args.no_coefficient_level:
+        if world == 1 and grad and J == 8 and args.full and not args.exact_synth and not args.no_coefficient_level:
             # Informational, not `value`: the same series through the coefficient-level entry point,
             # log-likelihood + gradient w.r.t. (ac, bc, cc, dc, x, diag, y) with U, V formed inside the kernels.
             ll_matrix = ll[:Bp].clone()
             del t, c, a, U, V, y, out, work
             torch.cuda.empty_cache()
             line["coefficient_level"], coeff_sample = coefficient_level(first, Bp, N, J, dev, ll_matrix, min(args.steps, 5), want_parity)
-        if world == 1 and grad and J in (2, 4, 6, 8) and not args.no_long_series:
+        if world == 1 and grad and J in (2, 4, 6, 8) and args.full and not args.no_long_series:
             line["long_series"] = long_series(J, dev)
         if want_parity:
             try:
@@ -731,7 +774,7 @@ def main():
                     line["parity_sample"]["step_batch_all"] = parity_all_obj
             except Exception as e:  # noqa: BLE001 -- the checker must not take the line down; its absence is visible
                 line["parity_sample"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, J, grad, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if dist_on:

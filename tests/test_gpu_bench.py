@@ -58,6 +58,25 @@ def test_bench_weak_scaling_variant(tmp_path):
     assert np.array_equal(np.load(two), np.load(ref))
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned (log-likelihoods, flags, the six gradients) as float64 .npy
+    files, bit for bit the same in a second process (seeded inputs) and the same log-likelihoods as --dump-ll; a plain run
+    carries none of the informational legs of --full."""
+    a, b, ll = tmp_path / "a", tmp_path / "b", str(tmp_path / "ll.npy")
+    rc, line, err = run_bench(["--gpus", "1", "--dump-outputs", str(a), "--dump-ll", ll] + SMALL, {})
+    assert rc == 0 and line["steps"] == 2 and line["ms_per_step"] > 0, err
+    assert not {"gappy", "gappy_all", "coefficient_level", "long_series", "parity_sample", "cpu_baseline"} & set(line)
+    rc, _, err = run_bench(["--gpus", "1", "--dump-outputs", str(b)] + SMALL, {})
+    assert rc == 0, err
+    names = {"ll", "flag", "bt", "bc", "ba", "bU", "bV", "by"}
+    assert {p.name for p in a.iterdir()} == {n + ".npy" for n in names}
+    for n in names:
+        x, y = np.load(a / (n + ".npy")), np.load(b / (n + ".npy"))
+        assert x.dtype == np.float64 and np.array_equal(x, y), n
+    assert np.array_equal(np.load(a / "ll.npy"), np.load(ll))
+    assert np.load(a / "bU.npy").shape == (64, 256, 8) and not np.load(a / "flag.npy").any()
+
+
 def test_bench_refuses_more_ranks_than_devices():
     import torch
     n = torch.cuda.device_count() + 1
@@ -97,8 +116,9 @@ def test_bench_rccl_two_ranks_if_two_devices(tmp_path):
 def test_bench_default_flags_two_ranks_dry_run():
     """The line the driver's scaling run asks for -- `python bench.py --gpus N` with the DEFAULT steps / warm-up / shape (N = 4096,
     J = 8, 10 timed steps, the `weak_scaling` object measured in the same run) -- as a two-rank dry run over gloo on this
-    box's one device, with a global batch (and a weak batch per GPU) small enough for two ranks to share it."""
-    rc, line, err = run_bench(["--gpus", "2", "--global-batch", "4096", "--weak-batch-per-gpu", "4096"],
+    box's one device, with a global batch (and a weak batch per GPU) small enough for two ranks to share it; --full, since
+    the `weak_scaling` object is one of the informational legs."""
+    rc, line, err = run_bench(["--gpus", "2", "--global-batch", "4096", "--weak-batch-per-gpu", "4096", "--full"],
                               {"C2_DIST_BACKEND": "gloo"}, timeout=900)
     assert rc == 0 and line is not None, err
     assert line["n_gpus"] == 2 and line["steps"] == 10 and line["warmup"] == 3 and line["scaling"] == "strong"

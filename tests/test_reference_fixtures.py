@@ -7,20 +7,12 @@ build container over oracle/ref_shim.py):
   * cpp_* / py_* / cfg1_*   dense expectations on the reference's K = term.to_dense()    test_driver.py:26-135
   * gp*_     the reference's numpy GaussianProcess / ConditionalDistribution, executed    numpy.py:66-121, core.py:9-150
 
-CPU part: the host-side mirror (celerite2_amd/terms.py coefficients) and the CPU restatement against them, the
-agreement of the reference-generated file with the round-1 fixtures, and -- where /root/reference is mounted (build
-container only) -- the reference's acceptance suites over the shim.  GPU part (`-m gpu`): the device path through the
+CPU part: the host-side mirror (celerite2_amd/terms.py coefficients) and the CPU restatement against them, and the
+agreement of the reference-generated file with the round-1 fixtures.  GPU part (`-m gpu`): the device path through the
 same fixtures.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 COEF_CASES = {
     "real": lambda T: T.RealTerm(a=1.3, c=0.4),
     "complex": lambda T: T.ComplexTerm(a=0.8, b=0.03, c=1.0, d=0.1),
@@ -106,38 +98,6 @@ def test_cfg1_reference_gp_equals_dense(golden):
     """BASELINE configs[0] as worded (celerite2.GaussianProcess on the CPU path): the reference's own numpy
     GaussianProcess (over the restatement) and dense algebra on the reference's K agree to 1e-11."""
     assert abs(golden["cfg1_loglik_ref_gp"] - golden["cfg1_loglik"]) <= 1e-11 * abs(golden["cfg1_loglik"])
-
-
-@pytest.mark.skipif(not os.path.isfile("/root/reference/python/celerite2/terms.py"),
-                    reason="the reference is mounted in the build container only")
-def test_reference_acceptance_suites_over_the_shim():
-    """/root/reference/python/test/test_driver.py + test_backprop.py, unmodified, with celerite2.driver / .backprop = the
-    CPU restatement (tools/ref_acceptance.py)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ref_acceptance.py")], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "27 passed" in r.stdout, r.stdout[-500:]
-
-
-@pytest.mark.skipif(not os.path.isfile("/root/reference/python/celerite2/terms.py"),
-                    reason="the reference is mounted in the build container only")
-def test_fixture_regenerates_from_the_reference(golden, tmp_path):
-    """The committed file is what the generator produces from the reference today (same numpy): spot keys, bit for bit."""
-    sys.dont_write_bytecode = True
-    from oracle import ref_shim
-
-    ref = ref_shim.install()
-    try:
-        x, c, a, U, V, K, Y = ref.testing.get_matrices(include_dense=True)
-        assert np.array_equal(K, golden["py_K"]) and np.array_equal(U, golden["py_U"]) and np.array_equal(c, golden["py_c"])
-        term = ref.terms.RotationTerm(sigma=1.5, period=3.45, Q0=1.3, dQ=1.05, f=0.5)
-        for cn, v in zip(COEF_NAMES, term.get_coefficients()):
-            assert np.array_equal(v, golden["coef_rotation_" + cn])
-        gp = ref.numpy.GaussianProcess(ref.terms.SHOTerm(S0=5.0, w0=0.1, Q=3.45))
-        gp.compute(golden["cfg1_t"], diag=golden["cfg1_diag"])
-        assert gp.log_likelihood(golden["cfg1_y"]) == float(golden["cfg1_loglik_ref_gp"])
-    finally:
-        ref_shim.uninstall()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

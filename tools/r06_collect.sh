@@ -1,7 +1,7 @@
 # tools/r06_collect.sh -- the round's profile collection in one gpurun call (outputs under gpurun_out/r6p; copied into profiles/r06_*)
 mkdir -p gpurun_out/r6p; P=$PWD/gpurun_out/r6p
-python bench.py > $P/bench.json 2> $P/bench.err
-python bench.py --parity-sample all --no-gappy --no-long-series --no-coefficient-level > $P/bench_parity_all.json 2> $P/bench_parity_all.err
+python bench.py --full > $P/bench.json 2> $P/bench.err
+python bench.py --full --parity-sample all --no-gappy --no-long-series --no-coefficient-level > $P/bench_parity_all.json 2> $P/bench_parity_all.err
 tools/final_rocprof.sh > $P/rocprof_65536.md 2>&1
 tools/final_rocprof.sh 8192 > $P/rocprof_8192.md 2>&1
 tools/traffic.sh $P/traffic.json 65536 8192 > $P/traffic.txt 2>&1
