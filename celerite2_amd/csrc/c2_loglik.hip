@@ -43,9 +43,6 @@ extern "C" void c2_internal_read_dbg(unsigned long long *out) {  // read and cle
   hipMemcpyToSymbol(HIP_SYMBOL(c2_dbg), z, sizeof(z));
 }
 #endif
-#ifndef C2_LOGLIK_PAIRLINES
-#define C2_LOGLIK_PAIRLINES 1
-#endif
 
 namespace c2 {
 
@@ -103,9 +100,6 @@ __device__ __forceinline__ void fwd_chain(double p, double u, double v, double a
 #endif
 #ifndef C2_REV_APARK
 #define C2_REV_APARK 1
-#endif
-#ifndef C2_BACK_EARLY
-#define C2_BACK_EARLY 0   // the backward sweep's prefetch a whole segment ahead instead of half: measured, 3 % slower at 8192 series
 #endif
 // Packed symmetric storage of the C saved S_n columns in LDS.  In XOR order slot k of lane j is S(j^k, j) and
 // slot k of lane j^k is its transpose twin S(j, j^k) -- the same number up to rounding -- so for k >= 1 only
@@ -295,18 +289,7 @@ __global__ __launch_bounds__(kWave) void k_tt8_gate(int64_t B, int64_t N, int64_
   }
 }
 
-// DG: the next step's p and U gathered by DPP permutes instead of through LDS.  The LDS form costs the VALU nothing but
-// makes the wavefront wait for two LDS round trips per step -- which one would expect to hurt when the grid gives every
-// wavefront a SIMD of its own; measured it does not: the DPP form is 2 - 9 % slower there too (launch_fwd).
-// LN (G = R = 8, no padding, N even, 16-byte aligned U and V; C2_LOGLIK_LINES=1, OFF by default): the rows of U and V arrive
-// as whole aligned 128-byte LINES.  A width-8 row is 64 bytes, so the eight series of a wavefront make a row request eight
-// half-lines -- and once every SIMD of a CU has its wavefront these kernels queue at the CU's address unit, which prices a
-// request by the runs it touches, not by its bytes (profiles/r05_lines.md: without the U / V requests the forward pass at 8192
-// series runs at its clock-scaled floor).  MEASURED: the LDS instructions of the detour cost a lone wavefront what the
-// address unit gives back -- 8192 series 4.69 against 4.72 ms, 1024 - 4096 series 9 - 12 % SLOWER -- hence off.  Rows (2P, 2P+1) of a series share a line: one 16-byte piece per lane fetches the pair for all eight
-// series (a ring of four pairs in registers, eight rows ahead), a per-wave LDS tile turns pieces into the lanes' own
-// elements one pair ahead of their use.
-template <int G, int R, int C, int MODE, bool PAD, int OCC = C2_FWD_OCC, bool DG = false, bool LN = false, bool TT = false>
+template <int G, int R, int C, int MODE, bool PAD, int OCC = C2_FWD_OCC, bool TT = false>
 __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N, int Jrt, const double *__restrict__ t,
                                                          int64_t t_bs, const double *__restrict__ c, int64_t c_bs,
                                                          const double *__restrict__ a,
@@ -324,7 +307,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N,
   // guard that path measured exceeds kBackwardGuard (stream-ordered device decision, no host round trip).
   if (gate_closed(gate, (int64_t)blockIdx.x * (kWave / G))) return;   // (the series of a wavefront share a group of 64)
   // TT: the coefficient-level form (`a` = the white-noise diagonal, U / V not read); `tgate`: one word per group of 64 series
-  static_assert(!TT || (G >= 2 && G <= 8 && !PAD && !LN && MODE != 2), "coefficient-level form: full groups of two to eight lanes");
+  static_assert(!TT || (G >= 2 && G <= 8 && !PAD && MODE != 2), "coefficient-level form: full groups of two to eight lanes");
   if constexpr (TT) { if (!tt_group_open(tgate, (int64_t)blockIdx.x * (kWave / G))) return; }
   // MODE 1 with Wst and segguard (the reverse sweep by the BACKWARD recursion, k_loglik_rev<..., BACK>): W rows are
   // recorded as well, and one more checkpoint holds the state after the last row.  segguard[2 w], [2 w + 1] (k_anchor_spans)
@@ -417,61 +400,31 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N,
   // (the ring is RR = min(R, C2_FWD_RING) rows long: blocks of sixteen rows -- scalar requests of whole 128-byte lines -- keep a
   // ring of eight)
   constexpr int RR = R < C2_FWD_RING ? R : C2_FWD_RING;
-  double ru[LN ? 1 : RR], rv[LN ? 1 : RR];
+  double ru[RR], rv[RR];
   const double *up = Ub, *vp = Vb;  // row n0 of the current block
   auto load_row = [&](int r, int ahead, int64_t n, bool clamp) {  // row n = n0 + ahead
-    if constexpr (!LN && !TT) {
+    if constexpr (!TT) {
       int64_t o = ahead;
       if (clamp && n >= N) o -= n - (N - 1);
       ru[r] = act ? up[o * J] : 0.0; rv[r] = act ? vp[o * J] : 0.0;
     }
   };
-  // LN: pair P = rows (2P, 2P+1) of the lane's series, piece j of its 128 bytes; slot P % 4 of the ring
-  static_assert(!LN || (G == 8 && R == 8 && !PAD), "line staging: full groups of eight lanes, blocks of eight rows");
-  __shared__ __attribute__((aligned(16))) double2 ltile[LN ? 2 : 1][LN ? kWave : 1];   // [U | V][series][piece]
-  const double2 *Ul = reinterpret_cast<const double2 *>(U + L.b0 * N * J + (int64_t)L.sl * N * J) + j;
-  const double2 *Vl = reinterpret_cast<const double2 *>(V + L.b0 * N * J + (int64_t)L.sl * N * J) + j;
-  const int64_t plast = N / 2 - 1;
-  double qux[LN ? 4 : 1], quy[LN ? 4 : 1], qvx[LN ? 4 : 1], qvy[LN ? 4 : 1];   // (plain doubles: arrays of double2 end up in scratch)
-  double cu[2] = {0.0, 0.0}, cv[2] = {0.0, 0.0};   // own elements of the current pair's two rows
-  double nu[2] = {0.0, 0.0}, nv[2] = {0.0, 0.0};   // ... of the next pair
-  const double *ltu = reinterpret_cast<const double *>(ltile[0]) + grp * 16 + j;
-  const double *ltv = reinterpret_cast<const double *>(ltile[LN ? 1 : 0]) + grp * 16 + j;
-  auto pair_load = [&](int slot, int64_t P) {
-    const int64_t Pc = P < plast ? P : plast;
-    const double2 a2 = Ul[Pc * 8], b2 = Vl[Pc * 8];
-    qux[slot] = a2.x; quy[slot] = a2.y; qvx[slot] = b2.x; qvy[slot] = b2.y;
-  };
-  auto pair_stage = [&](int slot) {
-    ltile[0][lane] = make_double2(qux[slot], quy[slot]);
-    ltile[LN ? 1 : 0][lane] = make_double2(qvx[slot], qvy[slot]);
-  };
-  if constexpr (LN) {
-    cu[0] = Ub[0]; cu[1] = Ub[J]; cv[0] = Vb[0]; cv[1] = Vb[J];   // pair 0 (rows 0 and 1: the first two steps)
-    pair_load(1, 1); pair_load(2, 2); pair_load(3, 3); pair_load(0, 4);   // (the first step stages pair 1 and requests pair 5)
-  } else {
 #pragma unroll
-    for (int r = 0; r < RR; ++r) load_row(r, r, r, true);
-  }
+  for (int r = 0; r < RR; ++r) load_row(r, r, r, true);
 
   const bool sparse = wrec && !(__longlong_as_double((long long)segguard[2 * blockIdx.x]) > kBackwardGuard);   // (uniform)
   // prepare step 0 (p = 1: the neutral state sits at t_0)
   lds_order();
   double tnext = sin_[0][0][grp][0];
-  double pc = 1.0, uc = LN ? cu[0] : ru[0];
+  double pc = 1.0, uc = ru[0];
   double vcur = 0.0;   // (TT) own column of V of the current row
   if constexpr (TT) lt.uv(tnext, uc, vcur);
   double pXc[G], uXc[G];
-  if constexpr (DG) {
-    xgather_dpp<G>(pc, xs[0], lane, pXc);
-    xgather_dpp<G>(uc, xs[1], lane, uXc);
-  } else {
-    xs[0][lane] = pc; xs[1][lane] = uc;
-    lds_order();
-    xgather_lds<G>(xs[0], lane, pXc);
-    xgather_lds<G>(xs[1], lane, uXc);
-    lds_order();
-  }
+  xs[0][lane] = pc; xs[1][lane] = uc;
+  lds_order();
+  xgather_lds<G>(xs[0], lane, pXc);
+  xgather_lds<G>(xs[1], lane, uXc);
+  lds_order();
 
   auto block = [&](int64_t n0, int q, auto checked_tag) {
     constexpr bool CHECKED = decltype(checked_tag)::value;
@@ -490,34 +443,19 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N,
         // (a) next step's p and U -> LDS -> XOR gathers (consumed by the next iteration)
         const int rn = (r + 1) % R;
         double v, un1;
-        if constexpr (LN) {
-          // blocks start at multiples of eight: r even <=> n even <=> the first row of pair P = n / 2
-          if (r % 2 == 0) {
-            v = cv[0]; un1 = cu[1];
-            lds_order();
-            pair_stage((r / 2 + 1) % 4);                            // pair P + 1 -> tile (read back at the end of this step)
-            pair_load((r / 2 + 1) % 4, n / 2 + 5);                  // its slot: pair P + 5, eight rows ahead
-          } else {
-            v = cv[1]; un1 = nu[0];                                 // (pair P + 1, read back during the step before)
-          }
-        } else if constexpr (TT) {
+        if constexpr (TT) {
           v = vcur;
           lt.uv(tn1, un1, vcur);   // row n + 1 (beyond the last row: the clamped time, unused)
         } else {
-          v = rv[LN ? 0 : r % RR]; un1 = ru[LN ? 0 : rn % RR];
+          v = rv[r % RR]; un1 = ru[rn % RR];
         }
         const double pn1 = exp_decay(cj * (tn - tn1));
         double pXn[G], uXn[G];
-        if constexpr (DG) {
-          xgather_dpp<G>(pn1, xs[0], lane, pXn);
-          xgather_dpp<G>(un1, xs[1], lane, uXn);
-        } else {
-          xs[0][lane] = pn1; xs[1][lane] = un1;
-          lds_order();
-          xgather_lds<G>(xs[0], lane, pXn);
-          xgather_lds<G>(xs[1], lane, uXn);
-          lds_order();
-        }
+        xs[0][lane] = pn1; xs[1][lane] = un1;
+        lds_order();
+        xgather_lds<G>(xs[0], lane, pXn);
+        xgather_lds<G>(xs[1], lane, uXn);
+        lds_order();
         // (b) the chain of step n
         fwd_chain<G>(pc, uc, v, an, yn, pXc, uXc, SX, F, w, d, z, rd, xs[2], lane);
         if (REC) {
@@ -539,11 +477,6 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N,
         }
         tnext = tn1;
         pc = pn1; uc = un1;
-        if (LN && r % 2 == 1) { cu[0] = nu[0]; cu[1] = nu[1]; cv[0] = nv[0]; cv[1] = nv[1]; }
-        if (LN && r % 2 == 0) {   // own elements of pair P + 1: used from the next step on, so their latency is hidden
-          lds_order();
-          nu[0] = ltu[0]; nu[1] = ltu[8]; nv[0] = ltv[0]; nv[1] = ltv[8];
-        }
 #pragma unroll
         for (int k = 0; k < G; ++k) { pXc[k] = pXn[k]; uXc[k] = uXn[k]; }
       }
@@ -628,7 +561,7 @@ __device__ __forceinline__ double afetch(int lo, int hi) {
 // drops out, and so do the 128 accumulation registers the replayed states waited in.
 // OCC = 2 (BACK only): two wavefronts per SIMD -- for batches with more wavefronts than the chip has SIMDs; the per-step
 // vectors then wait in LDS instead of accumulation registers (256 registers per wavefront all told).
-// SC = true (BACK only): the backward recursion and the adjoint recursion in a SCALED FRAME.  With g_n = exp(-c (t_ref - t_n)),
+// The backward recursion and the adjoint recursion (BACK) run in a SCALED FRAME.  With g_n = exp(-c (t_ref - t_n)),
 // t_ref the time of the anchor row above (so g <= 1 and, within the guard, >= e^-2), the scaled states
 //     S^_n = G_n S_n G_n,   M^_n = G_n^-1 M_n G_n^-1,   F~_n = g_n F_n,   bF-_n = bF_n / g_n,   bV-_n = bV_n / g_n
 // obey recursions WITHOUT decay factors: S^_{n-1} = S^_n - d_{n-1} w~ w~^T, F~_{n-1} = F~_n - w~ z_{n-1} (w~ = g_{n-1} W_{n-1});
@@ -636,11 +569,7 @@ __device__ __forceinline__ double afetch(int lo, int hi) {
 // bV-_{n-1} = (z/d) bF- + w~ M^ needs no factor at all.  Per step the gathers of p and 1/p and the 32 multiplications by
 // p_i p_j, 1/(p_i p_j) drop out (five gathered vectors -> three: u- = u / g_n, x- = bV- + 2 ba u-, w~); what is left of the
 // frame is one factor on u, w and on the rows bU_n, bV_n on their way out, and a change of frame at every anchor.
-// LN (SC, G = C = 8, no padding, N even, 16-byte aligned U, bU, bV): rows of U, bU, bV move as whole aligned 128-byte lines --
-// rows (2P, 2P+1) of a series share one -- through per-wave LDS tiles, as in k_loglik_fwd<..., LN>: four line requests per
-// segment for U (rows 8k .. 8k+7; row 8k is handed down to the segment below), one store per completed pair for bU and bV
-// (the lane's element goes into a two-row tile; a pair is complete at its even row and leaves during the step after).
-template <int G, int C, bool PAD, bool FR, bool BACK = false, int OCC = C2_REV_OCC, bool SC = false, bool LN = false, bool TT = false>
+template <int G, int C, bool PAD, bool FR, bool BACK = false, int OCC = C2_REV_OCC, bool TT = false>
 __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N, int Jrt, const double *__restrict__ t,
                                                          int64_t t_bs, const double *__restrict__ c, int64_t c_bs,
                                                          const double *__restrict__ U,
@@ -658,12 +587,10 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
                                                          TermsArgs8 T8 = TermsArgs8{}, TermsGrads8 G8 = TermsGrads8{},
                                                          const unsigned long long *__restrict__ tgate = nullptr) {
   // TT (coefficient-level form): bt, ba, by are bx, bdiag, by; U, bU, bV, bc are not touched; G8 takes the coefficient gradients
-  static_assert(!TT || (G >= 2 && G <= 8 && C == 8 && !PAD && !FR && BACK && OCC == 1 && SC && !LN && C2_REV_APARK),
+  static_assert(!TT || (G >= 2 && G <= 8 && C == 8 && !PAD && !FR && BACK && OCC == 1 && C2_REV_APARK),
                 "coefficient-level form: the scaled-frame backward sweep on full groups of two to eight lanes");
   if constexpr (TT) { if (!tt_group_open(tgate, (int64_t)blockIdx.x * (kWave / G))) return; }
   static_assert(!(BACK && FR), "factor_rev replays from the caller's workspace");
-  static_assert(!SC || BACK, "the scaled frame belongs to the backward-recursion sweep");
-  static_assert(!LN || (SC && G == 8 && C == 8 && !PAD), "line staging: the scaled-frame sweep on full groups of eight lanes");
   if (gate_closed(gate, (int64_t)blockIdx.x * (kWave / G))) return;  // see k_loglik_fwd
   int astep = kAnchor;   // (BACK, uniform) segments between two anchors of the backward recursion
   if (segguard) {   // this wavefront by the backward recursion, or (the launch behind it) by the replay
@@ -674,7 +601,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
   constexpr int SPW = kWave / G;         // series per wavefront
   constexpr int NV = (C + G - 1) / G;    // vector loads per scalar stream per segment
   // per-step vectors of the current segment: [r][0] = p_n, [1] = U_n, [2] = W_{n-1}; own value at [lane]
-  __shared__ __attribute__((aligned(16))) double vv[(C2_REV_APARK && G <= 8 && OCC == 1) ? 1 : C][4][kWave];  // [3] = bW_{n-1} (FR), 1 / p_n (BACK)
+  __shared__ __attribute__((aligned(16))) double vv[(C2_REV_APARK && G <= 8 && OCC == 1) ? 1 : C][4][kWave];  // [3] = bW_{n-1} (FR), 1 / g_n (BACK)
   // The replayed S_n columns wait for their reverse step in AGPRs (G <= 8: C*G*2 = 128 of them); wider groups
   // keep them in LDS, symmetric-packed.
   constexpr bool APARK = C2_REV_APARK && G <= 8 && OCC == 1;
@@ -759,15 +686,6 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
   double vt[NV];
   double2 vdz[NV];
   double iu[C], iw[C], ibw[FR ? C : 1];
-  // LN: raw 16-byte pieces of the segment's four U lines; tiles [series][row of the pair][element]
-  double qux[LN ? 4 : 1], quy[LN ? 4 : 1], ucar = 0.0;
-  __shared__ __attribute__((aligned(16))) double2 utile[LN ? 4 : 1][LN ? kWave : 1];
-  __shared__ __attribute__((aligned(16))) double2 otile[LN ? 2 : 1][2][LN ? kWave : 1];   // [pair parity][bU | bV]
-  const double2 *Ul = reinterpret_cast<const double2 *>(U + L.b0 * N * J + (int64_t)L.sl * N * J) + j;
-  double2 *bUl = reinterpret_cast<double2 *>(bU + L.b0 * N * J + (int64_t)L.sl * N * J) + j;
-  double2 *bVl = reinterpret_cast<double2 *>(bV + L.b0 * N * J + (int64_t)L.sl * N * J) + j;
-  const int64_t plast = N / 2 - 1;
-  const int lto = grp * 16 + j;   // the lane's element of row 0 of a pair tile, in doubles (row 1: + 8)
   double cS[G], cF = 0.0, cW = 0.0, tck = 0.0;
   auto load_segment = [&](int64_t k) {
     const int64_t n_lo = 1 + k * C;
@@ -780,18 +698,10 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
       if constexpr (FR) vdz[m] = make_double2(fdb[row], fbdb[row]);  // (d, bd) take the place of (d, z)
       else vdz[m] = dzb[row];
     }
-    if constexpr (LN) {   // pairs 4k .. 4k+3 = rows 8k .. 8k+7 (beyond the last pair: that one again, unused)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t P = 4 * k + i;
-        const double2 u2 = Ul[(P < plast ? P : plast) * 8];
-        qux[i] = u2.x; quy[i] = u2.y;
-      }
-    }
 #pragma unroll
     for (int r = 0; r < C; ++r) {
       const int64_t n = (full || n_lo + r < N) ? n_lo + r : N - 1;
-      if constexpr (!LN && !TT) iu[r] = act ? Ub[n * J] : 0.0;
+      if constexpr (!TT) iu[r] = act ? Ub[n * J] : 0.0;
       if constexpr (BACK) iw[r] = V[((size_t)blockIdx.x * N + (n - 1)) * kWave + lane];   // the recorded W row n-1 (lane-major)
       else iw[r] = act ? Vb[(n - 1) * J] : 0.0;  // V row n-1 (-> W_{n-1} in the replay); FR: the caller's W row n-1
       if constexpr (FR) ibw[r] = act ? fbWb[(n - 1) * J] : 0.0;
@@ -832,10 +742,10 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
 #endif
 
   double carS[BACK ? G : 1], carF = 0.0;   // (BACK) the recursed state handed from a segment to the one below
-  double tref = 0.0, gtop = 1.0, igtop = 1.0;   // (SC) reference time of the frame; g, 1 / g of the row above the current segment's last step
+  double tref = 0.0, gtop = 1.0, igtop = 1.0;   // (BACK) reference time of the frame; g, 1 / g of the row above the current segment's last step
 #pragma unroll
   for (int i = 0; i < (BACK ? G : 1); ++i) carS[i] = 0.0;
-  constexpr bool HOLD = C2_LOGLIK_PAIRLINES && G == 8 && C == 8 && NV == 1;   // (see the flush at the end of a segment)
+  constexpr bool HOLD = G == 8 && C == 8 && NV == 1;   // (see the flush at the end of a segment)
   double hA = 0.0, hY = 0.0, hT = 0.0;
   bool hAok = false, hTok = false;
   int bq = 0;   // buffer of oBT the current segment writes
@@ -855,13 +765,9 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
     lds_order();
     rowT[cnt][grp] = carT; rowD[cnt][grp] = carDZ.x; rowR[cnt][grp] = carR; rowZ[cnt][grp] = carDZ.y;
     lds_order();
-    double dtv[C], pown[C], ipown[(BACK && APARK) ? C : 1];   // (SC: pown = g, ipown = 1 / g of rows n_lo-1 .. n_lo+C-2)
+    double dtv[C], pown[C], ipown[(BACK && APARK) ? C : 1];   // (BACK: pown = g, ipown = 1 / g of rows n_lo-1 .. n_lo+C-2)
     const bool anchor = !BACK || (k + 1) % astep == 0 || k == nseg - 1;   // (BACK, uniform) re-anchor, or carry on
-    if constexpr (LN) {   // the segment's U lines -> tiles (read back as the lanes' own elements behind the exponentials)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) utile[i][lane] = make_double2(qux[i], quy[i]);
-    }
-    if constexpr (SC) {
+    if constexpr (BACK) {
       if (anchor) {   // change of frame: the anchor row (the segment's last) becomes the reference, g = 1 there
         double gX[G];
         xgather_dpp<G>(gtop, xB, lane, gX);
@@ -883,17 +789,6 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
         igl[r] = rcp_nr(pown[r]);
         if constexpr (APARK) ipown[r] = igl[r];
         else { vv[r][0][lane] = pown[r]; vv[r][3][lane] = igl[r]; }
-      }
-      if constexpr (LN) {   // rows 8k+1 .. 8k+7 from this segment's lines, row 8k+8 handed down by the segment above
-        lds_order();
-        iu[C - 1] = ucar;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const double *ut = reinterpret_cast<const double *>(utile[i]) + lto;
-          if (i == 0) ucar = ut[0];
-          else iu[2 * i - 1] = ut[0];
-          iu[2 * i] = ut[8];
-        }
       }
       if constexpr (TT) {   // own columns of U_n, V_n of rows n_lo .. n_lo + C - 1 (entry r + 1 of rowT)
 #pragma unroll
@@ -923,15 +818,12 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
         dtv[r] = tprev - tn;
         tprev = tn;
         pown[r] = exp_decay(cj * dtv[r]);
-        if constexpr (BACK && APARK) ipown[r] = rcp_nr(pown[r]);
         if constexpr (APARK) {  // the prefetch registers are refilled half way through phase C
-          if constexpr (BACK) apark(iw[r], wAlo[r], wAhi[r]);   // the recorded W_{n-1}
           apark(iu[r], uAlo[r], uAhi[r]);
           if constexpr (FR) apark(ibw[r], xAlo[r], xAhi[r]);
         } else {
           vv[r][0][lane] = pown[r];
           vv[r][1][lane] = iu[r];
-          if constexpr (BACK) { vv[r][2][lane] = iw[r]; vv[r][3][lane] = rcp_nr(pown[r]); }
           if constexpr (FR) vv[r][3][lane] = ibw[r];
         }
       }
@@ -1020,10 +912,10 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
     // ---- phase C: fused reverse steps; the next (earlier) segment is fetched half way through ---------
 #pragma unroll
     for (int r = C - 1; r >= 0; --r) {
-      if (r == (BACK && C2_BACK_EARLY ? C - 1 : C / 2 - 1) || (C == 1)) {
+      if (r == C / 2 - 1 || (C == 1)) {
         if (k > 0) load_segment(k - 1);
       }
-      if constexpr (SC) {
+      if constexpr (BACK) {
         if (r < cnt) {   // the step in the scaled frame (see the head of the kernel); F holds F~_n, bF holds bF-, bVn holds bV-_n
           const int64_t n = n_lo + r;
           const double rdm = rowR[r][grp], zm = rowZ[r][grp];
@@ -1046,17 +938,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
             xgather_dpp<G>(vv[r][2][lane], xB, lane, wX);
           }
           const double u = uX[0], wm = wX[0];   // u-_n and w~_{n-1} of this lane
-          // rows n (odd first, then even) of a pair fill its tile; blocks start at odd rows: r odd <=> n even, pair (r + 1) / 2 + 4k
-          double *obu = reinterpret_cast<double *>(otile[LN ? ((r + 1) / 2) & 1 : 0][0]) + lto + ((r & 1) ? 0 : 8);
-          double *obv = reinterpret_cast<double *>(otile[LN ? ((r + 1) / 2) & 1 : 0][1]) + lto + ((r & 1) ? 0 : 8);
-          if constexpr (LN) {
-            if (r % 2 == 0 && r + 1 < cnt) {   // the pair completed by the step before (row n + 1, even) leaves now
-              lds_order();
-              const int64_t P = (n + 1) / 2;
-              bUl[P * 8] = otile[((r + 2) / 2) & 1][0][lane];
-              bVl[P * 8] = otile[((r + 2) / 2) & 1][1][lane];
-            }
-          } else if constexpr (!TT) {
+          if constexpr (!TT) {
             if (st) bVb[n * J] = bVn * gn;
           }
           const double bVout = bVn * gn;
@@ -1077,8 +959,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
             else { xs0 = fma(xX[i], SX[i], xs0); bp0 = fma(SX[i], m, bp0); q0 = fma(wX[i], m, q0); }
           }
           double gs8 = 0.0;   // (TT) sum_k g_nk dc_k of row n: what bx_n has on top of bt_n
-          if constexpr (LN) { *obu = ign * (bU1 - (xs0 + xs1)); *obv = bVout; }   // (adjacent tiles: one ds_write2_b64)
-          else if constexpr (TT) {
+          if constexpr (TT) {
             // the reverse of the recipe for row n: own values and the XOR-1 partner's (the other column of the complex term)
             const double bUo = ign * (bU1 - (xs0 + xs1));          // bU_n, own column
             const double uo = u * gn;                              // U_n, own column (u is u- = U_n / g_n)
@@ -1114,9 +995,9 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
       } else
       if (r < cnt) {
         const int64_t n = n_lo + r;
-        const double Fpn = FR ? 0.0 : (BACK ? F : Fp[BACK ? 0 : r]);
+        const double Fpn = FR ? 0.0 : Fp[r];
         const double rdm = rowR[r][grp], zm = rowZ[r][grp];  // FR: zm = bd_{n-1}
-        const double dt = (BACK && !APARK) ? rowT[r][grp] - rowT[r + 1][grp] : dtv[r];   // (two wavefronts per SIMD: not kept)
+        const double dt = dtv[r];
         double bWm = 0.0;  // FR: the lane's own bW_{n-1}
         if constexpr (FR) {
           if constexpr (APARK) bWm = afetch(xAlo[r], xAhi[r]);
@@ -1139,24 +1020,11 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
           xgather_lds<G>(vv[r][2], lane, wX);
         }
         const double p = pX[0], u = uX[0], wm = wX[0];  // slot 0 of an XOR gather is the lane's own element
-        double ipX[BACK ? G : 1], tau_n = 0.0;
-        if constexpr (BACK) {   // S_n is the carried state; tau_n = U_n S_n as the forward pass formed it
-          if constexpr (APARK) xgather_dpp<G>(ipown[r], xB, lane, ipX);
-          else xgather_dpp<G>(vv[r][3][lane], xB, lane, ipX);
-          double ta0 = 0.0, ta1 = 0.0;
-#pragma unroll
-          for (int i = 0; i < G; ++i) {
-            Sf[i] = SX[i];
-            if (i & 1) ta1 = fma(uX[i], Sf[i], ta1);
-            else ta0 = fma(uX[i], Sf[i], ta0);
-          }
-          tau_n = ta0 + ta1;
-        } else if constexpr (APARK) {
-          tau_n = tauS[BACK ? 0 : r];
+        double tau_n = tauS[r];
+        if constexpr (APARK) {
 #pragma unroll
           for (int i = 0; i < G; ++i) Sf[i] = afetch(sAlo[r][i], sAhi[r][i]);
         } else {
-          tau_n = tauS[BACK ? 0 : r];
           const double *sfr = sfL[r];
 #pragma unroll
           for (int i = 0; i < G; ++i) Sf[i] = sfr[soff[i]];
@@ -1214,20 +1082,13 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
           ban = 0.5 * rdm * (zm * zr - 1.0) - 0.5 * Q - zr * Gs;
           oBA[grp][r] = ban;
         }
-        if constexpr (BACK) {   // the state of row n-1 (rowD[r] = d_{n-1}, zm = z_{n-1}, wX = W_{n-1})
-          const double ip = ipX[0], dwm = rowD[r][grp] * wm;
-#pragma unroll
-          for (int i = 0; i < G; ++i) SX[i] = fma(-dwm, wX[i], (ipX[i] * ip) * Sf[i]);
-          F = fma(-wm, zm, F * ip);
-        }
       }
     }
     if constexpr (BACK) {
 #pragma unroll
       for (int i = 0; i < G; ++i) carS[i] = SX[i];
       carF = F;
-    }
-    if constexpr (SC) {   // row n_lo - 1 is the row above the next (earlier) segment's last step
+      // row n_lo - 1 is the row above the next (earlier) segment's last step
       if constexpr (APARK) { gtop = pown[0]; igtop = ipown[0]; }
       else { gtop = vv[0][0][lane]; igtop = vv[0][3][lane]; }
     }
@@ -1237,7 +1098,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
     if constexpr (HOLD) {
       // (segments of eight rows at width 8: a run is HALF a 128-byte line, and the two halves of a line written eight steps apart
       // are merged on the memory side one by one -- profiles/r06_halflines.md.  The upper half (rows 16 i + 8 ..) waits in a register
-      // per stream and leaves with the lower half, back to back.  C2_LOGLIK_PAIRLINES=0: as they come.)
+      // per stream and leaves with the lower half, back to back.)
       if (PAD ? L.valid : true) {
         const double vA = oBA[grp][j], vT = j == 0 ? oBT[bq][grp][C - 1] : oBT[bq ^ 1][grp][j - 1];
         double vY = 0.0;
@@ -1316,15 +1177,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
   if constexpr (HOLD) {   // the upper half of bt's first line (rows 8 .. 15) waited for these
     if (hTok && (PAD ? L.valid : true)) btb[C + j] = hT;
   }
-  if constexpr (LN) {   // row 0 completes pair 0 (row 1 is in the tile of even pairs since the last step)
-    double *obu = reinterpret_cast<double *>(otile[0][0]) + lto, *obv = reinterpret_cast<double *>(otile[0][1]) + lto;
-    *obv = bVn * gtop;
-    *obu = 0.0;
-    lds_order();
-    bUl[0] = otile[0][0][lane];
-    bVl[0] = otile[0][1][lane];
-    bc[L.b * J + j] = bcj;
-  } else if constexpr (TT) {
+  if constexpr (TT) {
     const int JC = T8.Jc, JR = G - 2 * JC;
     const double bcp = dpp_mov<kDppXor1>(bcj);
     if (lt.re) { G8.bar[L.b * JR + j] = sba + accA; G8.bcr[L.b * JR + j] = bcj; }
@@ -1332,7 +1185,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
       const int64_t o = L.b * JC + ((j - JR) >> 1);
       G8.bac[o] = sba + accA; G8.bbc[o] = accB; G8.bdc[o] = accD; G8.bcc[o] = bcj + bcp;
     }
-  } else if (st) { bVb[0] = SC ? bVn * gtop : bVn; bUb[0] = 0.0; bc[L.b * J + j] = bcj; }
+  } else if (st) { bVb[0] = BACK ? bVn * gtop : bVn; bUb[0] = 0.0; bc[L.b * J + j] = bcj; }
 }
 
 }  // namespace c2
@@ -1355,14 +1208,6 @@ using namespace c2;
 static int64_t simd_count();
 namespace {
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP; }
-// the forward kernel's p / U gathers by DPP instead of through LDS (C2_FWD_DPP_GATHERS=1)
-// (measured, round 4: slower even then -- 1024 series 3.76 -> 4.11 ms for the gradient pair, forward-only 1.27 -> 1.30 at 4096
-// series: the 28 permutes join the step's dependency chain; kept as a switch, off)
-inline bool fwd_dpp_gathers(unsigned waves) {
-  (void)waves;
-  return opt::has(opt::k_fwd_dpp_gathers) && opt::ival(opt::k_fwd_dpp_gathers) != 0;
-}
-
 template <int MODE>
 int launch_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                const double *a, const double *U, const double *V, const double *y, double *ll, int32_t *flag,
@@ -1375,24 +1220,9 @@ int launch_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, c
                        c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wst, DZst, gate, segguard);
     return launch_ok();
   }
-  const bool dg = G_ <= 8 && fwd_dpp_gathers(grid.x);
-  // rows of U, V as whole 128-byte lines (k_loglik_fwd<..., LN>): J = 8, an even number of rows, 16-byte aligned arrays
-  if (J == 8 && N >= 2 && N % 2 == 0 && ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(V)) & 15) == 0 && !dg &&
-      opt::has(opt::k_loglik_lines) && (opt::ival(opt::k_loglik_lines) == 1 || opt::ival(opt::k_loglik_lines) == 2)) {
-    hipLaunchKernelGGL((k_loglik_fwd<8, 8, C2_CKPT_C, MODE, false, C2_FWD_OCC, false, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t,
-                       t_bs, c, c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wst, DZst, gate, segguard);
-    return launch_ok();
-  }
 #define C2_FWD(G, R, C)                                                                                          \
   do {                                                                                                           \
-    if (dg && G <= 8) {                                                                                          \
-      if (J == G)                                                                                                \
-        hipLaunchKernelGGL((k_loglik_fwd<(G <= 8 ? G : 8), R, C, MODE, false, C2_FWD_OCC, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t, \
-                           t_bs, c, c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wst, DZst, gate, segguard);         \
-      else                                                                                                       \
-        hipLaunchKernelGGL((k_loglik_fwd<(G <= 8 ? G : 8), R, C, MODE, true, C2_FWD_OCC, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t,  \
-                           t_bs, c, c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wst, DZst, gate, segguard);         \
-    } else if (J == G)                                                                                           \
+    if (J == G)                                                                                                  \
       hipLaunchKernelGGL((k_loglik_fwd<G, R, C, MODE, false>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs,   \
                          c, c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wst, DZst, gate, segguard);                 \
     else                                                                                                         \
@@ -1806,7 +1636,6 @@ static int64_t simd_count() {
   }
   return n;
 }
-static bool occ2_enabled() { return !(opt::has(opt::k_loglik_back_occ2) && opt::ival(opt::k_loglik_back_occ2) == 0); }
 static bool use_back(int64_t N, int64_t J) {
   if (opt::has(opt::k_loglik_back) && opt::ival(opt::k_loglik_back) == 0) return false;
   return group_size(J) <= 8 && N >= 2;
@@ -2138,35 +1967,19 @@ static int loglik_grad_group(int64_t B, int64_t N, int64_t J, const double *t, i
   // More wavefronts than SIMDs (8192 < B <= 16384 at J = 8; the two-lane pair takes over beyond): both kernels of the
   // backward form as instances that fit two wavefronts per SIMD, so the second half of the batch runs next to the first
   // instead of behind it
-  const bool occ2 = back && J == 8 && occ2_enabled() && (int64_t)grid.x > simd_count();
+  const bool occ2 = back && J == 8 && (int64_t)grid.x > simd_count();
   if (int e = launch_fwd<1>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, ckpt, nseg, Wrec, DZst, s, gate, segg, occ2)) return e;
-  // the sweep in the scaled frame (k_loglik_rev<..., SC>: no decay factors in the step); C2_LOGLIK_SCALED=0: the plain form (A/B runs)
-  const bool sc = !(opt::has(opt::k_loglik_scaled) && opt::ival(opt::k_loglik_scaled) == 0);
 #define C2_REVB_ARGS grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, (const double *)Wrec, (const double2 *)DZst, \
                      (const double *)ckpt, nseg, (const int32_t *)flag, bt, bc, ba, bU, bV, by, nullptr, nullptr, nullptr, gate, \
                      (const unsigned long long *)segg
-  // ... with the rows of U, bU, bV as whole 128-byte lines (k_loglik_rev<..., LN>): J = 8, an even number of rows, aligned arrays
-  const bool ln = sc && J == 8 && N >= 2 && N % 2 == 0 &&
-                  ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(bU) | reinterpret_cast<uintptr_t>(bV)) & 15) == 0 &&
-                  opt::has(opt::k_loglik_lines) && (opt::ival(opt::k_loglik_lines) == 1 || opt::ival(opt::k_loglik_lines) == 3);
   if (back && occ2) {
-    if (ln) hipLaunchKernelGGL((k_loglik_rev<8, C2_CKPT_C, false, false, true, 2, true, true>), C2_REVB_ARGS);
-    else if (sc) hipLaunchKernelGGL((k_loglik_rev<8, C2_CKPT_C, false, false, true, 2, true>), C2_REVB_ARGS);
-    else hipLaunchKernelGGL((k_loglik_rev<8, C2_CKPT_C, false, false, true, 2>), C2_REVB_ARGS);
-    if (int e = launch_ok()) return e;
-  } else if (back && ln) {
-    hipLaunchKernelGGL((k_loglik_rev<8, C2_CKPT_C, false, false, true, C2_REV_OCC, true, true>), C2_REVB_ARGS);
+    hipLaunchKernelGGL((k_loglik_rev<8, C2_CKPT_C, false, false, true, 2>), C2_REVB_ARGS);
     if (int e = launch_ok()) return e;
   } else if (back) {
 #define C2_REVB(G, C)                                                                                         \
   do {                                                                                                        \
-    if (J == G) {                                                                                             \
-      if (sc) hipLaunchKernelGGL((k_loglik_rev<G, C, false, false, true, C2_REV_OCC, true>), C2_REVB_ARGS);   \
-      else hipLaunchKernelGGL((k_loglik_rev<G, C, false, false, true>), C2_REVB_ARGS);                        \
-    } else {                                                                                                  \
-      if (sc) hipLaunchKernelGGL((k_loglik_rev<G, C, true, false, true, C2_REV_OCC, true>), C2_REVB_ARGS);    \
-      else hipLaunchKernelGGL((k_loglik_rev<G, C, true, false, true>), C2_REVB_ARGS);                         \
-    }                                                                                                         \
+    if (J == G) hipLaunchKernelGGL((k_loglik_rev<G, C, false, false, true>), C2_REVB_ARGS);                   \
+    else hipLaunchKernelGGL((k_loglik_rev<G, C, true, false, true>), C2_REVB_ARGS);                           \
   } while (0)
     switch (G_) {
       case 1: C2_REVB(1, C2_CKPT_C); break;
@@ -2236,11 +2049,11 @@ int c2_internal_loglik_g8_tt_grad(int64_t B, int64_t N, int64_t J, int64_t Jc, i
   if (int e = launch_ok()) return e;
 #define C2_TTG(G_, R_)                                                                                                                \
   do {                                                                                                                                \
-    hipLaunchKernelGGL((k_loglik_fwd<G_, R_, C2_CKPT_C, 1, false, 1, false, false, true>), grid, dim3(kWave), 0, s, B, N, G_, x, x_bs, \
+    hipLaunchKernelGGL((k_loglik_fwd<G_, R_, C2_CKPT_C, 1, false, 1, true>), grid, dim3(kWave), 0, s, B, N, G_, x, x_bs, \
                        c, J, diag, (const double *)nullptr, (const double *)nullptr, y, ll, flag, ckpt, nseg, Wrec, DZst,             \
                        (const unsigned long long *)nullptr, (const unsigned long long *)segg, T, (const unsigned long long *)tgate);  \
     if (int e = launch_ok()) return e;                                                                                                \
-    hipLaunchKernelGGL((k_loglik_rev<G_, C2_CKPT_C, false, false, true, 1, true, false, true>), grid, dim3(kWave), 0, s, B, N, G_, x,  \
+    hipLaunchKernelGGL((k_loglik_rev<G_, C2_CKPT_C, false, false, true, 1, true>), grid, dim3(kWave), 0, s, B, N, G_, x,  \
                        x_bs, c, J, (const double *)nullptr, (const double *)Wrec, (const double2 *)DZst, (const double *)ckpt, nseg,  \
                        (const int32_t *)flag, bx, (double *)nullptr, bdiag, (double *)nullptr, (double *)nullptr, by,                 \
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,                                     \
@@ -2267,7 +2080,7 @@ int c2_internal_loglik_g8_tt(int64_t B, int64_t N, int64_t J, int64_t Jc, int co
                      (const unsigned long long *)nullptr, T, x, x_bs, guard, tgate);
   if (int e = launch_ok()) return e;
 #define C2_TTF(G_, R_)                                                                                                                \
-  hipLaunchKernelGGL((k_loglik_fwd<G_, R_, C2_CKPT_C, 0, false, 1, false, false, true>), grid, dim3(kWave), 0, s, B, N, G_, x, x_bs, c, \
+  hipLaunchKernelGGL((k_loglik_fwd<G_, R_, C2_CKPT_C, 0, false, 1, true>), grid, dim3(kWave), 0, s, B, N, G_, x, x_bs, c, \
                      J, diag, (const double *)nullptr, (const double *)nullptr, y, ll, flag, (double *)nullptr, (int64_t)0,           \
                      (double *)nullptr, (double2 *)nullptr, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, \
                      T, (const unsigned long long *)tgate)

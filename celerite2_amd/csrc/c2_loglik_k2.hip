@@ -47,42 +47,13 @@
 namespace c2k2 {
 using namespace c2;
 
-// Streaming hints (C2K2_NT; see C2T_NT in c2_loglik_t.hip): every byte of this pair is touched once.  With the scalar gradients leaving as
-// whole lines (STR = 16 below) nothing has to SURVIVE in L2 here, so the hint is worth less than in the one-lane pair.
-#ifndef C2K2_NT
-#define C2K2_NT 0
-#endif
-typedef double k2d2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2 ld2s(const double2 *p) {
-#if C2K2_NT
-  const k2d2v v = __builtin_nontemporal_load(reinterpret_cast<const k2d2v *>(p));
-  return make_double2(v.x, v.y);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ double ld1s(const double *p) {
-#if C2K2_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void st2s(double2 *p, double2 v) {
-#if C2K2_NT
-  k2d2v w; w.x = v.x; w.y = v.y;
-  __builtin_nontemporal_store(w, reinterpret_cast<k2d2v *>(p));
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ void st1s(double *p, double v) {
-#if C2K2_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// Accesses of every stream this pair touches once: plain loads and stores.  The non-temporal hint of the one-lane pair (c2_loglik_t.hip)
+// gains nothing here -- with the scalar gradients leaving as whole lines (STR = 16 below) nothing has to SURVIVE in L2
+// (profiles/r06_halflines.md: 14.61 vs 14.63 ms).
+__device__ __forceinline__ double2 ld2s(const double2 *p) { return *p; }
+__device__ __forceinline__ double ld1s(const double *p) { return *p; }
+__device__ __forceinline__ void st2s(double2 *p, double2 v) { *p = v; }
+__device__ __forceinline__ void st1s(double *p, double v) { *p = v; }
 
 constexpr int J = 8, NL = 20, SPW = 32, C = 32, ST = 8;
 constexpr int RSTR = 2 * J;       // LDS stride (doubles) of a series in a two-row tile: one 128-byte line, its eight 16-byte
@@ -533,25 +504,16 @@ __global__ __launch_bounds__(kWave, 1) void k_k2_fwd(int64_t B, int64_t N, const
 // the backward recursion of S and F) on the local element set.  Entering step n: bz, ba, bV = complete cotangents of row n;
 // S, F = state of row n; M = bS + bS^T on the local elements; bF; carry = f_{n+1}.
 // =====================================================================================================================
-// C2K2_MLDS: the cotangent state M lives in LDS (pairs of elements, lane-major: conflict-free 16-byte accesses) instead of
+// The cotangent state M lives in LDS (pairs of elements, lane-major: conflict-free 16-byte accesses) instead of
 // registers -- the reverse step has ~340 registers' worth of live values at its peak and every value beyond 256 costs
-// a move to and from the accumulation registers per step (16384 series: 10.1 against 10.9 ms)
-#ifndef C2K2_MLDS
-#define C2K2_MLDS 1
-#endif
-#ifndef C2K2_SLDS
-#define C2K2_SLDS 0   // the forward state S of the backward recursion likewise: measured, no (16384 series: 12.2 against 10.1 ms)
-#endif
+// a move to and from the accumulation registers per step (16384 series: 10.1 against 10.9 ms).  The forward state S of the backward
+// recursion stays in registers (in LDS as well: 12.2 against 10.1 ms).
 // The scalar gradients (ba, by, bt) leave the reverse sweep as SIXTEEN-row tiles -- whole aligned 128-byte lines per series (second
 // session of round 6).  With eight-row tiles the two 64-byte halves of a line were written eight steps (~30 us) apart: the line has left
 // L2 by then and the memory side merges each half on its own (a read-modify-write); tools/ubench/replay_traffic.hip, which reproduces
 // the one-lane pair's times from its memory operations alone, puts that at 11 - 15 % of the reverse sweep (profiles/r06_halflines.md).
-// C2K2_STR=8: the earlier tiles (A/B builds).
-#ifndef C2K2_STR
-#define C2K2_STR 16
-#endif
-constexpr int STR = C2K2_STR, SSTRR = STR + 1;   // rows / LDS stride (doubles) of a series in a scalar tile of the reverse sweep
-constexpr int kRevLds = (2 * SPW * RSTR + 3 * SPW * SSTRR + (C2K2_MLDS ? NL * kWave : 0) + (C2K2_SLDS ? NL * kWave : 0)) * 8;
+constexpr int STR = 16, SSTRR = STR + 1;   // rows / LDS stride (doubles) of a series in a scalar tile of the reverse sweep
+constexpr int kRevLds = (2 * SPW * RSTR + 3 * SPW * SSTRR + NL * kWave) * 8;
 
 // STR-row scalar tile of the reverse sweep -> memory: one instruction moves (64 / STR) series x (8 STR) bytes
 template <bool FULL>
@@ -605,24 +567,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   // F, bF, the accumulators of bc: this lane's local 0..3 only (every use is a half of a dot product, a half row of an output
   // or a checkpoint); bV is needed whole by the pass over the elements and is completed from the partner
   double F[4], bF[4], bVn[J];
-#if C2K2_SLDS
-  double2 *Sl = reinterpret_cast<double2 *>(tBT + SPW * SSTRR + (C2K2_MLDS ? NL * kWave : 0)) + lane;
-#else
   double S[NL];
-#endif
-#if C2K2_MLDS
   double2 *Ml = reinterpret_cast<double2 *>(tBT + SPW * SSTRR) + lane;   // elements 2q, 2q + 1 at Ml[q * kWave]
 #pragma unroll
   for (int q = 0; q < NL / 2; ++q) Ml[q * kWave] = make_double2(0.0, 0.0);
-#else
-  double M[NL];
-#pragma unroll
-  for (int e = 0; e < NL; ++e) M[e] = 0.0;
-#endif
-#if !C2K2_SLDS
 #pragma unroll
   for (int e = 0; e < NL; ++e) S[e] = 0.0;
-#endif
 #pragma unroll
   for (int j = 0; j < 4; ++j) { F[j] = 0.0; bF[j] = 0.0; bcj[j] = 0.0; }
 #pragma unroll
@@ -640,34 +590,21 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   auto load_ckpt = [&]() {   // the recorded state of a checkpointed row replaces the recursed one
     --slot;
     const double *ck = recCK + (size_t)slot * CKD * kWave;
-#if C2K2_SLDS
-#pragma unroll
-    for (int q = 0; q < NL / 2; ++q) Sl[q * kWave] = make_double2(ck[(2 * q) * kWave + lane], ck[(2 * q + 1) * kWave + lane]);
-#else
 #pragma unroll
     for (int e = 0; e < NL; ++e) S[e] = ld1s(&ck[e * kWave + lane]);
-#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j) F[j] = ld1s(&ck[(NL + j) * kWave + lane]);
   };
   auto w_fetch = [&](int64_t row, double (&wv)[J]) {
     row = row < 0 ? 0 : row;
-#ifdef C2K2_EXP_CACHED_RECORDS
-    row &= 3;
-#endif
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const double2 v = ld2s(&recW[((size_t)row * 4 + ((q + 2 * h) & 3)) * SPW + sl]);
       wv[2 * q] = v.x; wv[2 * q + 1] = v.y;
     }
   };
-#ifdef C2K2_EXP_CACHED_RECORDS   // (timing experiment: every record load hits the cache -- what is left is arithmetic and stores)
-  auto dz_fetch = [&](int64_t row) { return recDZ[(size_t)((row < 0 ? 0 : row) & 3) * SPW + sl]; };
-  auto t_fetch = [&](int64_t row) { return recT[(size_t)((row < 0 ? 0 : row) & 3) * SPW + sl]; };
-#else
   auto dz_fetch = [&](int64_t row) { return ld2s(&recDZ[(size_t)(row < 0 ? 0 : row) * SPW + sl]); };
   auto t_fetch = [&](int64_t row) { return ld1s(&recT[(size_t)(row < 0 ? 0 : row) * SPW + sl]); };
-#endif
 
   if (N >= 2) {
     // ---- prologue: bV, ba, by of the last row are pure seeds ---------------------------------------------------------------
@@ -744,29 +681,15 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
 #pragma unroll
       for (int j = 0; j < J; ++j) { x[j] = fma(ba2, u[j], bVn[j]); xs[j] = 0.0; q[j] = 0.0; bps[j] = 0.0; }
       inverses<PAIRED>(p, ip);
-#if C2K2_MLDS
       double2 mpair;
-#endif
-#if C2K2_SLDS
-      double2 spair;
-#endif
 #pragma unroll
       for (int e = 0; e < NL; ++e) {
         const int i = LI[e], j2 = LJ[e];
         const double wgt = e >= kHalfFrom ? 0.5 : 1.0;
-#if C2K2_SLDS
-        if ((e & 1) == 0) spair = Sl[(e / 2) * kWave];
-        const double sv = (e & 1) ? spair.y : spair.x;
-#else
         const double sv = S[e];
-#endif
         const double svw = e >= kHalfFrom ? 0.5 * sv : sv;
-#if C2K2_MLDS
         if ((e & 1) == 0) mpair = Ml[(e / 2) * kWave];
         double m = (e & 1) ? mpair.y : mpair.x;
-#else
-        double m = M[e];
-#endif
         xs[j2] = fma(x[i], svw, xs[j2]);
         if (j2 != i) xs[i] = fma(x[j2], svw, xs[i]);
         m = fma(-u[i], bVn[j2], m);
@@ -774,20 +697,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
         bps[j2] = fma(svw, m, bps[j2]);
         if (j2 != i) bps[i] = fma(svw, m, bps[i]);
         m *= p[i] * p[j2];
-#if C2K2_MLDS
         if (e & 1) { mpair.y = m; Ml[(e / 2) * kWave] = mpair; } else mpair.x = m;
-#else
-        M[e] = m;
-#endif
         const double mw = wgt * m;
         q[j2] = fma(wa[i], mw, q[j2]);
         if (j2 != i) q[i] = fma(wa[j2], mw, q[i]);
         const double snew = fma(-(dm * wa[i]), wa[j2], sv * (ip[i] * ip[j2]));
-#if C2K2_SLDS
-        if (e & 1) { spair.y = snew; Sl[(e / 2) * kWave] = spair; } else spair.x = snew;
-#else
         S[e] = snew;
-#endif
       }
       // from here on every vector is this lane's local 0..3; scalars are (own half) + (partner's half)
       double xst[4], qt[4], bp[4];

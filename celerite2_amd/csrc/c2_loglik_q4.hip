@@ -4,7 +4,7 @@
 // costs 0.65 of the eight-lane step: the scalar chain (reciprocal, reductions, seeds) is replicated over four lanes instead
 // of eight, a gathered vector is 12 DPP moves per 16 series instead of 14 per 8.
 //
-// Both kernels work in a SCALED FRAME between anchors 32 rows apart (see k_loglik_rev<..., SC> in c2_loglik.hip for the
+// Both kernels work in a SCALED FRAME between anchors 32 rows apart (see k_loglik_rev<..., BACK> in c2_loglik.hip for the
 // reverse sweep's derivation).  Forward (forward.hpp:105-134 + internal.hpp:135-145), with h_n = exp(c (t_n - t_ref)), t_ref
 // the time of the anchor row below:
 //     S^_n = H_n S_n H_n = S^_{n-1} + d_{n-1} w~ w~^T          (w~ = h_{n-1} W_{n-1}; no decay factors)
@@ -32,9 +32,6 @@
 namespace c2 {
 namespace q4 {
 
-#ifndef C2Q4_PAIRLINES
-#define C2Q4_PAIRLINES 1
-#endif
 constexpr int LG = 4, J = 8, SPW = kWave / LG, C = 8, A = 4;   // C rows per segment, A segments between two anchors
 constexpr int kCkD2 = 9;                                       // double2 per lane and checkpoint: SX[2][8] + F[2]
 
@@ -810,15 +807,13 @@ __global__ __launch_bounds__(kWave, 1) void k_q4_rev(int64_t B, int64_t N, const
     // The scalar gradients of a segment are an aligned run of 8 rows = HALF a 128-byte line per series.  Written when they are ready,
     // the two halves of a line reach memory eight steps apart -- the line has left L2 in between and each half is merged on the
     // memory side on its own (a read-modify-write: 11 - 15 % of the one-lane reverse sweep, profiles/r06_halflines.md).  So the
-    // UPPER half (rows 16 i + 8 ..) waits in a register per lane and stream and leaves with the lower half, back to back
-    // (C2Q4_PAIRLINES=0: as they come).
+    // UPPER half (rows 16 i + 8 ..) waits in a register per lane and stream and leaves with the lower half, back to back.
 #pragma unroll
     for (int m = 0; m < NV; ++m) {   // (slots beyond the batch hold copies of its last series: same values, same addresses)
       if (ok8[m]) {
         const double vA = oBA[ssl[m]][srow], vY = oBY[ssl[m]][srow];
         const double vT = srow == 0 ? oBT[bq][ssl[m]][C - 1] : oBT[bq ^ 1][ssl[m]][srow - 1];
         const bool tv = n_lo + C - 1 + srow < N;
-#if C2Q4_PAIRLINES
         if (k & 1) {                       // rows 8 k ..: the upper half of their lines
           hA[m] = vA; hY[m] = vY; hAok[m] = srow < cnt;
         } else {
@@ -835,13 +830,6 @@ __global__ __launch_bounds__(kWave, 1) void k_q4_rev(int64_t B, int64_t N, const
           if (hTok[m]) btb8[m][n_lo + 2 * C - 1 + srow] = hT[m];
           hTok[m] = false;
         }
-#else
-        if (srow < cnt) {
-          bab8[m][n_lo - 1 + srow] = vA;
-          byb8[m][n_lo - 1 + srow] = vY;
-        }
-        if (tv) btb8[m][n_lo + C - 1 + srow] = vT;
-#endif
       }
     }
     bq ^= 1;
@@ -850,9 +838,7 @@ __global__ __launch_bounds__(kWave, 1) void k_q4_rev(int64_t B, int64_t N, const
 #pragma unroll
   for (int m = 0; m < NV; ++m) {   // the rows of bt the first segment left behind (1 .. C - 1; row 0 below) + their line's upper half
     if (ok8[m] && srow >= 1 && srow < N) btb8[m][srow] = oBT[bq ^ 1][ssl[m]][srow - 1];
-#if C2Q4_PAIRLINES
     if (ok8[m] && hTok[m]) btb8[m][C + srow] = hT[m];
-#endif
   }
   if (nseg == 0) {   // N == 1
     const double rd0 = 1.0 / carDZ.x, cz = carDZ.y;

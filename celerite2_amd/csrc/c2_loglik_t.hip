@@ -58,9 +58,6 @@ __device__ __forceinline__ constexpr bool piece_in(int p) { return JS == J || (p
 #ifndef C2T_C
 #define C2T_C 32
 #endif
-#ifndef C2T_M2
-#define C2T_M2 1   // the rank-2 update of M in two fma per element (0: three, x in the registers of bV)
-#endif
 constexpr int C = C2T_C;             // checkpoint interval (rows)
 constexpr double kGuard = kBackwardGuard;  // largest allowed max_j c_j * (t_end - t_start) of a segment
 constexpr int RT = 16 / J;           // rows per tile of the width-J streams: one aligned 128-byte line per series
@@ -81,16 +78,7 @@ __host__ __device__ constexpr int sym(int i, int j) { return i <= j ? sidx(i, j)
 //   CK  : [wave][slot][NS + J][64] double (state after row n_slot: S packed, F), slots in the order written
 //   CKR : [wave][n] int32                 (slot of the checkpoint of row n, meaningful where the row carries one -- which is
 //                                          the sign of the row's d in DZ)
-// C2T_TM = 1: the per-row records (W, DZ, T) are TIME-major across the wavefronts of the launch -- [n][wave][..][64] -- so
-// that the rows the resident wavefronts touch at any moment (they walk the series in near lockstep) form ONE contiguous
-// stretch of memory, spread evenly over every HBM stack / channel whatever the allocator's placement; 0: [wave][n][..][64]
-// (each wavefront its own stretch, 16 MB apart at the bench shape).
-#ifndef C2T_TM
-#define C2T_TM 0
-#endif
-#ifndef C2T_RECFIRST
-#define C2T_RECFIRST 0
-#endif
+// The per-row records (W, DZ, T) are wave-major, [wave][n][..][64]: each wavefront its own stretch (16 MB apart at the bench shape).
 struct Rec {
   size_t w, dz, ck, ckr, t, total;  // offsets / total in doubles
   int64_t nck;                      // checkpoint slots per wavefront (capacity)
@@ -139,7 +127,7 @@ struct RowIOT {
 };
 using RowIO = RowIOT<false>;
 
-// Streaming hints (C2T_NT).  Every byte of this pair is touched ONCE -- inputs, records, gradients -- so nothing it streams needs to
+// Streaming hints.  Every byte of this pair is touched ONCE -- inputs, records, gradients -- so nothing it streams needs to
 // stay in L2; what DOES need to stay is the half-written lines of the scalar gradients: ba, by, bt leave the reverse sweep as 64-byte
 // runs, and the other half of each 128-byte line follows eight steps (~30 us, ~20 MB of traffic through a 4 MB L2) later.  Evicted in
 // between, each half is merged on the memory side on its own (read-modify-write).  tools/ubench/replay_traffic.hip -- the pair's memory
@@ -148,26 +136,13 @@ using RowIO = RowIOT<false>;
 // scalar tiles need 13 KB more per wavefront): 15.8 -> 13.8 ms.  Level 1: the records and the width-J gradients (round 2's flag, then
 // measured 'no gain' -- with the inputs still displacing the half lines).  Level 2 (default since round 6): the API rows and scalars
 // the passes read as well.  Bench step, six alternating fresh processes on one box: 30.06 (28.8 - 31.1) -> 27.75 ms (27.2 - 28.9)
-// (profiles/r06_halflines.md).  0: plain accesses (A/B builds).
-#ifndef C2T_NT
-#define C2T_NT 2
-#endif
+// (profiles/r06_halflines.md).
 typedef double d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 ld2_in(const double2 *p) {
-#if C2T_NT >= 2
   const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(p));
   return make_double2(v.x, v.y);
-#else
-  return *p;
-#endif
 }
-__device__ __forceinline__ double ld1_in(const double *p) {
-#if C2T_NT >= 2
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+__device__ __forceinline__ double ld1_in(const double *p) { return __builtin_nontemporal_load(p); }
 // global -> registers: rows n0 .. n0+RT-1 (clamped to [0, N-1]) of every series
 // (staging registers are plain doubles: arrays of double2 end up in scratch)
 template <class IO>
@@ -320,37 +295,17 @@ __device__ __forceinline__ double afetch(int lo, int hi) {
 #ifndef C2T_MLDS
 #define C2T_MLDS 0   // half of M in LDS for the coefficient-level sweep: measured, 3 - 5 % SLOWER (20.4 against 19.8 ms at 65536 series)
 #endif
-// the records (written once by the forward pass, read once by the reverse sweep) and the width-J gradients: C2T_NT >= 1
+// the records (written once by the forward pass, read once by the reverse sweep) and the width-J gradients
 __device__ __forceinline__ double2 ld2_stream(const double2 *p) {
-#if C2T_NT
   const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(p));
   return make_double2(v.x, v.y);
-#else
-  return *p;
-#endif
 }
-__device__ __forceinline__ double ld1_stream(const double *p) {
-#if C2T_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+__device__ __forceinline__ double ld1_stream(const double *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st2_stream(double2 *p, double2 v) {
-#if C2T_NT
   d2v w; w.x = v.x; w.y = v.y;
   __builtin_nontemporal_store(w, reinterpret_cast<d2v *>(p));
-#else
-  *p = v;
-#endif
 }
-__device__ __forceinline__ void st1_stream(double *p, double v) {
-#if C2T_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void st1_stream(double *p, double v) { __builtin_nontemporal_store(v, p); }
 
 // p_j = exp(c_j dt).  PAIRED: c_{2k} == c_{2k+1} for every series of the wavefront (complex terms, terms.py:171-173):
 // one exponential per pair -- bit-identical to evaluating both.
@@ -494,22 +449,12 @@ __device__ __forceinline__ void fwd_body(int64_t B, int64_t N, const double *__r
   for (int j = 0; j < J; ++j) cmax = fmax(cmax, cj[j]);
 
   // records of this wavefront
-#if C2T_TM
-  const size_t rsW = (size_t)gridDim.x * (J / 2) * kWave, rs1 = (size_t)gridDim.x * kWave;   // row strides (elements)
-  double2 *recW = REC ? reinterpret_cast<double2 *>(rec + R.w) + (size_t)blockIdx.x * (J / 2) * kWave : nullptr;
-  double2 *recDZ = REC ? reinterpret_cast<double2 *>(rec + R.dz) + (size_t)blockIdx.x * kWave : nullptr;
-#else
   constexpr size_t rsW = (size_t)(J / 2) * kWave, rs1 = kWave;
   double2 *recW = REC ? reinterpret_cast<double2 *>(rec + R.w + (size_t)blockIdx.x * N * J * kWave) : nullptr;
   double2 *recDZ = REC ? reinterpret_cast<double2 *>(rec + R.dz + (size_t)blockIdx.x * N * 2 * kWave) : nullptr;
-#endif
   double *recCK = REC ? rec + R.ck + (size_t)blockIdx.x * R.nck * (NS + J) * kWave : nullptr;
   int32_t *recCKR = REC ? reinterpret_cast<int32_t *>(rec + R.ckr + (size_t)blockIdx.x * (((size_t)N + 1) / 2)) : nullptr;
-#if C2T_TM
-  double *recT = REC ? rec + R.t + (size_t)blockIdx.x * kWave : nullptr;  // the grid, lane-major like (d, z)
-#else
   double *recT = REC ? rec + R.t + (size_t)blockIdx.x * N * kWave : nullptr;  // the grid, lane-major like (d, z)
-#endif
 
   // ---- row 0 --------------------------------------------------------------------------------------------------
   double S[NS];
@@ -837,22 +782,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   double *tACC = lds;   // coefficient-level form: takes the place of the U tile (64 x 14 <= 64 x 18 doubles)
   const double *Ub = U + b0 * N * JS;
   double *bUb = bU + b0 * N * JS, *bVb = bV + b0 * N * JS, *bab = ba + b0 * N, *byb = by + b0 * N, *btb = bt + b0 * N;
-#if C2T_TM
-  const size_t rsW = (size_t)gridDim.x * (J / 2) * kWave, rs1 = (size_t)gridDim.x * kWave;   // row strides (elements)
-  const double2 *recW = reinterpret_cast<const double2 *>(rec + R.w) + (size_t)blockIdx.x * (J / 2) * kWave;
-  const double2 *recDZ = reinterpret_cast<const double2 *>(rec + R.dz) + (size_t)blockIdx.x * kWave;
-#else
   constexpr size_t rsW = (size_t)(J / 2) * kWave, rs1 = kWave;
   const double2 *recW = reinterpret_cast<const double2 *>(rec + R.w + (size_t)blockIdx.x * N * J * kWave);
   const double2 *recDZ = reinterpret_cast<const double2 *>(rec + R.dz + (size_t)blockIdx.x * N * 2 * kWave);
-#endif
   const double *recCK = rec + R.ck + (size_t)blockIdx.x * R.nck * (NS + J) * kWave;
   const int32_t *recCKR = reinterpret_cast<const int32_t *>(rec + R.ckr + (size_t)blockIdx.x * (((size_t)N + 1) / 2));
-#if C2T_TM
-  const double *recT = rec + R.t + (size_t)blockIdx.x * kWave;
-#else
   const double *recT = rec + R.t + (size_t)blockIdx.x * N * kWave;
-#endif
   const bool failed = flag[b] != 0;  // NaN gradients for a failed factorisation (see k_loglik_rev)
   const double nan = __builtin_nan("");
 
@@ -1053,25 +988,14 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
       C2T_TICK(4);
       // ---- fixed part: U_n into its tile, requests for two steps ahead ------------------------------------------------
       double wb[J];
-#if C2T_RECFIRST
-      // the records of the row below are wanted one step from now, the tile of U rows two: request them in that order (the
-      // counter of outstanding memory operations retires in order -- behind the 64 scattered lines of a U tile the records
-      // would wait for the slowest of them)
-      w_fetch(n - 2, wb);
-      const double2 dzb = dz_fetch(n - 2);
-      const double tb2 = t_fetch(n - 2);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       if constexpr (!TERMS && STAGE) {
         lds_order();
         row_stage(tU, lane, su);
         row_fetch(Ub, N, n - 2 * RT + 1, io, su);
       }
-#if !C2T_RECFIRST
       w_fetch(n - 2, wb);
       const double2 dzb = dz_fetch(n - 2);
       const double tb2 = t_fetch(n - 2);
-#endif
       if constexpr (!TERMS && STAGE) lds_order();
 
       // ---- the step ---------------------------------------------------------------------------------------------
@@ -1113,14 +1037,9 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
       const double dm = fabs(dza.x), rdm = rcp_nr(dm), zm = dza.y;
       bool ckm = false;
       if constexpr (XCK) ckm = __builtin_amdgcn_readfirstlane(__double2hiint(dza.x)) < 0;   // row n-1 carries a checkpoint
-#if C2T_M2
       // (x_j - 2 ba u_j = bV_j, so M -= u_i x_j + x_i u_j - 2 ba u_i u_j = u_i bV_j + x_i u_j: two fma per element, with
       // bV kept next to x for the length of the pass)
       double x[J];
-#else
-      // (bV_i = x_i - 2 ba u_i, so M -= u_i x_j + x_i u_j - 2 ba u_i u_j: x takes the registers of bV)
-      double (&x)[J] = bVn;
-#endif
       double xs[J], q[J];
       const double ba2 = 2.0 * ban;
 #pragma unroll
@@ -1141,14 +1060,8 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
           }
           xs[j2] = fma(x[i], sv, xs[j2]);
           if (j2 != i) xs[i] = fma(x[j2], sv, xs[i]);
-#if C2T_M2
           m = fma(-u[i], bVn[j2], m);
           m = fma(-x[i], u[j2], m);
-#else
-          m = fma(-u[i], x[j2], m);
-          m = fma(-x[i], u[j2], m);
-          m = fma(ba2 * u[i], u[j2], m);
-#endif
           bp[j2] = fma(sv, m, bp[j2]);
           if (j2 != i) bp[i] = fma(sv, m, bp[i]);
           m *= p[i] * p[j2];

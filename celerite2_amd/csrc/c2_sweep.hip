@@ -15,9 +15,6 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 
-#ifndef C2_SWEEP1_PAIRLINES
-#define C2_SWEEP1_PAIRLINES 1
-#endif
 namespace c2 {
 
 // LN >= 0 (G = J = 8, U and V 16-byte aligned): the two width-8 rows of a step are requested as halves of the aligned
@@ -55,7 +52,7 @@ __global__ __launch_bounds__(kWave) void k_sweep1(int64_t B, int64_t N, int Jrt,
   // Z = Y (solve, forward.hpp:168,205) / Z = 0 (matmul called with zero_z) / Z unchanged (matmul accumulate) and the zero
   // workspace row (internal.hpp:127 / :170) like any other step -- so blocks cover positions [R b, R b + R) and the
   // transposed requests of t, y, z are whole aligned runs (profiles/r05_alignment.md).
-  constexpr bool HOLDZ = C2_SWEEP1_PAIRLINES && G == 8 && R == 8 && NV == 1 && !PAD;
+  constexpr bool HOLDZ = G == 8 && R == 8 && NV == 1 && !PAD;
   double hZ = 0.0;
   int64_t hZrow = 0;
   bool hZok = false;
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(kWave) void k_sweep1(int64_t B, int64_t N, int Jrt,
     if constexpr (HOLDZ) {
       // (a block's run of Z is HALF a 128-byte line per series: the half the sweep reaches first waits in a register and leaves
       // with the other, back to back -- profiles/r06_halflines.md.  In-place Z == Y stays legal: the rows a held store covers were
-      // read two blocks ago.  C2_SWEEP1_PAIRLINES=0: as they come.)
+      // read two blocks ago.)
       const int64_t row = rowof(s0 + j);
       const bool ok = !CHECKED || s0 + j < N;
       const double v = sout[grp][j];
@@ -250,7 +247,7 @@ __global__ __launch_bounds__(kWave) void k_sweep1_rev(int64_t B, int64_t N, int 
   constexpr double sgn = SOLVE ? -1.0 : 1.0;
   auto rowof = [&](int64_t q) { return LOWER ? N - 1 - q : q; };
 
-  constexpr bool HOLD = C2_SWEEP1_PAIRLINES && G == 8 && R == 8 && NV == 1 && !PAD;
+  constexpr bool HOLD = G == 8 && R == 8 && NV == 1 && !PAD;
   double hT = 0.0, hY = 0.0;
   int64_t hldrow = 0;
   bool hTok = false, hYok = false;
@@ -414,7 +411,7 @@ __global__ __launch_bounds__(kWave) void k_sweep1_rev(int64_t B, int64_t N, int 
     if constexpr (HOLD) {
       // (a block's run of bt / bY is HALF a 128-byte line per series; written when ready, the two halves of a line reach memory
       // eight steps apart and are merged on the memory side one by one -- profiles/r06_halflines.md.  The half the sweep reaches
-      // first waits in a register per stream and leaves with the other, back to back.  C2_SWEEP1_PAIRLINES=0: as they come.)
+      // first waits in a register per stream and leaves with the other, back to back.)
       const int64_t row = rowof(u0 + j);
       const bool okT = !CHECKED || u0 + j + 1 < N, okY = !CHECKED || u0 + j < N;
       const double vT = sout[grp][j], vY = j == 0 ? soutY[s ^ 1][grp][R - 1] : soutY[s][grp][j - 1];

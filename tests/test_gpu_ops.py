@@ -543,20 +543,15 @@ def test_group_mapping_backward_recursion_and_its_fallback(ops, oracle, monkeypa
         llo, go, flo = oracle.loglik_grad_batched(tg, c, a, U, V, y, nthreads=2)
         assert int(np.abs(flo).sum()) == 0
         args = dev(tg, c, a, U, V, y)
-        # (backward recursion in the scaled frame -- the default --, in the plain frame, and the replay alone)
-        # ... and the scaled form with the rows of U, V, bU, bV as 128-byte lines (C2_LOGLIK_LINES=1: J = 8, even N; off by default)
-        for back, scaled, lines in (("1", "1", "0"), ("1", "0", "0"), ("0", "1", "0"), ("1", "1", "1")):
+        # (backward recursion in the scaled frame -- the default -- and the replay alone)
+        for back in ("1", "0"):
             monkeypatch.setenv("C2_LOGLIK_BACK", back)
-            monkeypatch.setenv("C2_LOGLIK_SCALED", scaled)
-            monkeypatch.setenv("C2_LOGLIK_LINES", lines)
             ll, grads, flag = ops.loglik_grad(*args)
             assert int(flag.abs().sum()) == 0
             close(ll, llo)
             for g, e in zip(grads, go):
                 close(g, e, floor=4e-12)
         monkeypatch.delenv("C2_LOGLIK_BACK")
-        monkeypatch.delenv("C2_LOGLIK_SCALED")
-        monkeypatch.delenv("C2_LOGLIK_LINES")
 
 
 @pytest.mark.parametrize("lanes", ["8", "4", "2", "1"])

@@ -19,7 +19,5 @@ run() {  # label, batch, env...
 run "two lanes (default)      " 32768 C2_NOP=1
 [ -n "$SHARD_AB_OLD" ] && run "one lane (round 3)       " 32768 C2_LANES=1
 run "four lanes (default)     " 16384 C2_NOP=1
-[ -n "$SHARD_AB_OLD" ] && run "8 lanes (round 4)        " 16384 C2_LANES=8 C2_LOGLIK_SCALED=0
 run "8 lanes (default)        " 8192 C2_NOP=1
-[ -n "$SHARD_AB_OLD" ] && run "8 lanes, plain frame (round 4)" 8192 C2_LOGLIK_SCALED=0
 exit 0
