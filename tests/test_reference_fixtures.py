@@ -209,7 +209,8 @@ def test_device_loglik_terms_vs_reference_gaussian_process(golden, monkeypatch, 
     complex) against the log-likelihood the reference's numpy GaussianProcess returned for the same series -- through the composed
     chain and through every kernel that forms the rows in the lanes (one / two / four / eight lanes per series; width 4: one lane
     and the group of four), 70 copies of the series so that whole and partial groups of 64 are exercised.  The gradient call must
-    return the same log-likelihood; its gradients are pinned against the oracle chain in tests/test_gpu_terms.py."""
+    return the same log-likelihood, and its nine gradients the exact ones of the dense kernel matrix built on the same
+    coefficients (oracle/exact.py)."""
     import torch
     from celerite2_amd import ops
     if case == "gprot" and lanes in ("two", "four"):
@@ -228,6 +229,12 @@ def test_device_loglik_terms_vs_reference_gaussian_process(golden, monkeypatch, 
     want = np.full(B, float(g["loglik"]))
     _close(ll, want); _close(ll2, want)
     assert all(bool(torch.isfinite(v).all()) for v in grads)
+    from oracle import exact
+    llx, gx = exact.terms_grad(*[np.atleast_1d(g["coef_" + cn]) for cn in COEF_NAMES], g["x"], g["diag"], g["y"] - g["mean"])
+    _close(np.array([llx]), np.array([float(g["loglik"])]))
+    for v, e in zip(grads, gx):
+        if e.size:
+            _close(v, np.repeat(e[None], B, axis=0))
 
 
 @pytest.mark.gpu
