@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -84,6 +84,98 @@ def log_likelihood_terms(ar, cr, ac, bc, cc, dc, x, diag, y):
     white-noise diagonal and the data -- the gradient a sampler needs, computed by the device chain of c2_terms.hip.
     Shared coefficients / times (one fewer dimension) receive the batch-summed gradient."""
     return _LogLikTerms.apply(ar, cr, ac, bc, cc, dc, x, diag, y)
+
+
+class _TermCoefficients(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, program, P, B):
+        Pd = P.detach().contiguous()
+        coefs, flag = ops.term_coefficients(program, Pd, B)
+        ctx.program, ctx.shared = program, P.dim() == 1
+        ctx.save_for_backward(Pd)
+        return coefs
+
+    @staticmethod
+    def backward(ctx, *cots):
+        (P,) = ctx.saved_tensors
+        bP = ops.term_coefficients_rev(ctx.program, P, [c.contiguous() for c in cots])
+        return None, (bP.sum(0) if ctx.shared else bP), None
+
+
+def term_coefficients(program, P, B=None):
+    """(ar, cr, ac, bc, cc, dc) (B, Jr) / (B, Jc) from the parameter matrix P (B, NP) | shared (NP,) of a term program
+    (ops.TermProgram), differentiable in P: c2_term_coefficients forward, c2_term_coefficients_rev backward (one launch each;
+    a shared P receives the batch sum).  What the reference's jax / pymc term classes give by autodiff."""
+    return _TermCoefficients.apply(program, P, B)
+
+
+class _LogLikKernel(torch.autograd.Function):
+    """noise_mean_apply -> term_coefficients -> loglik_terms[_grad] -> term_coefficients_rev / noise_mean_rev as ONE node:
+    the gradients come out of the forward call (as in _LogLikTerms), backward scales them by the incoming cotangent."""
+
+    @staticmethod
+    def forward(ctx, program, is_sigma, P, x, yerr, jitter, mean, y):
+        tens = (P, x, yerr, jitter, mean, y)
+        Pd, xd, ed, jd, md, yd = [None if v is None else v.detach().contiguous() for v in tens]
+        B = y.shape[0]
+        if not any(v is not None and v.requires_grad for v in tens):
+            diag, r = ops.noise_mean_apply(ed, jd, md, yd, yerr_is_sigma=is_sigma)
+            coefs, tflag = ops.term_coefficients(program, Pd, B)
+            ll, flag = ops.loglik_terms(*coefs, xd, diag, r)
+            return torch.where(tflag != 0, torch.full_like(ll, -float("inf")), ll)
+        ll, (bP, bj, bm, bx, bdiag, by), flag = ops.loglik_kernel_grad(program, Pd, xd, ed, jd, md, yd, yerr_is_sigma=is_sigma)
+        ctx.shared_P, ctx.shared_x = P.dim() == 1, x.dim() == 1
+        ctx.has = (jitter is not None, mean is not None)
+        # byerr = 2 yerr bdiag only when somebody asks for it
+        be = bdiag if not is_sigma else (2.0 * ed * bdiag if yerr.requires_grad else None)
+        ctx.has_e = be is not None
+        ctx.save_for_backward(flag, bP, bj, bm, bx, by, *([be] if be is not None else []))
+        return ll
+
+    @staticmethod
+    def backward(ctx, g):
+        flag, bP, bj, bm, bx, by = ctx.saved_tensors[:6]
+        be = ctx.saved_tensors[6] if ctx.has_e else None
+        zero = torch.zeros((), dtype=g.dtype, device=g.device)
+        dead = (g == 0) | (flag != 0)     # a masked-out or flagged series contributes exactly zero (_LogLikTerms.backward)
+        sc1 = lambda v: torch.where(dead, zero, v * g)
+        sc2 = lambda v: torch.where(dead[:, None], zero, v * g[:, None])
+        gP, gx = sc2(bP), sc2(bx)
+        return (None, None, gP.sum(0) if ctx.shared_P else gP, gx.sum(0) if ctx.shared_x else gx,
+                sc2(be) if be is not None else None, sc1(bj) if ctx.has[0] else None, sc1(bm) if ctx.has[1] else None, sc2(by))
+
+
+def _per_series(v, B, like):
+    """A float, a 0-d or a (B,) tensor -> (B,) (autograd sums the gradient of a shared value), None stays None."""
+    if v is None:
+        return None
+    if not torch.is_tensor(v):
+        return torch.full((B,), float(v), dtype=torch.float64, device=like.device)
+    if v.dim() == 0 or tuple(v.shape) == (1,):
+        return v.reshape(()).expand(B)
+    if tuple(v.shape) != (B,):
+        raise ValueError("Invalid shape: jitter / mean (must be a float, 0-d or (B,))")
+    return v
+
+
+def log_likelihood_kernel(kernel, x, y, *, yerr=None, diag=None, jitter=None, mean=None):
+    """Batched GP log-likelihood (B,) as a differentiable function of the HYPER-PARAMETERS: every tensor parameter of
+    `kernel` (terms.RealTerm / ComplexTerm / SHOTerm / Matern32Term / RotationTerm and their sums, with parameters given as
+    float64 device tensors, 0-d or (B,)), `jitter` (added in quadrature: diag = yerr^2 + jitter^2, or diag + jitter^2) and
+    `mean` (floats, 0-d or (B,) tensors), and x (N,) | (B, N), yerr | diag (B, N), y (B, N) when they require grad.
+    Everything between the parameters and the gradient runs on the device (csrc/c2_term_params.hip around
+    c2_loglik_terms_grad); shared parameters receive the batch-summed gradient.  A series whose factorisation fails, or whose
+    Q is on the wrong side of an SHO term's regime, has ll = -inf and contributes zero gradient; the others are untouched."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, N) is required")
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B = y.shape[0]
+    if not kernel._has_tensors():
+        raise TypeError("log_likelihood_kernel: the kernel has no tensor parameter (give its parameters as device tensors)")
+    P = kernel.parameter_matrix(B)
+    return _LogLikKernel.apply(kernel.program, yerr is not None, P, x, yerr if diag is None else diag,
+                               _per_series(jitter, B, y), _per_series(mean, B, y), y)
 
 
 def _reduce(g, like):

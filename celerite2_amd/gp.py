@@ -24,7 +24,7 @@ class LinAlgError(Exception):
 class GaussianProcess:
     def __init__(self, kernel, t=None, *, mean=0.0, **kwargs):
         self.kernel = kernel
-        self.mean = float(mean)
+        self.mean = mean if torch.is_tensor(mean) else float(mean)   # (a 0-d device tensor stays where it is: log_likelihood_kernel differentiates it)
         self._t = None
         if t is not None:
             self.compute(t, **kwargs)
@@ -92,6 +92,16 @@ class GaussianProcess:
         self._need()
         self._check_vector(y)
         return ops.loglik_grad(self._t, self._c, self._a, self._U, self._V, (y - self.mean).contiguous(), work=work)
+
+    def log_likelihood_kernel(self, y, *, jitter=None):
+        """ll (B,) of `y` as a differentiable function of the kernel's tensor hyper-parameters, of `jitter` (added in
+        quadrature to the computed diagonal) and of a tensor `mean`: autograd.log_likelihood_kernel on this GP's t, diag
+        and mean -- the coefficient-level kernels, not the matrices `compute` factored."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.log_likelihood_kernel(self.kernel, self._t, y, diag=self._diag, jitter=jitter, mean=self.mean)
 
     # -- core.py:342-376 + numpy.py:94-98 ----------------------------------------------------------------
     def apply_inverse(self, y):
@@ -228,6 +238,9 @@ class ConditionalDistribution:
 
     def _k0(self):
         """k(0) = sum ar + sum ac (terms.py:58-79 at tau = 0): a python float, or (B, 1) on the device for per-series coefficients."""
+        if self._kernel()._has_tensors():
+            co = self._kernel()._device_coefs(self.gp._diag.shape[0])[0]
+            return (co[0].sum(dim=-1) + co[2].sum(dim=-1))[:, None]
         co = self._kernel().get_coefficients()
         if all(v.ndim == 1 for v in co):
             return float(co[0].sum() + co[2].sum())

@@ -19,6 +19,8 @@ __all__ = [
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
+    "TermProgram", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
+    "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
 
 _i64 = ctypes.c_int64
@@ -550,3 +552,197 @@ def _loglik_grad_composite(t, c, a, U, V, y):
                                       _p(flag), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
     _lib.check(rc, "loglik_grad_composite")
     return ll, out, flag
+
+
+# ---- term hyper-parameters on the device (csrc/c2_term_params.hip) --------------------------------------------------------
+class _TermRec(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("par", ctypes.c_int32), ("regime", ctypes.c_int32), ("jr", ctypes.c_int32),
+                ("jc", ctypes.c_int32), ("col", ctypes.c_int32 * 5), ("eps", ctypes.c_double)]
+
+
+class _TermProgram(ctypes.Structure):
+    _fields_ = [("nterms", ctypes.c_int32), ("np", ctypes.c_int32), ("Jr", ctypes.c_int32), ("Jc", ctypes.c_int32),
+                ("term", _TermRec * 16)]
+
+
+_KINDS = {"real": (0, 2, 1, 0), "complex": (1, 4, 0, 1), "sho": (2, 3, None, None), "matern32": (3, 2, 0, 1),
+          "rotation": (4, 5, 0, 2)}   # name -> (C2_TERM_*, parameters, real slots, complex slots)
+_REGIMES = {"under": (0, 0, 1), "over": (1, 2, 0), "mixed": (2, 2, 1)}   # name -> (C2_SHO_*, real slots, complex slots)
+SHO_SIGMA, SHO_RHO, SHO_TAU = 1, 2, 4
+
+
+class TermProgram:
+    """The flattened sum of terms the kernels walk (c2_term_program, celerite2_amd.h): built ONCE from a list of records
+    `dict(kind=, cols=, par=0, regime=None, eps=)` and passed to the kernels by value.  `kind` is "real" (cols a, c),
+    "complex" (a, b, c, d), "sho" (S0|sigma, w0|rho, Q|tau; `par` = OR of SHO_SIGMA / SHO_RHO / SHO_TAU; `regime` "under" |
+    "over" | "mixed"), "matern32" (sigma, rho) or "rotation" (sigma, period, Q0, dQ, f); `cols` index the parameter matrix
+    P (B, NP) | (NP,).  Coefficient slots follow program order, reals and complex terms each concatenated
+    (TermSum.get_coefficients).  Jr + 2 Jc <= 32."""
+
+    def __init__(self, records, NP):
+        if not 1 <= len(records) <= 16:
+            raise ValueError("a term program holds 1 .. 16 terms (got %d)" % len(records))
+        self.records = [dict(r) for r in records]
+        self.NP = int(NP)
+        c = _TermProgram()
+        jr = jc = 0
+        for i, r in enumerate(self.records):
+            if r["kind"] not in _KINDS:
+                raise ValueError("unknown term kind %r" % (r["kind"],))
+            kind, npar, wr, wc = _KINDS[r["kind"]]
+            regime = 0
+            if r["kind"] == "sho":
+                if r.get("regime") not in _REGIMES:
+                    raise ValueError("SHO regime must be 'under', 'over' or 'mixed'")
+                regime, wr, wc = _REGIMES[r["regime"]]
+            cols = [int(k) for k in r["cols"]]
+            if len(cols) != npar or any(not 0 <= k < self.NP for k in cols):
+                raise ValueError("term %d (%s): needs %d parameter columns in [0, %d)" % (i, r["kind"], npar, self.NP))
+            t = c.term[i]
+            t.kind, t.par, t.regime, t.jr, t.jc = kind, int(r.get("par") or 0), regime, jr, jc
+            for k, v in enumerate(cols):
+                t.col[k] = v
+            eps = r.get("eps")
+            t.eps = float((0.01 if r["kind"] == "matern32" else 1e-5) if eps is None else eps)
+            r.update(jr=jr, jc=jc, eps=t.eps, par=t.par)
+            jr += wr
+            jc += wc
+        c.nterms, c.np, c.Jr, c.Jc = len(self.records), self.NP, jr, jc
+        self.Jr, self.Jc = jr, jc
+        if jr + 2 * jc > 32:
+            raise ValueError("term program: width %d not supported (the coefficient-level entry points take J <= 32)" % (jr + 2 * jc))
+        self._c = c
+
+    @property
+    def width(self):
+        return self.Jr + 2 * self.Jc
+
+
+def _program_P(program, P):
+    if P.dim() not in (1, 2):
+        raise ValueError("Invalid shape: P (must be (NP,) or (B, NP))")
+    _chk(P)
+    if P.shape[-1] != program.NP:
+        raise ValueError("Invalid shape: P (got %s, expected (%d,) or (B, %d))" % (tuple(P.shape), program.NP, program.NP))
+
+
+def term_coefficients(program, P, B=None, *, out=None, flag=None):
+    """P (B, NP) | shared (NP,) (then `B` says how many series) -> ((ar, cr, ac, bc, cc, dc), flag): the coefficients in the
+    layout loglik_terms takes, (B, Jr) / (B, Jc), and flag (B,) int32 (nonzero: an SHO series on the wrong side of its regime)."""
+    _program_P(program, P)
+    B = P.shape[0] if P.dim() == 2 else B
+    if B is None:
+        raise ValueError("term_coefficients: a shared P needs the batch size B")
+    _shape("P", P, (program.NP,), (B, program.NP))
+    dev = P.device
+    Jr, Jc = program.Jr, program.Jc
+    shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4
+    if out is None:
+        out = [torch.empty(sh, dtype=torch.float64, device=dev) for sh in shapes]
+    else:
+        _chk(*out)
+        for nm, o, sh in zip(("ar", "cr", "ac", "bc", "cc", "dc"), out, shapes):
+            _shape(nm, o, sh)
+    flag = torch.empty(B, dtype=torch.int32, device=dev) if flag is None else flag
+    rc = _lib.load().c2_term_coefficients(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
+                                          *_coef_ptrs(*out, Jr, Jc), _p(flag), _stream())
+    _lib.check(rc, "term_coefficients")
+    return tuple(out), flag
+
+
+def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=None, ll=None, out=None):
+    """The reverse of term_coefficients: cotangents (bar, bcr, bac, bbc, bcc, bdc), (B, Jr) / (B, Jc), -> bP (B, NP), per series
+    also for a shared P.  `tflag` (term_coefficients' flag), `lflag` (loglik_terms_grad's flag) and `ll`, when given, are
+    settled on the device: a wrong-regime series gets a zero row, ll = -inf and lflag = -2; a failed factorisation a zero row."""
+    _program_P(program, P)
+    Jr, Jc = program.Jr, program.Jc
+    cot = list(cotangents)
+    if len(cot) != 6:
+        raise ValueError("Invalid shape: cotangents (six tensors)")
+    B = cot[0].shape[0] if Jr else cot[2].shape[0]
+    _shape("P", P, (program.NP,), (B, program.NP))
+    _chk(*cot)
+    for nm, o, w in zip(("bar", "bcr", "bac", "bbc", "bcc", "bdc"), cot, (Jr, Jr, Jc, Jc, Jc, Jc)):
+        _shape(nm, o, (B, w))
+    bP = torch.empty((B, program.NP), dtype=torch.float64, device=P.device) if out is None else out
+    _chk(bP)
+    _shape("bP", bP, (B, program.NP))
+    for nm, f in (("tflag", tflag), ("lflag", lflag)):
+        if f is not None and (f.dtype != torch.int32 or tuple(f.shape) != (B,) or not f.is_contiguous()):
+            raise ValueError("Invalid shape: %s (must be (B,) int32)" % nm)
+    _shape("ll", ll, (B,))
+    rc = _lib.load().c2_term_coefficients_rev(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
+                                              *_coef_ptrs(*cot, Jr, Jc), _p(tflag), _p(lflag), _p(ll), _p(bP), _stream())
+    _lib.check(rc, "term_coefficients_rev")
+    return bP
+
+
+def noise_mean_apply(yerr, jitter, mean, y, *, yerr_is_sigma=True, out=None):
+    """diag = yerr^2 + jitter^2 (`yerr_is_sigma=False`: yerr is already a variance, diag = yerr + jitter^2) and r = y - mean in
+    one pass.  yerr, y (B, N); jitter, mean (B,) or None (= 0).  Returns (diag, r); `out` = two (B, N) tensors to write into."""
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B, N = y.shape
+    diag, r = (torch.empty_like(y), torch.empty_like(y)) if out is None else out
+    _chk(yerr, jitter, mean, y, diag, r)
+    _shape("yerr", yerr, (B, N)); _shape("jitter", jitter, (B,)); _shape("mean", mean, (B,))
+    _shape("diag", diag, (B, N)); _shape("r", r, (B, N))
+    rc = _lib.load().c2_noise_mean_apply(_i64(B), _i64(N), _p(yerr), ctypes.c_int(1 if yerr_is_sigma else 0), _p(jitter),
+                                         _p(mean), _p(y), _p(diag), _p(r), _stream())
+    _lib.check(rc, "noise_mean_apply")
+    return diag, r
+
+
+def noise_mean_rev(jitter, bdiag, by, *, flag=None, out=None):
+    """bjitter = 2 jitter sum_n bdiag, bmean = -sum_n by, (B,) each, in one pass over bdiag and by (B, N) with a fixed
+    summation order (two runs give identical bits).  jitter (B,) or None (bjitter = 0); a series with flag != 0 gets zeros."""
+    if by.dim() != 2:
+        raise ValueError("Invalid shape: by (must be (B, N))")
+    B, N = by.shape
+    bj, bm = (torch.empty(B, dtype=torch.float64, device=by.device) for _ in range(2)) if out is None else out
+    _chk(jitter, bdiag, by, bj, bm)
+    _shape("jitter", jitter, (B,)); _shape("bdiag", bdiag, (B, N)); _shape("bjitter", bj, (B,)); _shape("bmean", bm, (B,))
+    if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (B,)):
+        raise ValueError("Invalid shape: flag (must be (B,) int32)")
+    rc = _lib.load().c2_noise_mean_rev(_i64(B), _i64(N), _p(jitter), _p(bdiag), _p(by), _p(flag), _p(bj), _p(bm), _stream())
+    _lib.check(rc, "noise_mean_rev")
+    return bj, bm
+
+
+def loglik_kernel_workspace(program, B, N, device):
+    """Caller-owned buffers of loglik_kernel_grad, reusable across calls of the same shape (and required for graph capture):
+    a dict with the scratch of loglik_terms_grad, the six coefficient arrays and their cotangents, diag, r and the term flag."""
+    f64 = dict(dtype=torch.float64, device=device)
+    Jr, Jc = program.Jr, program.Jc
+    shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4
+    return {"terms": loglik_terms_workspace(B, N, Jr, Jc, device), "coefs": [torch.empty(sh, **f64) for sh in shapes],
+            "cots": [torch.empty(sh, **f64) for sh in shapes], "diag": torch.empty((B, N), **f64),
+            "r": torch.empty((B, N), **f64), "tflag": torch.empty(B, dtype=torch.int32, device=device)}
+
+
+def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=True, work=None, out=None):
+    """Hyper-parameters to log-likelihood and gradient in one stream-ordered chain, no host traffic (graph-capturable with
+    caller-owned `work` = loglik_kernel_workspace(...) and `out` = a previous call's six gradient tensors):
+    noise_mean_apply -> term_coefficients -> loglik_terms_grad -> term_coefficients_rev / noise_mean_rev.
+    P (B, NP) | (NP,); x (N,) | (B, N); yerr, y (B, N); jitter, mean (B,) or None.
+    Returns (ll, (bP, bjitter, bmean, bx, bdiag, by), flag): bP (B, NP), bjitter, bmean (B,) per series; bdiag is the
+    cotangent of diag = yerr^2 + jitter^2 (byerr = 2 yerr bdiag is the caller's).  flag: 0, the first failing row of the
+    factorisation, or -2 for an SHO series on the wrong side of its regime; a flagged series has ll = -inf and ZERO bP,
+    bjitter, bmean (its rows of bx, bdiag, by are what loglik_terms_grad left there)."""
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B, N = y.shape
+    dev = y.device
+    if work is None:
+        work = loglik_kernel_workspace(program, B, N, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    if out is None:
+        out = (torch.empty((B, program.NP), **f64), torch.empty(B, **f64), torch.empty(B, **f64), torch.empty((B, N), **f64),
+               torch.empty((B, N), **f64), torch.empty((B, N), **f64))
+    bP, bj, bm, bx, bdiag, by = out
+    diag, r = noise_mean_apply(yerr, jitter, mean, y, yerr_is_sigma=yerr_is_sigma, out=(work["diag"], work["r"]))
+    coefs, tflag = term_coefficients(program, P, B, out=work["coefs"], flag=work["tflag"])
+    ll, _, flag = loglik_terms_grad(*coefs, x, diag, r, work=work["terms"], out=tuple(work["cots"]) + (bx, bdiag, by))
+    term_coefficients_rev(program, P, work["cots"], tflag=tflag, lflag=flag, ll=ll, out=bP)
+    noise_mean_rev(jitter, bdiag, by, flag=flag, out=(bj, bm))
+    return ll, (bP, bj, bm, bx, bdiag, by), flag

@@ -6,6 +6,12 @@ A minimal mirror of the reference's term algebra (python/celerite2/terms.py): ea
 `get_celerite_matrices(x, diag)` fills c with the reference's interleaved layout (terms.py:171-173) and runs
 the c2_get_celerite_matrices kernel (driver.cpp:422-477) for (a, U, V).  Parameters may be python floats
 (one kernel shared by the batch) or 1-D arrays of length B (one hyper-parameter draw per series).
+
+Parameters may also be float64 torch TENSORS on the device, 0-d (shared) or (B,), with or without requires_grad: the
+reference's jax / pymc term classes (python/celerite2/jax/terms.py, pymc/terms.py) on this backend.  A kernel with any
+tensor parameter is flattened ONCE into a term program (ops.TermProgram); `coefficients(B)` forms its six coefficient
+arrays on the device by one kernel (csrc/c2_term_params.hip), differentiable in every tensor parameter, and nothing is
+read back to the host.  With floats / numpy arrays every path below runs as it always did.
 """
 import numpy as np
 
@@ -14,6 +20,10 @@ __all__ = ["Term", "TermSum", "RealTerm", "ComplexTerm", "SHOTerm", "Matern32Ter
 
 def _col(x):
     return np.atleast_1d(np.asarray(x, dtype=np.float64))
+
+
+def _is_tensor(v):
+    return hasattr(v, "requires_grad") and hasattr(v, "device")
 
 
 class Term:
@@ -27,8 +37,83 @@ class Term:
 
     @property
     def width(self):
+        if self._has_tensors():
+            return self.program.width
         ar, _, ac, _, _, _ = self.get_coefficients()
         return ar.shape[-1] + 2 * ac.shape[-1]
+
+    # -- tensor parameters: the device path -------------------------------------------------------------------------
+    def _records(self, add):
+        """The term's records for ops.TermProgram; `add(value)` registers a parameter and returns its column of P."""
+        raise NotImplementedError
+
+    def _has_tensors(self):
+        return any(_is_tensor(v) or (isinstance(v, tuple) and any(_is_tensor(w) for w in v)) for v in self.__dict__.values())
+
+    def _no_host(self):
+        if self._has_tensors():
+            raise TypeError("this kernel has tensor parameters: its coefficients live on the device -- use coefficients(B)")
+
+    def _build_program(self):
+        cached = self.__dict__.get("_program")
+        if cached is None:
+            from . import ops
+
+            values = []
+
+            def add(v):
+                for k, w in enumerate(values):   # the SAME tensor in two terms reads one column
+                    if w is v and _is_tensor(v):
+                        return k
+                values.append(v)
+                return len(values) - 1
+
+            records = self._records(add)
+            cached = self.__dict__["_program"] = (ops.TermProgram(records, len(values)), values)
+        return cached
+
+    @property
+    def program(self):
+        """The flattened kernel (ops.TermProgram), built once."""
+        return self._build_program()[0]
+
+    def parameter_matrix(self, B=None):
+        """The parameters as ONE float64 device matrix, columns in program order: (NP,) when every parameter is shared
+        (a float or a 0-d tensor), else (B, NP).  Formed by torch on the device, so gradients w.r.t. P reach the tensors.
+        (Floats / numpy arrays given next to tensors are uploaded on every call; give tensors to keep the host out of it.)"""
+        import torch
+
+        _, values = self._build_program()
+        device = next(v.device for v in values if _is_tensor(v))
+        cols = []
+        for v in values:
+            if not _is_tensor(v):
+                v = torch.as_tensor(np.asarray(v, dtype=np.float64), device=device)
+            if v.dtype != torch.float64 or v.dim() > 1:
+                raise ValueError("term parameters must be float64 tensors, 0-d or (B,)")
+            cols.append(v.reshape(()) if v.numel() == 1 else v)
+        nb = {int(v.shape[0]) for v in cols if v.dim() == 1}
+        if len(nb) > 1 or (nb and B is not None and nb != {B}):
+            raise ValueError("per-series parameters disagree on the batch size: %s" % sorted(nb | ({B} if B else set())))
+        if not nb:
+            return torch.stack(cols)
+        n = nb.pop()
+        return torch.stack([v.expand(n) for v in cols], dim=1)
+
+    def coefficients(self, B):
+        """(ar, cr, ac, bc, cc, dc), (B, Jr) / (B, Jc) device tensors by c2_term_coefficients, differentiable.  A series on
+        the wrong side of an SHO regime raises nothing here (no read-back): autograd.log_likelihood_kernel gives it -inf."""
+        from . import autograd
+
+        return autograd.term_coefficients(self.program, self.parameter_matrix(B), B)
+
+    def _device_coefs(self, B):
+        """Detached device coefficients + the interleaved c of terms.py:171-173, for the matrix-level paths."""
+        import torch
+
+        co = [v.detach() for v in self.coefficients(B)]
+        c = torch.cat([co[1], co[4].repeat_interleave(2, dim=-1)], dim=-1)
+        return co, c
 
     def get_value(self, tau):
         """k(tau) (terms.py:58-79), numpy, for dense cross-checks; shared coefficients only."""
@@ -75,9 +160,13 @@ class Term:
         cross-covariances `KxsT`, `k(0)` and `k(xs - xs')` (core.py:57-66, 134-150)."""
         import torch
 
-        host = self.get_coefficients()
-        batched = any(np.ndim(v) == 2 for v in host)
-        (ar, cr, ac, bc, cc, dc) = self._dev_coefs(tau.device, tau.shape[0])[0][:6] if batched else host
+        if self._has_tensors():
+            batched = True
+            ar, cr, ac, bc, cc, dc = self._device_coefs(tau.shape[0])[0]
+        else:
+            host = self.get_coefficients()
+            batched = any(np.ndim(v) == 2 for v in host)
+            (ar, cr, ac, bc, cc, dc) = self._dev_coefs(tau.device, tau.shape[0])[0][:6] if batched else host
         tau = tau.abs()
         extra = (1,) * (tau.dim() - 1)
 
@@ -101,6 +190,9 @@ class Term:
 
         from . import ops
 
+        if self._has_tensors():
+            nb = B if B is not None else max(t.shape[0] if t.dim() == 2 else 1 for t in (t1, t2))
+            return ops.kernel_values(*self._device_coefs(nb)[0], t1.contiguous(), t2.contiguous(), B=nb)
         dev, _ = self._dev_coefs(t1.device, B)
         return ops.kernel_values(*dev[:6], t1.contiguous(), t2.contiguous(), B=B)
 
@@ -110,7 +202,10 @@ class Term:
 
         from . import ops
 
-        (ar, cr, ac, bc, cc, dc, c), _ = self._dev_coefs(diag.device, diag.shape[0])
+        if self._has_tensors():
+            (ar, cr, ac, bc, cc, dc), c = self._device_coefs(diag.shape[0])
+        else:
+            (ar, cr, ac, bc, cc, dc, c), _ = self._dev_coefs(diag.device, diag.shape[0])
         a, U, V = ops.get_celerite_matrices(ar, ac, bc, dc, x, diag)
         return c, a, U, V
 
@@ -119,9 +214,16 @@ class TermSum(Term):
     def __init__(self, *terms):
         self.terms = []
         for t in terms:
-            self.terms += t.terms if isinstance(t, TermSum) else [t]
+            self.terms += t.terms if isinstance(t, TermSum) and t.terms else [t]
+
+    def _has_tensors(self):
+        return any(t._has_tensors() for t in self.terms)
+
+    def _records(self, add):
+        return [r for t in self.terms for r in t._records(add)]
 
     def get_coefficients(self):
+        self._no_host()
         parts = [t.get_coefficients() for t in self.terms]
         nb = max(max(v.shape[0] if v.ndim == 2 else 0 for v in p) for p in parts)
 
@@ -155,7 +257,11 @@ class RealTerm(Term):
     def __init__(self, *, a, c):
         self.a, self.c = a, c
 
+    def _records(self, add):
+        return [dict(kind="real", cols=(add(self.a), add(self.c)))]
+
     def get_coefficients(self):
+        self._no_host()
         ar, cr = _stack(self.a), _stack(self.c)
         e = _empty_like(ar)
         return ar, cr, e, e, e, e
@@ -167,17 +273,47 @@ class ComplexTerm(Term):
     def __init__(self, *, a, b, c, d):
         self.a, self.b, self.c, self.d = a, b, c, d
 
+    def _records(self, add):
+        return [dict(kind="complex", cols=(add(self.a), add(self.b), add(self.c), add(self.d)))]
+
     def get_coefficients(self):
+        self._no_host()
         ac, bc, cc, dc = _stack(self.a), _stack(self.b), _stack(self.c), _stack(self.d)
         e = _empty_like(ac)
         return e, e, ac, bc, cc, dc
 
 
 class SHOTerm(Term):
-    """Stochastically driven damped harmonic oscillator (terms.py:641-691).  Q is a python float
-    (the over/under-damped branch is chosen once); S0 and w0 may be per-series arrays."""
+    """Stochastically driven damped harmonic oscillator (terms.py:641-691).  With floats / numpy arrays Q is ONE number
+    (the over/under-damped branch is chosen once on the host); S0 and w0 may be per-series arrays.
 
-    def __init__(self, *, S0=None, w0=None, Q=None, sigma=None, rho=None, tau=None, eps=1e-5):
+    With tensor parameters (any of S0 | sigma, w0 | rho, Q | tau a device tensor) the parameters stay as given -- the
+    alternative parameterisations are resolved on the device, forward and reverse -- and `regime` says how the branch is
+    taken, so that nothing is read back: "under" / "over": the whole batch is on that side of Q = 1/2 (one complex term /
+    two real terms; a series on the wrong side gets ll = -inf and zero gradients from autograd.log_likelihood_kernel);
+    "mixed": each series takes the side ITS Q selects, as the reference's jax term does (jax/terms.py:481-548).  Mixed
+    costs width 4 instead of 2: the term occupies two real AND one complex slot, the unused side with zero amplitudes.
+    `regime` is required when Q (or the w0 | rho and tau it derives from) is a tensor; with a float Q it defaults to the
+    side of that Q."""
+
+    def __init__(self, *, S0=None, w0=None, Q=None, sigma=None, rho=None, tau=None, eps=1e-5, regime=None):
+        if regime not in (None, "under", "over", "mixed"):
+            raise ValueError("SHOTerm: regime must be 'under', 'over' or 'mixed'")
+        self.regime = regime
+        if any(_is_tensor(v) for v in (S0, w0, Q, sigma, rho, tau)):
+            if (S0 is None) == (sigma is None) or (w0 is None) == (rho is None) or (Q is None) == (tau is None):
+                raise ValueError("SHOTerm: give exactly one of S0 | sigma, of w0 | rho and of Q | tau")
+            self._given = (sigma if S0 is None else S0, rho if w0 is None else w0, tau if Q is None else Q)
+            self._par = (1 if S0 is None else 0) | (2 if w0 is None else 0) | (4 if Q is None else 0)
+            self.eps = float(eps)
+            if regime is None:
+                qsrc = (Q,) if tau is None else (tau, self._given[1])
+                if any(_is_tensor(v) for v in qsrc) or np.size(qsrc[0]) != 1 or np.size(qsrc[-1]) != 1:
+                    raise ValueError("SHOTerm: Q is a tensor (or derives from one): say regime='under', 'over' or 'mixed'")
+                w = float(2 * np.pi / rho) if w0 is None else float(w0)
+                q = float(Q) if tau is None else 0.5 * w * float(tau)
+                self.regime = "over" if q < 0.5 else "under"
+            return
         if w0 is None:
             w0 = 2 * np.pi / _col(rho)
         if Q is None:
@@ -193,7 +329,15 @@ class SHOTerm(Term):
             S0 = _col(sigma) ** 2 / (_col(w0) * Q)  # the same Q that is stored and used below
         self.S0, self.w0, self.Q, self.eps = S0, w0, Q, float(eps)
 
+    def _records(self, add):
+        if "_given" in self.__dict__:
+            return [dict(kind="sho", cols=tuple(add(v) for v in self._given), par=self._par, regime=self.regime, eps=self.eps)]
+        # float parameters next to tensor terms in one sum: (S0, w0, Q) as stored, the side of the float Q
+        regime = self.regime or ("over" if self.Q < 0.5 else "under")
+        return [dict(kind="sho", cols=(add(self.S0), add(self.w0), add(self.Q)), par=0, regime=regime, eps=self.eps)]
+
     def get_coefficients(self):
+        self._no_host()
         S0, w0, Q = _col(self.S0), _col(self.w0), self.Q
         if Q < 0.5:
             f = np.sqrt(max(1.0 - 4.0 * Q**2, self.eps))
@@ -215,7 +359,11 @@ class Matern32Term(Term):
     def __init__(self, *, sigma, rho, eps=0.01):
         self.sigma, self.rho, self.eps = sigma, rho, float(eps)
 
+    def _records(self, add):
+        return [dict(kind="matern32", cols=(add(self.sigma), add(self.rho)), eps=self.eps)]
+
     def get_coefficients(self):
+        self._no_host()
         w0 = np.sqrt(3.0) / _col(self.rho)
         S0 = _col(self.sigma) ** 2 / w0
         ac, bc, cc, dc = _stack(w0 * S0), _stack(w0 * w0 * S0 / self.eps), _stack(w0), _stack(np.full_like(w0, self.eps))
@@ -227,6 +375,11 @@ class RotationTerm(TermSum):
     """Mixture of two SHO terms at period and period/2 (terms.py:791-812)."""
 
     def __init__(self, *, sigma, period, Q0, dQ, f):
+        if any(_is_tensor(v) for v in (sigma, period, Q0, dQ, f)):
+            # one record of its own kind: the two oscillators share their five parameters (Q0, dQ > 0: both under-damped)
+            self._given = (sigma, period, Q0, dQ, f)
+            self.terms = []
+            return
         amp = float(sigma) ** 2 / (1 + float(f))
         Q1 = 0.5 + Q0 + dQ
         w1 = 4 * np.pi * Q1 / (period * np.sqrt(4 * Q1**2 - 1))
@@ -235,3 +388,11 @@ class RotationTerm(TermSum):
         w2 = 8 * np.pi * Q2 / (period * np.sqrt(4 * Q2**2 - 1))
         S2 = f * amp / (w2 * Q2)
         super().__init__(SHOTerm(S0=S1, w0=w1, Q=Q1), SHOTerm(S0=S2, w0=w2, Q=Q2))
+
+    def _has_tensors(self):
+        return "_given" in self.__dict__ or super()._has_tensors()
+
+    def _records(self, add):
+        if "_given" in self.__dict__:
+            return [dict(kind="rotation", cols=tuple(add(v) for v in self._given), eps=1e-5)]
+        return super()._records(add)

@@ -296,6 +296,64 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
                          double *bcr, double *bac, double *bbc, double *bcc, double *bdc, double *bx, double *bdiag,
                          double *by, int32_t *flag, void *work, size_t work_bytes, c2_stream_t stream);
 
+/* Term HYPER-PARAMETERS on the device (csrc/c2_term_params.hip): what the reference's jax / pymc frontends get by
+ * autodiff through their term classes (python/celerite2/jax/terms.py, pymc/terms.py).  A model is a PROGRAM, the flattened
+ * sum of terms (terms.py:233-235), passed by value: each record names its kind, its parameterisation, the columns of the
+ * parameter matrix P (B,NP) | shared (NP,) (p_bs = NP or 0) it reads, and its first real / complex coefficient slot
+ * (jr, jc: slots in program order, reals and complex terms each concatenated, as TermSum.get_coefficients does).
+ *   C2_TERM_REAL      col = (a, c)                       terms.py:515-521   1 real slot
+ *   C2_TERM_COMPLEX   col = (a, b, c, d)                 terms.py:554-569   1 complex slot
+ *   C2_TERM_SHO       col = (S0|sigma, w0|rho, Q|tau)    terms.py:644-691   par = OR of C2_SHO_SIGMA / _RHO / _TAU
+ *   C2_TERM_MATERN32  col = (sigma, rho)                 terms.py:729-745   1 complex slot
+ *   C2_TERM_ROTATION  col = (sigma, period, Q0, dQ, f)   terms.py:791-812   2 complex slots
+ * SHO regime: C2_SHO_UNDER (1 complex slot) / C2_SHO_OVER (2 real slots): the whole batch on one side of Q = 1/2
+ * (terms.py:691), a series on the wrong side gets flag[b] = 1 + its term's index; C2_SHO_MIXED: 2 real AND 1 complex
+ * slot (width 4 instead of 2), each series fills the side its Q selects and the other side gets amplitudes 0, the rate
+ * w0 / 2Q and dc = 0.  eps as in the reference (sqrt(max(., eps)); where it clamps nothing flows through f in reverse).
+ * Widths: Jr + 2 Jc <= 32, what c2_loglik_terms takes. */
+#define C2_TERM_REAL 0
+#define C2_TERM_COMPLEX 1
+#define C2_TERM_SHO 2
+#define C2_TERM_MATERN32 3
+#define C2_TERM_ROTATION 4
+#define C2_SHO_SIGMA 1
+#define C2_SHO_RHO 2
+#define C2_SHO_TAU 4
+#define C2_SHO_UNDER 0
+#define C2_SHO_OVER 1
+#define C2_SHO_MIXED 2
+#define C2_TERMS_MAX 16
+#define C2_FLAG_REGIME (-2)
+typedef struct {
+  int32_t kind, par, regime, jr, jc;
+  int32_t col[5];
+  double eps;
+} c2_term_rec;
+typedef struct {
+  int32_t nterms, np, Jr, Jc;
+  c2_term_rec term[C2_TERMS_MAX];
+} c2_term_program;
+/* P -> ar, cr (B,Jr), ac, bc, cc, dc (B,Jc) (always per series: coef_batched = 1 downstream) and flag (B,). */
+int c2_term_coefficients(const c2_term_program *prog, int64_t B, const double *P, int64_t p_bs, double *ar, double *cr,
+                         double *ac, double *bc, double *cc, double *dc, int32_t *flag, c2_stream_t stream);
+/* The reverse: cotangents bar .. bdc (what c2_loglik_terms_grad writes) -> bP (B,NP), per series also for a shared P.
+ * tflag (nullable): the flag of c2_term_coefficients; lflag (nullable): the flag of c2_loglik_terms_grad; ll (nullable).
+ * A series with tflag != 0 gets a zero row, ll = -inf and lflag = C2_FLAG_REGIME; one with lflag != 0 a zero row. */
+int c2_term_coefficients_rev(const c2_term_program *prog, int64_t B, const double *P, int64_t p_bs, const double *bar,
+                             const double *bcr, const double *bac, const double *bbc, const double *bcc,
+                             const double *bdc, const int32_t *tflag, int32_t *lflag, double *ll, double *bP,
+                             c2_stream_t stream);
+/* The two hyper-parameters every model has (core.py:262-310: diag = yerr^2 + ..., core.py:407-428: y - mean), one pass:
+ * diag[b,n] = (yerr_is_sigma ? yerr[b,n]^2 : yerr[b,n]) + jitter[b]^2, r[b,n] = y[b,n] - mean[b].  jitter, mean (B,),
+ * nullable (= 0).  The outputs must not alias the inputs. */
+int c2_noise_mean_apply(int64_t B, int64_t N, const double *yerr, int yerr_is_sigma, const double *jitter,
+                        const double *mean, const double *y, double *diag, double *r, c2_stream_t stream);
+/* ... and its reverse, one pass over bdiag and by (B,N) with a fixed summation order (deterministic):
+ * bjitter[b] = 2 jitter[b] sum_n bdiag[b,n], bmean[b] = -sum_n by[b,n]; either output may be NULL; a series with
+ * flag[b] != 0 (nullable) gets zeros. */
+int c2_noise_mean_rev(int64_t B, int64_t N, const double *jitter, const double *bdiag, const double *by,
+                      const int32_t *flag, double *bjitter, double *bmean, c2_stream_t stream);
+
 /* dot_tril -- python/celerite2/numpy.py:100-102: Z = Y * sqrt(d)[:,None];
  * Z += tril(U W^T) Z.  Y == Z allowed. */
 int c2_dot_tril(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs, const double *c,
