@@ -90,28 +90,43 @@ class _TermCoefficients(torch.autograd.Function):
     @staticmethod
     def forward(ctx, program, P, B):
         Pd = P.detach().contiguous()
-        coefs, flag = ops.term_coefficients(program, Pd, B)
         ctx.program, ctx.shared = program, P.dim() == 1
         ctx.save_for_backward(Pd)
+        if isinstance(program, ops.TermExpr):   # seven outputs: the diagonal shift of a convolution is differentiable too
+            coefs, flag, shift = ops.term_coefficients(program, Pd, B)
+            return coefs + (shift,)
+        coefs, flag = ops.term_coefficients(program, Pd, B)
         return coefs
 
     @staticmethod
     def backward(ctx, *cots):
         (P,) = ctx.saved_tensors
-        bP = ops.term_coefficients_rev(ctx.program, P, [c.contiguous() for c in cots])
+        if isinstance(ctx.program, ops.TermExpr):
+            bP = ops.term_coefficients_rev(ctx.program, P, [c.contiguous() for c in cots[:6]], bshift=cots[6].contiguous())
+        else:
+            bP = ops.term_coefficients_rev(ctx.program, P, [c.contiguous() for c in cots])
         return None, (bP.sum(0) if ctx.shared else bP), None
 
 
-def term_coefficients(program, P, B=None):
+def term_coefficients(program, P, B=None, *, with_shift=False):
     """(ar, cr, ac, bc, cc, dc) (B, Jr) / (B, Jc) from the parameter matrix P (B, NP) | shared (NP,) of a term program
-    (ops.TermProgram), differentiable in P: c2_term_coefficients forward, c2_term_coefficients_rev backward (one launch each;
-    a shared P receives the batch sum).  What the reference's jax / pymc term classes give by autodiff."""
-    return _TermCoefficients.apply(program, P, B)
+    (ops.TermProgram, or ops.TermExpr for products / derivatives / the exposure-time convolution), differentiable in P:
+    c2_term[_expr]_coefficients forward, c2_term[_expr]_coefficients_rev backward (one launch each; a shared P receives the
+    batch sum).  What the reference's jax / pymc term classes give by autodiff.  `with_shift=True`: a seventh tensor, the
+    diagonal shift (B,) of a convolution (zeros for any other kernel), differentiable as well."""
+    out = _TermCoefficients.apply(program, P, B)
+    if not with_shift:
+        return tuple(out[:6])
+    if len(out) == 7:
+        return tuple(out)
+    n = out[0].shape[0] if program.Jr else out[2].shape[0]
+    return tuple(out) + (torch.zeros(n, dtype=torch.float64, device=P.device),)
 
 
 class _LogLikKernel(torch.autograd.Function):
-    """noise_mean_apply -> term_coefficients -> loglik_terms[_grad] -> term_coefficients_rev / noise_mean_rev as ONE node:
-    the gradients come out of the forward call (as in _LogLikTerms), backward scales them by the incoming cotangent."""
+    """noise_mean_apply -> term_coefficients -> loglik_terms[_grad] -> term_coefficients_rev / noise_mean_rev as ONE node
+    (ops.loglik_kernel_grad; with a TermExpr its chain through the diagonal shift): the gradients come out of the forward
+    call (as in _LogLikTerms), backward scales them by the incoming cotangent."""
 
     @staticmethod
     def forward(ctx, program, is_sigma, P, x, yerr, jitter, mean, y):
@@ -119,8 +134,12 @@ class _LogLikKernel(torch.autograd.Function):
         Pd, xd, ed, jd, md, yd = [None if v is None else v.detach().contiguous() for v in tens]
         B = y.shape[0]
         if not any(v is not None and v.requires_grad for v in tens):
-            diag, r = ops.noise_mean_apply(ed, jd, md, yd, yerr_is_sigma=is_sigma)
-            coefs, tflag = ops.term_coefficients(program, Pd, B)
+            if isinstance(program, ops.TermExpr):
+                coefs, tflag, shift = ops.term_coefficients(program, Pd, B)
+                diag, r = ops.noise_mean_shift_apply(ed, jd, md, shift, yd, yerr_is_sigma=is_sigma)
+            else:
+                diag, r = ops.noise_mean_apply(ed, jd, md, yd, yerr_is_sigma=is_sigma)
+                coefs, tflag = ops.term_coefficients(program, Pd, B)
             ll, flag = ops.loglik_terms(*coefs, xd, diag, r)
             return torch.where(tflag != 0, torch.full_like(ll, -float("inf")), ll)
         ll, (bP, bj, bm, bx, bdiag, by), flag = ops.loglik_kernel_grad(program, Pd, xd, ed, jd, md, yd, yerr_is_sigma=is_sigma)
@@ -160,8 +179,9 @@ def _per_series(v, B, like):
 
 def log_likelihood_kernel(kernel, x, y, *, yerr=None, diag=None, jitter=None, mean=None):
     """Batched GP log-likelihood (B,) as a differentiable function of the HYPER-PARAMETERS: every tensor parameter of
-    `kernel` (terms.RealTerm / ComplexTerm / SHOTerm / Matern32Term / RotationTerm and their sums, with parameters given as
-    float64 device tensors, 0-d or (B,)), `jitter` (added in quadrature: diag = yerr^2 + jitter^2, or diag + jitter^2) and
+    `kernel` (terms.RealTerm / ComplexTerm / SHOTerm / Matern32Term / RotationTerm, their sums, products (TermProduct),
+    derivatives (TermDiff) and exposure-time convolution (TermConvolution), with parameters given as float64 device tensors,
+    0-d or (B,)), `jitter` (added in quadrature: diag = yerr^2 + jitter^2, or diag + jitter^2) and
     `mean` (floats, 0-d or (B,) tensors), and x (N,) | (B, N), yerr | diag (B, N), y (B, N) when they require grad.
     Everything between the parameters and the gradient runs on the device (csrc/c2_term_params.hip around
     c2_loglik_terms_grad); shared parameters receive the batch-summed gradient.  A series whose factorisation fails, or whose

@@ -193,7 +193,8 @@ class ConditionalDistribution:
         return self._Kinv_KxsT
 
     def _do_dot(self, inp, target):
-        """core.py:68-113 + numpy.py:15-22: target += K(xs, t) inp through general_matmul_lower/upper."""
+        """core.py:68-113 + numpy.py:15-22: target += K(xs, t) inp through general_matmul_lower/upper.  (Under a
+        TermConvolution these semiseparable products are exact for lags >= delta, the reference's behaviour.)"""
         gp = self.gp
         if self.kernel is None:
             U1, V1 = gp._U, gp._V
@@ -237,15 +238,18 @@ class ConditionalDistribution:
         return self._k0() - ops.colsumsq_over_d(self.Linv_KxsT, self.gp._d)
 
     def _k0(self):
-        """k(0) = sum ar + sum ac (terms.py:58-79 at tau = 0): a python float, or (B, 1) on the device for per-series coefficients."""
-        if self._kernel()._has_tensors():
-            co = self._kernel()._device_coefs(self.gp._diag.shape[0])[0]
-            return (co[0].sum(dim=-1) + co[2].sum(dim=-1))[:, None]
-        co = self._kernel().get_coefficients()
+        """k(0) = sum ar + sum ac (terms.py:58-79 at tau = 0), plus delta_diag under a TermConvolution (its piecewise k(0),
+        terms.py:421-482): a python float, or (B, 1) on the device for per-series coefficients."""
+        kernel, B, dev = self._kernel(), self.gp._diag.shape[0], self.gp._diag.device
+        shift = kernel._k0_shift(B, dev)
+        if kernel._has_tensors():
+            co = kernel._device_coefs(B)[0]
+            return (co[0].sum(dim=-1) + co[2].sum(dim=-1))[:, None] + shift
+        co = kernel.get_coefficients()
         if all(v.ndim == 1 for v in co):
-            return float(co[0].sum() + co[2].sum())
-        dev, _ = self._kernel()._dev_coefs(self.gp._diag.device, self.gp._diag.shape[0])
-        return (dev[0].sum(dim=-1) + dev[2].sum(dim=-1))[:, None]
+            return float(co[0].sum() + co[2].sum()) + shift
+        co, _ = kernel._dev_coefs(dev, B)
+        return (co[0].sum(dim=-1) + co[2].sum(dim=-1))[:, None] + shift
 
     @property
     def covariance(self):  # core.py:142-150: k(xs - xs') - K(xs, t) K^-1 K(t, xs), (B, M, M)

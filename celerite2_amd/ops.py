@@ -19,7 +19,8 @@ __all__ = [
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
-    "TermProgram", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
+    "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
+    "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
 
@@ -571,6 +572,46 @@ _REGIMES = {"under": (0, 0, 1), "over": (1, 2, 0), "mixed": (2, 2, 1)}   # name 
 SHO_SIGMA, SHO_RHO, SHO_TAU = 1, 2, 4
 
 
+def _fill_program(records, NP):
+    """records -> (copies with jr / jc / eps / par filled in, NP, the c2_term_program)."""
+    if not 1 <= len(records) <= 16:
+        raise ValueError("a term program holds 1 .. 16 terms (got %d)" % len(records))
+    records = [dict(r) for r in records]
+    NP = int(NP)
+    c = _TermProgram()
+    jr = jc = 0
+    for i, r in enumerate(records):
+        if r["kind"] not in _KINDS:
+            raise ValueError("unknown term kind %r" % (r["kind"],))
+        kind, npar, wr, wc = _KINDS[r["kind"]]
+        regime = 0
+        if r["kind"] == "sho":
+            if r.get("regime") not in _REGIMES:
+                raise ValueError("SHO regime must be 'under', 'over' or 'mixed'")
+            regime, wr, wc = _REGIMES[r["regime"]]
+        cols = [int(k) for k in r["cols"]]
+        if len(cols) != npar or any(not 0 <= k < NP for k in cols):
+            raise ValueError("term %d (%s): needs %d parameter columns in [0, %d)" % (i, r["kind"], npar, NP))
+        t = c.term[i]
+        t.kind, t.par, t.regime, t.jr, t.jc = kind, int(r.get("par") or 0), regime, jr, jc
+        for k, v in enumerate(cols):
+            t.col[k] = v
+        eps = r.get("eps")
+        t.eps = float((0.01 if r["kind"] == "matern32" else 1e-5) if eps is None else eps)
+        r.update(jr=jr, jc=jc, eps=t.eps, par=t.par)
+        jr += wr
+        jc += wc
+    c.nterms, c.np, c.Jr, c.Jc = len(records), NP, jr, jc
+    return records, NP, c
+
+
+def record_widths(record):
+    """(real slots, complex slots) of one leaf record."""
+    if record["kind"] == "sho":
+        return _REGIMES[record["regime"]][1:]
+    return _KINDS[record["kind"]][2:]
+
+
 class TermProgram:
     """The flattened sum of terms the kernels walk (c2_term_program, celerite2_amd.h): built ONCE from a list of records
     `dict(kind=, cols=, par=0, regime=None, eps=)` and passed to the kernels by value.  `kind` is "real" (cols a, c),
@@ -580,42 +621,100 @@ class TermProgram:
     (TermSum.get_coefficients).  Jr + 2 Jc <= 32."""
 
     def __init__(self, records, NP):
-        if not 1 <= len(records) <= 16:
-            raise ValueError("a term program holds 1 .. 16 terms (got %d)" % len(records))
-        self.records = [dict(r) for r in records]
-        self.NP = int(NP)
-        c = _TermProgram()
-        jr = jc = 0
-        for i, r in enumerate(self.records):
-            if r["kind"] not in _KINDS:
-                raise ValueError("unknown term kind %r" % (r["kind"],))
-            kind, npar, wr, wc = _KINDS[r["kind"]]
-            regime = 0
-            if r["kind"] == "sho":
-                if r.get("regime") not in _REGIMES:
-                    raise ValueError("SHO regime must be 'under', 'over' or 'mixed'")
-                regime, wr, wc = _REGIMES[r["regime"]]
-            cols = [int(k) for k in r["cols"]]
-            if len(cols) != npar or any(not 0 <= k < self.NP for k in cols):
-                raise ValueError("term %d (%s): needs %d parameter columns in [0, %d)" % (i, r["kind"], npar, self.NP))
-            t = c.term[i]
-            t.kind, t.par, t.regime, t.jr, t.jc = kind, int(r.get("par") or 0), regime, jr, jc
-            for k, v in enumerate(cols):
-                t.col[k] = v
-            eps = r.get("eps")
-            t.eps = float((0.01 if r["kind"] == "matern32" else 1e-5) if eps is None else eps)
-            r.update(jr=jr, jc=jc, eps=t.eps, par=t.par)
-            jr += wr
-            jc += wc
-        c.nterms, c.np, c.Jr, c.Jc = len(self.records), self.NP, jr, jc
-        self.Jr, self.Jc = jr, jc
-        if jr + 2 * jc > 32:
-            raise ValueError("term program: width %d not supported (the coefficient-level entry points take J <= 32)" % (jr + 2 * jc))
+        self.records, self.NP, self._c = _fill_program(records, NP)
+        self.Jr, self.Jc = self._c.Jr, self._c.Jc
+        if self.Jr + 2 * self.Jc > 32:
+            raise ValueError("term program: width %d not supported (the coefficient-level entry points take J <= 32)" % (self.Jr + 2 * self.Jc))
+
+    @property
+    def width(self):
+        return self.Jr + 2 * self.Jc
+
+
+class _TermRange(ctypes.Structure):
+    _fields_ = [("r0", ctypes.c_int32), ("nr", ctypes.c_int32), ("c0", ctypes.c_int32), ("nc", ctypes.c_int32)]
+
+
+class _TermOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("col", ctypes.c_int32), ("a", _TermRange), ("b", _TermRange), ("out", _TermRange)]
+
+
+class _TermExpr(ctypes.Structure):
+    _fields_ = [("leaves", _TermProgram), ("nops", ctypes.c_int32), ("NR", ctypes.c_int32), ("NC", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("op", _TermOp * 16)]
+
+
+_OPS = {"sum": 0, "product": 1, "diff": 2, "convolve": 3}
+
+
+class TermExpr:
+    """Term ALGEBRA the kernels walk (c2_term_expr, celerite2_amd.h): the leaf records of a TermProgram (`records`, same
+    dicts, but their total width is not limited to 32) followed by `operations` in post-order, each
+    `dict(op="sum" | "product" | "diff" | "convolve", a=, b=, col=)`.  An operand is an int i (the result of operation i) or a
+    4-tuple (r0, nr, c0, nc) of leaf registers: real registers [r0, r0 + nr) and complex registers [c0, c0 + nc), numbered
+    as the leaves' jr / jc.  "diff" and "convolve" take `a` only; "convolve" must be the last operation and `col` names the
+    column of P that holds the boxcar width delta.  Results get fresh registers in order (filled in as `out`); the result
+    of the last operation is the kernel: Jr, Jc, width <= 32."""
+
+    def __init__(self, records, operations, NP):
+        self.records, self.NP, leaves = _fill_program(records, NP)
+        if not 1 <= len(operations) <= 16:
+            raise ValueError("a term expression holds 1 .. 16 operations (got %d)" % len(operations))
+        c = _TermExpr()
+        c.leaves = leaves
+        nr, nc = leaves.Jr, leaves.Jc
+        self.operations = []
+        for i, o in enumerate(operations):
+            o = dict(o)
+            if o["op"] not in _OPS:
+                raise ValueError("unknown operation %r" % (o["op"],))
+            binary = o["op"] in ("sum", "product")
+            rng = []
+            for key in ("a", "b") if binary else ("a",):
+                v = o[key]
+                if isinstance(v, int):
+                    if not 0 <= v < i:
+                        raise ValueError("operation %d: operand %r is not an earlier operation" % (i, v))
+                    v = self.operations[v]["out"]
+                v = tuple(int(k) for k in v)
+                if len(v) != 4 or min(v) < 0 or v[0] + v[1] > nr or v[2] + v[3] > nc:
+                    raise ValueError("operation %d: operand range %r outside the registers written so far" % (i, v))
+                rng.append(v)
+            a = rng[0]
+            b = rng[1] if binary else (0, 0, 0, 0)
+            if o["op"] == "sum":
+                wr, wc = a[1] + b[1], a[3] + b[3]
+            elif o["op"] == "product":
+                wr, wc = a[1] * b[1], a[1] * b[3] + b[1] * a[3] + 2 * a[3] * b[3]
+            else:
+                wr, wc = a[1], a[3]
+            col = -1
+            if o["op"] == "convolve":
+                col = int(o["col"])
+                if i != len(operations) - 1 or not 0 <= col < self.NP:
+                    raise ValueError("a convolution is the last operation and reads a column of P")
+            out = (nr, wr, nc, wc)
+            if wr + 2 * wc > 32 or nr + wr > 256 or nc + wc > 256:
+                raise ValueError("term expression: width %d not supported (the coefficient-level entry points take J <= 32)" % (wr + 2 * wc))
+            t = c.op[i]
+            t.op, t.col = _OPS[o["op"]], col
+            for dst, src in ((t.a, a), (t.b, b), (t.out, out)):
+                dst.r0, dst.nr, dst.c0, dst.nc = src
+            nr, nc = nr + wr, nc + wc
+            self.operations.append(dict(op=o["op"], a=a, b=b, out=out, col=col))
+        c.nops, c.NR, c.NC = len(operations), nr, nc
+        self.Jr, self.Jc = self.operations[-1]["out"][1], self.operations[-1]["out"][3]
+        self.has_shift = self.operations[-1]["op"] == "convolve"
         self._c = c
 
     @property
     def width(self):
         return self.Jr + 2 * self.Jc
+
+    def workspace(self, B, device):
+        """The register buffer of term_coefficients[_rev] for B series (values + cotangents)."""
+        nbytes = _lib.load().c2_term_expr_workspace_bytes(ctypes.byref(self._c), B)
+        return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
 
 
 def _program_P(program, P):
@@ -626,9 +725,11 @@ def _program_P(program, P):
         raise ValueError("Invalid shape: P (got %s, expected (%d,) or (B, %d))" % (tuple(P.shape), program.NP, program.NP))
 
 
-def term_coefficients(program, P, B=None, *, out=None, flag=None):
+def term_coefficients(program, P, B=None, *, out=None, flag=None, shift=None, work=None):
     """P (B, NP) | shared (NP,) (then `B` says how many series) -> ((ar, cr, ac, bc, cc, dc), flag): the coefficients in the
-    layout loglik_terms takes, (B, Jr) / (B, Jc), and flag (B,) int32 (nonzero: an SHO series on the wrong side of its regime)."""
+    layout loglik_terms takes, (B, Jr) / (B, Jc), and flag (B,) int32 (nonzero: an SHO series on the wrong side of its regime).
+    For a TermExpr (products, derivatives, the exposure-time convolution) a third value is returned, `shift` (B,): what the
+    convolution adds to the diagonal (0 without one); `work` = program.workspace(B, device), reusable."""
     _program_P(program, P)
     B = P.shape[0] if P.dim() == 2 else B
     if B is None:
@@ -644,16 +745,27 @@ def term_coefficients(program, P, B=None, *, out=None, flag=None):
         for nm, o, sh in zip(("ar", "cr", "ac", "bc", "cc", "dc"), out, shapes):
             _shape(nm, o, sh)
     flag = torch.empty(B, dtype=torch.int32, device=dev) if flag is None else flag
+    if isinstance(program, TermExpr):
+        shift = torch.empty(B, dtype=torch.float64, device=dev) if shift is None else shift
+        work = program.workspace(B, dev) if work is None else work
+        _chk(shift, work)
+        _shape("shift", shift, (B,))
+        rc = _lib.load().c2_term_expr_coefficients(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
+                                                   *_coef_ptrs(*out, Jr, Jc), _p(shift), _p(flag), _p(work),
+                                                   ctypes.c_size_t(work.numel() * 8), _stream())
+        _lib.check(rc, "term_expr_coefficients")
+        return tuple(out), flag, shift
     rc = _lib.load().c2_term_coefficients(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
                                           *_coef_ptrs(*out, Jr, Jc), _p(flag), _stream())
     _lib.check(rc, "term_coefficients")
     return tuple(out), flag
 
 
-def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=None, ll=None, out=None):
+def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=None, ll=None, out=None, bshift=None, work=None):
     """The reverse of term_coefficients: cotangents (bar, bcr, bac, bbc, bcc, bdc), (B, Jr) / (B, Jc), -> bP (B, NP), per series
     also for a shared P.  `tflag` (term_coefficients' flag), `lflag` (loglik_terms_grad's flag) and `ll`, when given, are
-    settled on the device: a wrong-regime series gets a zero row, ll = -inf and lflag = -2; a failed factorisation a zero row."""
+    settled on the device: a wrong-regime series gets a zero row, ll = -inf and lflag = -2; a failed factorisation a zero row.
+    For a TermExpr: `bshift` (B,), the cotangent of the diagonal shift (None = 0), and `work` as in term_coefficients."""
     _program_P(program, P)
     Jr, Jc = program.Jr, program.Jc
     cot = list(cotangents)
@@ -671,6 +783,15 @@ def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=N
         if f is not None and (f.dtype != torch.int32 or tuple(f.shape) != (B,) or not f.is_contiguous()):
             raise ValueError("Invalid shape: %s (must be (B,) int32)" % nm)
     _shape("ll", ll, (B,))
+    if isinstance(program, TermExpr):
+        work = program.workspace(B, P.device) if work is None else work
+        _chk(bshift, work)
+        _shape("bshift", bshift, (B,))
+        rc = _lib.load().c2_term_expr_coefficients_rev(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
+                                                       *_coef_ptrs(*cot, Jr, Jc), _p(bshift), _p(tflag), _p(lflag), _p(ll),
+                                                       _p(bP), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+        _lib.check(rc, "term_expr_coefficients_rev")
+        return bP
     rc = _lib.load().c2_term_coefficients_rev(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
                                               *_coef_ptrs(*cot, Jr, Jc), _p(tflag), _p(lflag), _p(ll), _p(bP), _stream())
     _lib.check(rc, "term_coefficients_rev")
@@ -709,21 +830,62 @@ def noise_mean_rev(jitter, bdiag, by, *, flag=None, out=None):
     return bj, bm
 
 
+def noise_mean_shift_apply(yerr, jitter, mean, shift, y, *, yerr_is_sigma=True, out=None):
+    """noise_mean_apply with one more per-series term: diag = yerr^2 (or yerr) + jitter^2 + shift[b] -- the (negative) diagonal
+    shift of an exposure-time convolution (term_coefficients of a TermExpr).  shift (B,) or None (then noise_mean_apply's bits)."""
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B, N = y.shape
+    diag, r = (torch.empty_like(y), torch.empty_like(y)) if out is None else out
+    _chk(yerr, jitter, mean, shift, y, diag, r)
+    _shape("yerr", yerr, (B, N)); _shape("jitter", jitter, (B,)); _shape("mean", mean, (B,)); _shape("shift", shift, (B,))
+    _shape("diag", diag, (B, N)); _shape("r", r, (B, N))
+    rc = _lib.load().c2_noise_mean_shift_apply(_i64(B), _i64(N), _p(yerr), ctypes.c_int(1 if yerr_is_sigma else 0), _p(jitter),
+                                               _p(mean), _p(shift), _p(y), _p(diag), _p(r), _stream())
+    _lib.check(rc, "noise_mean_shift_apply")
+    return diag, r
+
+
+def noise_mean_shift_rev(jitter, bdiag, by, *, flag=None, tflag=None, out=None):
+    """noise_mean_rev plus bshift = sum_n bdiag, the cotangent of noise_mean_shift_apply's shift: (bjitter, bmean, bshift), (B,)
+    each, one pass, the same fixed summation order.  A series with flag != 0 or tflag != 0 gets zeros."""
+    if by.dim() != 2:
+        raise ValueError("Invalid shape: by (must be (B, N))")
+    B, N = by.shape
+    bj, bm, bs = (torch.empty(B, dtype=torch.float64, device=by.device) for _ in range(3)) if out is None else out
+    _chk(jitter, bdiag, by, bj, bm, bs)
+    _shape("jitter", jitter, (B,)); _shape("bdiag", bdiag, (B, N))
+    _shape("bjitter", bj, (B,)); _shape("bmean", bm, (B,)); _shape("bshift", bs, (B,))
+    for f in (flag, tflag):
+        if f is not None and (f.dtype != torch.int32 or tuple(f.shape) != (B,)):
+            raise ValueError("Invalid shape: flag (must be (B,) int32)")
+    rc = _lib.load().c2_noise_mean_shift_rev(_i64(B), _i64(N), _p(jitter), _p(bdiag), _p(by), _p(flag), _p(tflag), _p(bj),
+                                             _p(bm), _p(bs), _stream())
+    _lib.check(rc, "noise_mean_shift_rev")
+    return bj, bm, bs
+
+
 def loglik_kernel_workspace(program, B, N, device):
     """Caller-owned buffers of loglik_kernel_grad, reusable across calls of the same shape (and required for graph capture):
-    a dict with the scratch of loglik_terms_grad, the six coefficient arrays and their cotangents, diag, r and the term flag."""
+    a dict with the scratch of loglik_terms_grad, the six coefficient arrays and their cotangents, diag, r and the term flag;
+    for a TermExpr also the diagonal shift, its cotangent and the register buffer of the coefficient kernels."""
     f64 = dict(dtype=torch.float64, device=device)
     Jr, Jc = program.Jr, program.Jc
     shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4
-    return {"terms": loglik_terms_workspace(B, N, Jr, Jc, device), "coefs": [torch.empty(sh, **f64) for sh in shapes],
+    work = {"terms": loglik_terms_workspace(B, N, Jr, Jc, device), "coefs": [torch.empty(sh, **f64) for sh in shapes],
             "cots": [torch.empty(sh, **f64) for sh in shapes], "diag": torch.empty((B, N), **f64),
             "r": torch.empty((B, N), **f64), "tflag": torch.empty(B, dtype=torch.int32, device=device)}
+    if isinstance(program, TermExpr):
+        work.update(shift=torch.empty(B, **f64), bshift=torch.empty(B, **f64), expr=program.workspace(B, device))
+    return work
 
 
 def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=True, work=None, out=None):
     """Hyper-parameters to log-likelihood and gradient in one stream-ordered chain, no host traffic (graph-capturable with
     caller-owned `work` = loglik_kernel_workspace(...) and `out` = a previous call's six gradient tensors):
     noise_mean_apply -> term_coefficients -> loglik_terms_grad -> term_coefficients_rev / noise_mean_rev.
+    With a TermExpr the coefficient stage comes first, because diag needs its shift:
+    term_coefficients -> noise_mean_shift_apply -> loglik_terms_grad -> noise_mean_shift_rev -> term_coefficients_rev.
     P (B, NP) | (NP,); x (N,) | (B, N); yerr, y (B, N); jitter, mean (B,) or None.
     Returns (ll, (bP, bjitter, bmean, bx, bdiag, by), flag): bP (B, NP), bjitter, bmean (B,) per series; bdiag is the
     cotangent of diag = yerr^2 + jitter^2 (byerr = 2 yerr bdiag is the caller's).  flag: 0, the first failing row of the
@@ -740,6 +902,15 @@ def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=Tr
         out = (torch.empty((B, program.NP), **f64), torch.empty(B, **f64), torch.empty(B, **f64), torch.empty((B, N), **f64),
                torch.empty((B, N), **f64), torch.empty((B, N), **f64))
     bP, bj, bm, bx, bdiag, by = out
+    if isinstance(program, TermExpr):
+        coefs, tflag, shift = term_coefficients(program, P, B, out=work["coefs"], flag=work["tflag"], shift=work["shift"],
+                                                work=work["expr"])
+        diag, r = noise_mean_shift_apply(yerr, jitter, mean, shift, y, yerr_is_sigma=yerr_is_sigma, out=(work["diag"], work["r"]))
+        ll, _, flag = loglik_terms_grad(*coefs, x, diag, r, work=work["terms"], out=tuple(work["cots"]) + (bx, bdiag, by))
+        noise_mean_shift_rev(jitter, bdiag, by, flag=flag, tflag=tflag, out=(bj, bm, work["bshift"]))
+        term_coefficients_rev(program, P, work["cots"], tflag=tflag, lflag=flag, ll=ll, out=bP, bshift=work["bshift"],
+                              work=work["expr"])
+        return ll, (bP, bj, bm, bx, bdiag, by), flag
     diag, r = noise_mean_apply(yerr, jitter, mean, y, yerr_is_sigma=yerr_is_sigma, out=(work["diag"], work["r"]))
     coefs, tflag = term_coefficients(program, P, B, out=work["coefs"], flag=work["tflag"])
     ll, _, flag = loglik_terms_grad(*coefs, x, diag, r, work=work["terms"], out=tuple(work["cots"]) + (bx, bdiag, by))

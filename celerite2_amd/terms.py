@@ -12,10 +12,20 @@ reference's jax / pymc term classes (python/celerite2/jax/terms.py, pymc/terms.p
 tensor parameter is flattened ONCE into a term program (ops.TermProgram); `coefficients(B)` forms its six coefficient
 arrays on the device by one kernel (csrc/c2_term_params.hip), differentiable in every tensor parameter, and nothing is
 read back to the host.  With floats / numpy arrays every path below runs as it always did.
+
+Term ALGEBRA (terms.py:238-482): `t1 * t2` / TermProduct, TermDiff and TermConvolution, nested freely with sums (a
+convolution only as the outermost term).  With floats / numpy arrays they map coefficient arrays on the host; with tensor
+parameters the kernel becomes an expression (ops.TermExpr: the leaf records plus operation records) that
+csrc/c2_term_expr.hip evaluates and differentiates on the device.  A kernel without them is a TermProgram as before.
 """
+import math
+
 import numpy as np
 
-__all__ = ["Term", "TermSum", "RealTerm", "ComplexTerm", "SHOTerm", "Matern32Term", "RotationTerm"]
+__all__ = ["Term", "TermSum", "TermProduct", "TermDiff", "TermConvolution", "RealTerm", "ComplexTerm", "SHOTerm", "Matern32Term",
+           "RotationTerm"]
+
+_CONV_OUTER = "You cannot perform operations on an TermConvolution, it must be the outer term in the kernel"
 
 
 def _col(x):
@@ -34,6 +44,9 @@ class Term:
 
     def __add__(self, other):
         return TermSum(self, other)
+
+    def __mul__(self, other):
+        return TermProduct(self, other)
 
     @property
     def width(self):
@@ -68,13 +81,27 @@ class Term:
                 values.append(v)
                 return len(values) - 1
 
-            records = self._records(add)
-            cached = self.__dict__["_program"] = (ops.TermProgram(records, len(values)), values)
+            if self._uses_algebra():   # products / derivatives / a convolution: leaf records + operation records
+                ctx = _ExprBuilder(add)
+                self._emit(ctx)
+                program = ops.TermExpr(ctx.records, ctx.operations, len(values))
+            else:
+                program = ops.TermProgram(self._records(add), len(values))
+            cached = self.__dict__["_program"] = (program, values)
         return cached
+
+    def _uses_algebra(self):
+        """Does the kernel contain a TermProduct / TermDiff / TermConvolution (then its program is an ops.TermExpr)?"""
+        return False
+
+    def _emit(self, ctx):
+        """Post-order walk for ops.TermExpr: emits this term's records / operations, returns the operand that names its
+        coefficient list (a leaf register range, or the index of the operation that produced it)."""
+        return ctx.leaf(self._records(ctx.add))
 
     @property
     def program(self):
-        """The flattened kernel (ops.TermProgram), built once."""
+        """The flattened kernel (ops.TermProgram; ops.TermExpr when it uses products, derivatives or a convolution), built once."""
         return self._build_program()[0]
 
     def parameter_matrix(self, B=None):
@@ -114,6 +141,33 @@ class Term:
         co = [v.detach() for v in self.coefficients(B)]
         c = torch.cat([co[1], co[4].repeat_interleave(2, dim=-1)], dim=-1)
         return co, c
+
+    def get_psd(self, omega):
+        """Power spectral density at the angular frequencies `omega` (terms.py:81-104).  Floats / numpy parameters: numpy,
+        shape of omega (shared coefficients) or (B, M).  Tensor parameters: torch on the device from coefficients(B),
+        (B, M) for omega (M,) with B the batch size of the parameters (1 when all are shared)."""
+        if self._has_tensors():
+            import torch
+
+            P = self.parameter_matrix()
+            co = self._device_coefs(P.shape[0] if P.dim() == 2 else 1)[0]
+            w2 = torch.as_tensor(omega, dtype=torch.float64, device=P.device).reshape(1, -1) ** 2
+            return _psd(co, w2, lambda v, j: v[:, j, None])
+        co = self.get_coefficients()
+        w2 = np.atleast_1d(np.asarray(omega, dtype=np.float64)) ** 2
+        if any(v.ndim == 2 for v in co):
+            nb = max(v.shape[0] for v in co if v.ndim == 2)
+            co = [np.broadcast_to(v, (nb, v.shape[-1])) for v in co]
+            return _psd(co, w2.reshape(1, -1), lambda v, j: v[:, j, None])
+        return _psd(co, w2, lambda v, j: float(v[j]))
+
+    def _k0_shift(self, B, device):
+        """What k(0) has beyond sum ar + sum ac: nothing, except under a TermConvolution."""
+        return 0.0
+
+    def _shifted(self, diag):
+        """diag plus the kernel's own diagonal shift (TermConvolution only)."""
+        return diag
 
     def get_value(self, tau):
         """k(tau) (terms.py:58-79), numpy, for dense cross-checks; shared coefficients only."""
@@ -206,12 +260,58 @@ class Term:
             (ar, cr, ac, bc, cc, dc), c = self._device_coefs(diag.shape[0])
         else:
             (ar, cr, ac, bc, cc, dc, c), _ = self._dev_coefs(diag.device, diag.shape[0])
-        a, U, V = ops.get_celerite_matrices(ar, ac, bc, dc, x, diag)
+        a, U, V = ops.get_celerite_matrices(ar, ac, bc, dc, x, self._shifted(diag))
         return c, a, U, V
+
+
+def _psd(co, w2, cof):
+    """terms.py:88-104 on numpy arrays or torch tensors; cof(v, j) = coefficient j, broadcastable against w2."""
+    ar, cr, ac, bc, cc, dc = co
+    psd = 0.0 * w2
+    for j in range(ar.shape[-1]):
+        a, c = cof(ar, j), cof(cr, j)
+        psd = psd + a * c / (c * c + w2)
+    for j in range(ac.shape[-1]):
+        a, b, c, d = cof(ac, j), cof(bc, j), cof(cc, j), cof(dc, j)
+        w02 = c * c + d * d
+        psd = psd + ((a * c + b * d) * w02 + (a * c - b * d) * w2) / (w2 * w2 + 2.0 * (c * c - d * d) * w2 + w02 * w02)
+    return math.sqrt(2.0 / math.pi) * psd
+
+
+class _ExprBuilder:
+    """Collects the leaf records and the operation records of an ops.TermExpr while a kernel is walked in post-order."""
+
+    def __init__(self, add):
+        self.add, self.records, self.operations, self.jr, self.jc = add, [], [], 0, 0
+
+    def leaf(self, records):
+        from . import ops
+
+        r0, c0 = self.jr, self.jc
+        for r in records:
+            wr, wc = ops.record_widths(r)
+            self.jr += wr
+            self.jc += wc
+        self.records += records
+        return (r0, self.jr - r0, c0, self.jc - c0)
+
+    def op(self, name, a, b=None, col=None):
+        self.operations.append(dict(op=name, a=a, b=b, col=col))
+        return len(self.operations) - 1
+
+
+def _same_batch(*coefs):
+    """Coefficient tuples of several terms, every array broadcast to (nb, J) when any of them is per-series."""
+    nb = max(v.shape[0] if v.ndim == 2 else 0 for co in coefs for v in co)
+    if not nb:
+        return coefs
+    return tuple(tuple(np.broadcast_to(v, (nb, v.shape[-1])) if v.ndim == 1 else v for v in co) for co in coefs)
 
 
 class TermSum(Term):
     def __init__(self, *terms):
+        if any(isinstance(t, TermConvolution) for t in terms):
+            raise TypeError(_CONV_OUTER)
         self.terms = []
         for t in terms:
             self.terms += t.terms if isinstance(t, TermSum) and t.terms else [t]
@@ -221,6 +321,28 @@ class TermSum(Term):
 
     def _records(self, add):
         return [r for t in self.terms for r in t._records(add)]
+
+    def _uses_algebra(self):
+        return any(t._uses_algebra() for t in self.terms)
+
+    def _emit(self, ctx):
+        if not self._uses_algebra():
+            return ctx.leaf(self._records(ctx.add))
+        acc, run = [None], []   # runs of plain terms become one leaf list; coefficient order = term order (terms.py:233-235)
+
+        def join(h):
+            acc[0] = h if acc[0] is None else ctx.op("sum", acc[0], h)
+
+        for t in self.terms + [None]:
+            if t is not None and not t._uses_algebra():
+                run.append(t)
+                continue
+            if run:
+                join(ctx.leaf([r for u in run for r in u._records(ctx.add)]))
+                run = []
+            if t is not None:
+                join(t._emit(ctx))
+        return acc[0]
 
     def get_coefficients(self):
         self._no_host()
@@ -234,6 +356,267 @@ class TermSum(Term):
             return np.concatenate(arrs, axis=-1)
 
         return tuple(cat(i) for i in range(6))
+
+
+class TermProduct(Term):
+    """k = k1 k2 (terms.py:238-301): again a celerite kernel, wider.  Coefficients in the reference's order: reals =
+    product(reals1, reals2); complex = real1 x complex2, then real2 x complex1, then per complex pair the (dj - dk) term
+    followed by the (dj + dk) term."""
+
+    def __init__(self, term1, term2):
+        if isinstance(term1, TermConvolution) or isinstance(term2, TermConvolution):
+            raise TypeError(_CONV_OUTER)
+        self.term1, self.term2 = term1, term2
+
+    def _has_tensors(self):
+        return self.term1._has_tensors() or self.term2._has_tensors()
+
+    def _uses_algebra(self):
+        return True
+
+    def _emit(self, ctx):
+        a = self.term1._emit(ctx)
+        b = self.term2._emit(ctx)
+        return ctx.op("product", a, b)
+
+    def get_coefficients(self):
+        self._no_host()
+        c1, c2 = _same_batch(self.term1.get_coefficients(), self.term2.get_coefficients())
+        lead = c1[0].shape[:-1]
+        R, C = [[], []], [[], [], [], []]
+        for j in range(c1[0].shape[-1]):
+            for k in range(c2[0].shape[-1]):
+                R[0].append(c1[0][..., j] * c2[0][..., k])
+                R[1].append(c1[1][..., j] + c2[1][..., k])
+        for x, y in ((c1, c2), (c2, c1)):   # real x complex
+            for j in range(x[0].shape[-1]):
+                for k in range(y[2].shape[-1]):
+                    C[0].append(x[0][..., j] * y[2][..., k])
+                    C[1].append(x[0][..., j] * y[3][..., k])
+                    C[2].append(x[1][..., j] + y[4][..., k])
+                    C[3].append(y[5][..., k] + 0.0 * x[0][..., j])
+        for j in range(c1[2].shape[-1]):
+            aj, bj, cj, dj = (c1[i][..., j] for i in range(2, 6))
+            for k in range(c2[2].shape[-1]):
+                ak, bk, ck, dk = (c2[i][..., k] for i in range(2, 6))
+                C[0] += [0.5 * (aj * ak + bj * bk), 0.5 * (aj * ak - bj * bk)]
+                C[1] += [0.5 * (bj * ak - aj * bk), 0.5 * (bj * ak + aj * bk)]
+                C[2] += [cj + ck, cj + ck]
+                C[3] += [dj - dk, dj + dk]
+        st = lambda v: np.stack(v, axis=-1) if v else np.empty(lead + (0,))
+        return tuple(st(v) for v in R + C)
+
+
+class TermDiff(Term):
+    """The covariance of the derivative process, -k'' (terms.py:304-330): ar <- -ar cr^2, (a, b) <- (a (d^2 - c^2) + 2 b c d,
+    b (d^2 - c^2) - 2 a c d); rates unchanged.  (Not every kernel has a derivative process: TermDiff(RealTerm) is not a
+    valid covariance.)"""
+
+    def __init__(self, term):
+        if isinstance(term, TermConvolution):
+            raise TypeError(_CONV_OUTER)
+        self.term = term
+
+    def _has_tensors(self):
+        return self.term._has_tensors()
+
+    def _uses_algebra(self):
+        return True
+
+    def _emit(self, ctx):
+        return ctx.op("diff", self.term._emit(ctx))
+
+    def get_coefficients(self):
+        self._no_host()
+        ar, cr, a, b, c, d = self.term.get_coefficients()
+        q = (d - c) * (d + c)   # d^2 - c^2 without the cancellation of two rounded squares
+        return (-ar * cr**2, cr, a * q + 2 * b * c * d, b * q - 2 * a * c * d, c, d)
+
+
+_CONV_SERIES = 9
+
+
+def _conv_FG(z):
+    """F(z) = 2 (cosh z - 1) / z^2 and G(z) = 2 (z - sinh z) / z^2 at complex z.  The closed forms lose 2 / |z|^2 in
+    relative accuracy at small z (an exposure time is short against the kernel's time scales), so below |z| = 1/2 the power
+    series are summed -- the same split as the device kernel (csrc/c2_term_expr.hip, conv_fg)."""
+    z = np.asarray(z, dtype=np.complex128)
+    w = z * z
+    f = g = np.zeros_like(z)
+    for k in range(_CONV_SERIES - 1, -1, -1):
+        f = f * w + 2.0 / math.factorial(2 * k + 2)
+        g = g * w - 2.0 / math.factorial(2 * k + 3)
+    with np.errstate(all="ignore"):
+        F = 2.0 * (np.cosh(z) - 1.0) / w
+        G = 2.0 * (z - np.sinh(z)) / w
+    small = np.abs(z) ** 2 < 0.25
+    return np.where(small, f, F), np.where(small, z * g, G)
+
+
+def _conv_value(xp, coefs, cof, dt, tau):
+    """The boxcar-convolved kernel at lags tau (terms.py:421-482), piecewise in |tau| < dt, on numpy arrays (xp = numpy) or
+    torch tensors (xp = torch).  coefs: the INNER term's coefficients; cof(v, j): coefficient j, a float or broadcastable
+    against tau; dt likewise."""
+    ar, cr, ac, bc, cc, dc = coefs
+
+    def fn(name, v):
+        return getattr(math, name)(v) if isinstance(v, float) else getattr(xp, name)(v)
+
+    tau = abs(tau)
+    dpt, dmt = dt + tau, dt - tau
+    large, small = 0.0 * tau, 0.0 * tau
+    for j in range(ar.shape[-1]):
+        a, c = cof(ar, j), cof(cr, j)
+        crd = c * dt
+        norm = 2.0 * a / (crd * crd)
+        big = norm * (fn("cosh", crd) - 1.0) * xp.exp(-c * tau)
+        x = c * dmt
+        large = large + big
+        small = small + big + norm * (x - xp.sinh(x))
+    for j in range(ac.shape[-1]):
+        a, b, c, d = cof(ac, j), cof(bc, j), cof(cc, j), cof(dc, j)
+        cd, dd, c2, d2 = c * dt, d * dt, c * c, d * d
+        n = c2 + d2
+        C1 = a * (c2 - d2) + 2.0 * b * c * d
+        C2 = b * (c2 - d2) - 2.0 * a * c * d
+        norm = 1.0 / ((dt * n) * (dt * n))
+        k0, cdt, sdt = xp.exp(-c * tau), xp.cos(d * tau), xp.sin(d * tau)
+        ct = 2.0 * (fn("cosh", cd) * fn("cos", dd) - 1.0)
+        st = 2.0 * (fn("sinh", cd) * fn("sin", dd))
+        large = large + ((C1 * ct - C2 * st) * cdt + (C2 * ct + C1 * st) * sdt) * (k0 * norm)
+        edmt, edpt = xp.exp(-c * dmt), xp.exp(-c * dpt)
+        ct = edmt * xp.cos(d * dmt) + edpt * xp.cos(d * dpt) - 2.0 * k0 * cdt
+        st = edmt * xp.sin(d * dmt) + edpt * xp.sin(d * dpt) - 2.0 * k0 * sdt
+        small = small + 2.0 * (a * c + b * d) * n * dmt * norm + (C1 * ct + C2 * st) * norm
+    return xp.where(tau >= dt, large, small)
+
+
+class TermConvolution(Term):
+    """The kernel integrated over a boxcar of width `delta`, e.g. an exposure time (terms.py:333-482): new amplitudes, and a
+    diagonal shift `delta_diag` that get_celerite_matrices adds to diag; get_value is piecewise for |tau| < delta.  It must be
+    the OUTERMOST term.  `delta` is data, not a hyper-parameter: a float, a numpy (B,) array (one exposure time per series) or
+    a tensor that does not require grad.
+
+    The semiseparable form (compute / log_likelihood / the conditional MEAN at new times, core.py:68-113) is exact for lags
+    >= delta, as in the reference: observations closer than delta to each other, or predictions closer than delta to an
+    observation, see the tail formula instead of the piecewise one.  The conditional variance / covariance use get_value_grid
+    and are piecewise-exact."""
+
+    def __init__(self, term, delta):
+        if isinstance(term, TermConvolution):
+            raise TypeError(_CONV_OUTER)
+        if _is_tensor(delta):
+            if delta.requires_grad:
+                raise TypeError("TermConvolution: delta is data, not a hyper-parameter (it must not require grad)")
+        elif np.ndim(delta) == 0:
+            delta = float(delta)
+        else:
+            delta = np.asarray(delta, dtype=np.float64).reshape(-1)
+        self.term, self.delta = term, delta
+
+    def _has_tensors(self):
+        return self.term._has_tensors() or _is_tensor(self.delta)
+
+    def _uses_algebra(self):
+        return True
+
+    def _emit(self, ctx):
+        h = self.term._emit(ctx)
+        return ctx.op("convolve", h, col=ctx.add(self.delta))
+
+    def _dt_host(self):
+        return self.delta if isinstance(self.delta, float) else self.delta[:, None]
+
+    def _convolved(self):
+        """(coefficients, delta_diag) on the host: (a - i b) <- (a - i b) F(z) and delta_diag = sum Re (a - i b) G(z) with
+        z = (c - i d) delta (d = b = 0 for the real terms) -- the reference's terms.py:350-410 in complex arithmetic."""
+        ar, cr, a, b, c, d = self.term.get_coefficients()
+        dt = self._dt_host()
+        Fr, Gr = _conv_FG(cr * dt + 0j)
+        Fc, Gc = _conv_FG((c - 1j * d) * dt)
+        w = (a - 1j * b) * Fc
+        shift = np.sum(ar * Gr.real, axis=-1, keepdims=True) + np.sum(((a - 1j * b) * Gc).real, axis=-1, keepdims=True)
+        one = np.ones_like(w.real)
+        return (ar * Fr.real, cr * np.ones_like(Fr.real), w.real, -w.imag, c * one, d * one), shift
+
+    def get_coefficients(self):
+        self._no_host()
+        return self._convolved()[0]
+
+    def get_delta_diag(self):
+        """delta_diag (terms.py:353-378), host parameters: a float, or (B, 1) with per-series coefficients / delta."""
+        self._no_host()
+        out = self._convolved()[1]
+        return float(out[0]) if out.ndim == 1 else out
+
+    def _shift_device(self, B, device):
+        """delta_diag as a float (shared host parameters) or a (B, 1) device tensor."""
+        import torch
+
+        if self._has_tensors():
+            from . import autograd
+
+            return autograd.term_coefficients(self.program, self.parameter_matrix(B), B, with_shift=True)[6].detach()[:, None]
+        s = self.get_delta_diag()
+        return s if isinstance(s, float) else torch.from_numpy(np.ascontiguousarray(s)).to(device)
+
+    def _k0_shift(self, B, device):
+        return self._shift_device(B, device)
+
+    def _shifted(self, diag):
+        return (diag + self._shift_device(diag.shape[0], diag.device)).contiguous()
+
+    def get_psd(self, omega):
+        """The inner term's spectrum times sinc^2(delta omega / 2) (terms.py:412-419)."""
+        psd0 = self.term.get_psd(omega) if not (_is_tensor(self.delta) and not self.term._has_tensors()) else None
+        if _is_tensor(psd0) or psd0 is None:
+            import torch
+
+            dev = self.delta.device if psd0 is None else psd0.device
+            if psd0 is None:
+                psd0 = torch.as_tensor(np.atleast_2d(self.term.get_psd(omega)), device=dev)
+            w = torch.as_tensor(omega, dtype=torch.float64, device=dev).reshape(1, -1)
+            dt = self.delta if _is_tensor(self.delta) else torch.as_tensor(self.delta, dtype=torch.float64, device=dev)
+            arg = 0.5 * dt.reshape(-1, 1) * w
+            return psd0 * torch.sinc(arg / math.pi) ** 2
+        w = np.atleast_1d(np.asarray(omega, dtype=np.float64))
+        arg = 0.5 * self._dt_host() * (w if psd0.ndim == 1 else w.reshape(1, -1))
+        return psd0 * np.sinc(arg / np.pi) ** 2
+
+    def get_value(self, tau):
+        """The piecewise convolved kernel (terms.py:421-482), numpy; shared coefficients and a float delta only."""
+        self._no_host()
+        co = self.term.get_coefficients()
+        if any(v.ndim == 2 for v in co) or not isinstance(self.delta, float):
+            raise ValueError("TermConvolution.get_value: shared coefficients only (use get_value_device for a batch)")
+        return _conv_value(np, co, lambda v, j: float(v[j]), self.delta, np.atleast_1d(np.asarray(tau, dtype=np.float64)))
+
+    def get_value_device(self, tau):
+        """The piecewise convolved kernel on the device (a torch expression on the lag tensor: the O(N M) prediction path)."""
+        import torch
+
+        B, extra = tau.shape[0], (1,) * (tau.dim() - 1)
+        inner = self.term
+        if inner._has_tensors():
+            co, batched = inner._device_coefs(B)[0], True
+        else:
+            co = inner.get_coefficients()
+            batched = any(v.ndim == 2 for v in co)
+            if batched:
+                co = inner._dev_coefs(tau.device, B)[0][:6]
+        cof = (lambda v, j: v[:, j].reshape((-1,) + extra)) if batched else (lambda v, j: float(v[j]))
+        dt = self.delta
+        if not isinstance(dt, float):
+            dt = dt.detach().to(tau.device) if _is_tensor(dt) else torch.from_numpy(dt).to(tau.device)
+            dt = dt.reshape((-1,) + extra) if dt.numel() > 1 else dt.reshape(())
+        return _conv_value(torch, co, cof, dt, tau)
+
+    def get_value_grid(self, t1, t2, B=None):
+        """k(t1[n] - t2[m]), (B, N, M), piecewise for |lag| < delta: get_value_device on the lag tensor."""
+        nb = B if B is not None else max(t.shape[0] if t.dim() == 2 else 1 for t in (t1, t2))
+        a = t1 if t1.dim() == 2 else t1[None].expand(nb, -1)
+        b = t2 if t2.dim() == 2 else t2[None].expand(nb, -1)
+        return self.get_value_device(a[:, :, None] - b[:, None, :]).contiguous()
 
 
 def _stack(*cols):

@@ -354,6 +354,72 @@ int c2_noise_mean_apply(int64_t B, int64_t N, const double *yerr, int yerr_is_si
 int c2_noise_mean_rev(int64_t B, int64_t N, const double *jitter, const double *bdiag, const double *by,
                       const int32_t *flag, double *bjitter, double *bmean, c2_stream_t stream);
 
+/* TERM ALGEBRA on the device (csrc/c2_term_expr.hip): sums, PRODUCTS (terms.py:238-301), DERIVATIVES (terms.py:304-330)
+ * and the exposure-time CONVOLUTION (terms.py:333-410) of the five term kinds above.  A product of two celerite kernels is
+ * again a celerite kernel, so all of it is a map parameters -> coefficients in front of c2_loglik_terms[_grad]; only the
+ * convolution adds something new, one number per series: `shift`, which the caller adds to the diagonal
+ * (c2_noise_mean_shift_apply) and whose cotangent is the row sum of bdiag (c2_noise_mean_shift_rev).
+ *
+ * An EXPRESSION (c2_term_expr, passed by value to the kernels like c2_term_program) is the leaf program followed by
+ * operation records in post-order.  Coefficients live in REGISTERS: real register k holds one (ar, cr) pair, complex
+ * register k one (ac, bc, cc, dc) quadruple.  The leaves fill real registers [0, leaves.Jr) and complex registers
+ * [0, leaves.Jc) (their jr / jc, exactly as in the flat program, but without its width limit); operation i reads the
+ * register ranges a and b (b unused by DIFF and CONVOLVE) and writes `out`, which starts at the first register no leaf
+ * and no earlier operation wrote (so a result never overlaps anything still needed, and every register is written once):
+ *   C2_OP_SUM       out = a followed by b                                  out.nr = a.nr + b.nr, out.nc = a.nc + b.nc
+ *   C2_OP_PRODUCT   reals a x b; complex: real(a) x complex(b), real(b) x complex(a), then per complex pair the
+ *                   (dj - dk) and the (dj + dk) term                       out.nr = a.nr b.nr,
+ *                                                                          out.nc = a.nr b.nc + b.nr a.nc + 2 a.nc b.nc
+ *   C2_OP_DIFF      ar <- -ar cr^2; (a, b) <- (a (d^2 - c^2) + 2 b c d, b (d^2 - c^2) - 2 a c d); same sizes
+ *   C2_OP_CONVOLVE  boxcar of width delta = P[col] (data: its column of bP stays 0); same sizes; LAST operation only;
+ *                   shift[b] = delta_diag of terms.py:350-380
+ * The result of the expression is `out` of the last operation (the leaf registers themselves when nops = 0); its width
+ * out.nr + 2 out.nc <= 32.  NR / NC = registers in all (leaves + results), at most C2_EXPR_REGS_MAX each.
+ * The registers are kept in the caller's `work` buffer as [field of register][series] (consecutive lanes, consecutive
+ * addresses): 2 NR + 4 NC doubles per series forward, twice that in reverse (values + cotangents). */
+#define C2_OP_SUM 0
+#define C2_OP_PRODUCT 1
+#define C2_OP_DIFF 2
+#define C2_OP_CONVOLVE 3
+#define C2_EXPR_OPS_MAX 16
+#define C2_EXPR_REGS_MAX 256
+typedef struct {
+  int32_t r0, nr, c0, nc; /* real registers [r0, r0 + nr), complex registers [c0, c0 + nc) */
+} c2_term_range;
+typedef struct {
+  int32_t op, col; /* col: CONVOLVE only, the column of P that holds delta */
+  c2_term_range a, b, out;
+} c2_term_op;
+typedef struct {
+  c2_term_program leaves;
+  int32_t nops, NR, NC, reserved;
+  c2_term_op op[C2_EXPR_OPS_MAX];
+} c2_term_expr;
+/* Bytes of `work` for B series (the reverse's need; the forward takes half). 0 for an invalid expression. */
+size_t c2_term_expr_workspace_bytes(const c2_term_expr *expr, int64_t B);
+/* P -> the coefficients of the expression's result, (B,Jr) / (B,Jc) with (Jr, Jc) = (out.nr, out.nc) of the last
+ * operation, shift (B,) (0 without a convolution) and flag (B,) as c2_term_coefficients (a leaf SHO on the wrong side). */
+int c2_term_expr_coefficients(const c2_term_expr *expr, int64_t B, const double *P, int64_t p_bs, double *ar, double *cr,
+                              double *ac, double *bc, double *cc, double *dc, double *shift, int32_t *flag, void *work,
+                              size_t work_bytes, c2_stream_t stream);
+/* The reverse: the forward is replayed into `work`, the operation records are reversed (last to first) into cotangents of
+ * the leaf registers, then the leaves as c2_term_coefficients_rev.  bshift (B,) nullable (= 0).  tflag / lflag / ll are
+ * settled as in c2_term_coefficients_rev. */
+int c2_term_expr_coefficients_rev(const c2_term_expr *expr, int64_t B, const double *P, int64_t p_bs, const double *bar,
+                                  const double *bcr, const double *bac, const double *bbc, const double *bcc,
+                                  const double *bdc, const double *bshift, const int32_t *tflag, int32_t *lflag,
+                                  double *ll, double *bP, void *work, size_t work_bytes, c2_stream_t stream);
+/* c2_noise_mean_apply with one more per-series term: diag[b,n] = yerr[b,n]^2 (or yerr[b,n]) + jitter[b]^2 + shift[b]
+ * (shift nullable = the kernel without it, bit for bit) ... */
+int c2_noise_mean_shift_apply(int64_t B, int64_t N, const double *yerr, int yerr_is_sigma, const double *jitter,
+                              const double *mean, const double *shift, const double *y, double *diag, double *r,
+                              c2_stream_t stream);
+/* ... and c2_noise_mean_rev with bshift[b] = sum_n bdiag[b,n] (the row sum bjitter is formed from: same fixed order, no
+ * atomics); any of the three outputs may be NULL; a series with flag[b] != 0 or tflag[b] != 0 (both nullable) gets zeros. */
+int c2_noise_mean_shift_rev(int64_t B, int64_t N, const double *jitter, const double *bdiag, const double *by,
+                            const int32_t *flag, const int32_t *tflag, double *bjitter, double *bmean, double *bshift,
+                            c2_stream_t stream);
+
 /* dot_tril -- python/celerite2/numpy.py:100-102: Z = Y * sqrt(d)[:,None];
  * Z += tril(U W^T) Z.  Y == Z allowed. */
 int c2_dot_tril(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs, const double *c,
