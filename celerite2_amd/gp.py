@@ -130,6 +130,50 @@ class GaussianProcess:
             out = out + self.mean
         return out[:, 0] if size is None else out
 
+    # -- the diagonal of (K + D)^-1 in linear time (ops.inverse_diag; no counterpart in the reference) ------------
+    def _nan_failed(self, *xs):
+        """Series whose factorisation failed (compute(..., quiet=True)) hold NaN."""
+        failed = (self._flag != 0)[:, None]
+        nan = torch.full((), math.nan, dtype=torch.float64, device=self._diag.device)
+        return tuple(torch.where(failed, nan, x) for x in xs)
+
+    def _q_alpha(self, y):
+        self._check_vector(y)
+        r = (y - self.mean)[..., None].contiguous()
+        z = ops.solve_lower(self._t, self._c, self._U, self._W, r)[..., 0]   # (B, N): a view of a contiguous (B, N, 1)
+        return ops.inverse_diag(self._t, self._c, self._U, self._W, self._d, z=z, alpha=z)
+
+    def inverse_diagonal(self):
+        """q (B, N): q[b, n] = [(K + D)^-1]_nn of the matrix `compute` factored, O(N J^2) per series."""
+        self._need()
+        return self._nan_failed(ops.inverse_diag(self._t, self._c, self._U, self._W, self._d))[0]
+
+    def predict_observed(self, y, *, return_var=False, include_mean=True):
+        """The conditional mean (B, N) of the process at the observed times, y - D alpha with alpha = (K + D)^-1 (y - mean),
+        and with `return_var` its variance (B, N), D_n - D_n^2 q_n with q the diagonal of (K + D)^-1 -- from
+        K (K + D)^-1 K = K - D + D (K + D)^-1 D.  One solve_lower and one inverse_diag pass: O(N J^2) per series, no
+        N x N cross-covariance (`predict(y, return_var=True)` builds one and solves with N right-hand sides).
+
+        This is the variance under the FACTORED matrix.  For every kernel but a TermConvolution that is the kernel itself
+        and the result is `predict`'s; under a TermConvolution the factored matrix is the semiseparable form (exact for
+        lags >= delta), whereas `predict` evaluates the piecewise kernel for its cross-covariance, so the two differ
+        there and only there.  D is the diagonal given to `compute`."""
+        self._need()
+        q, alpha = self._q_alpha(y)
+        mu = y - self._diag * alpha
+        if not include_mean:
+            mu = mu - self.mean
+        if not return_var:
+            return self._nan_failed(mu)[0]
+        return self._nan_failed(mu, self._diag - self._diag * self._diag * q)
+
+    def leave_one_out(self, y):
+        """(mean, var), each (B, N): the predictive distribution of y_n from all the OTHER points,
+        mean = y_n - alpha_n / q_n and var = 1 / q_n (the white noise of point n included)."""
+        self._need()
+        q, alpha = self._q_alpha(y)
+        return self._nan_failed(y - alpha / q, 1.0 / q)
+
     # -- conditional distribution, core.py:430-478 ------------------------------------------------------
     def condition(self, y, t=None, *, include_mean=True, kernel=None):
         self._need()

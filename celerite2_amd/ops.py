@@ -18,6 +18,7 @@ __all__ = [
     "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "general_matmul_lower",
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
+    "inverse_diag",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
     "noise_mean_shift_apply", "noise_mean_shift_rev",
@@ -401,6 +402,34 @@ def dot_tril(t, c, U, W, d, Y, Z=None):
 
 
 _KRON_METHODS = {"collapsed": 0, "interleaved": 1}
+
+
+def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None):
+    """q (B, N), the diagonal of the inverse of the factored matrix K + D = L diag(d) L^T, in one backward sweep over
+    d, W (c2_inverse_diag).  With z (B, N) -- solve_lower of a residual -- the same pass also returns
+    alpha = L^-T (z / d) = (K + D)^-1 (y - mean): (q, alpha); `alpha` may be `z` itself (the only aliasing allowed).  Caller-owned outputs `q`,
+    `alpha` are accepted (nothing is allocated then: capturable in a HIP graph)."""
+    B, N, J = _dims(U)
+    q = torch.empty_like(d) if q is None else q
+    if z is None:
+        if alpha is not None:
+            raise ValueError("Invalid shape: alpha (given without z)")
+    elif alpha is None:
+        alpha = torch.empty_like(z)
+    _chk(t, c, U, W, d, z, q, alpha)
+    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
+    _shape("z", z, (B, N)); _shape("q", q, (B, N)); _shape("alpha", alpha, (B, N))
+    # the only aliasing the sweep allows is alpha == z (a row's z is read before its alpha is stored)
+    if q.data_ptr() == d.data_ptr():
+        raise ValueError("Invalid argument: q must not alias d")
+    if z is not None and q.data_ptr() in (z.data_ptr(), alpha.data_ptr()):
+        raise ValueError("Invalid argument: q must not alias z or alpha")
+    if alpha is not None and alpha.data_ptr() == d.data_ptr():
+        raise ValueError("Invalid argument: alpha must not alias d")
+    rc = _lib.load().c2_inverse_diag(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
+                                     _p(W), _p(d), _p(z), _p(q), _p(alpha), _stream())
+    _lib.check(rc, "inverse_diag")
+    return q if z is None else (q, alpha)
 
 
 def _kron_args(t, c, a, U, V, alpha, diag, y, method):

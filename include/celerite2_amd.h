@@ -426,6 +426,19 @@ int c2_dot_tril(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, 
                 int64_t c_bs, const double *U, const double *W, const double *d, const double *Y, double *Z,
                 c2_stream_t stream);
 
+/* Diagonal of the inverse of the factored matrix, q[b, n] = [(K + D)^-1]_nn, from d, W of c2_factor in ONE backward sweep
+ * with a symmetric J x J state (csrc/c2_invdiag.hip; O(N J^2) per series, the cost class of factor).  No counterpart in
+ * the reference, whose predictive variance at the observed times solves against the N x N cross-covariance
+ * (core.py:134-140) and which has no leave-one-out entry point; parity is pinned by the dense inverse.  With D the
+ * diagonal the caller added to the kernel:  variance of the process at the data = D_n - D_n^2 q_n;  leave-one-out mean
+ * y_n - alpha_n / q_n and variance 1 / q_n.  With z (B,N) -- the c2_solve_lower output of the residual -- the same pass
+ * also carries the one-column upper solve alpha = L^-T (z / d) = (K + D)^-1 (y - mean) (forward.hpp:193-207): it reads
+ * the same t, U, W, d rows in the same order.  z and alpha are both given or both NULL; alpha may alias z, and that is
+ * the only aliasing allowed (q must not alias d, z or alpha; alpha must not alias d).  Rows of a series whose factorisation failed hold garbage (never another series'). */
+int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
+                    const double *U, const double *W, const double *d, const double *z /* nullable */, double *q,
+                    double *alpha /* nullable iff z is */, c2_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * HOST entry points (B == 1, synchronous) -- what celerite2.driver /
  * celerite2.backprop bind.  Same argument meaning as the pybind11 functions of

@@ -1,5 +1,5 @@
 """One op of the device ABI a few times, for profilers: python tools/op_run.py <op> <B> <N> <J> [reps]
-op: loglik | loglik_grad | terms | terms_grad (coefficient-level, bench coefficients) | factor | factor_s | factor_rev | solve_rhs<nrhs> | rev_rhs<nrhs> (solve_lower_rev) | predict[_var|_cov] | chain (factor_s + solve_lower F + solve_lower_rev + factor_rev)"""
+op: loglik | loglik_grad | terms | terms_grad (coefficient-level, bench coefficients) | factor | factor_s | inverse_diag[_z] (the mapping: C2_INVDIAG_LANES) | factor_rev | solve_rhs<nrhs> | rev_rhs<nrhs> (solve_lower_rev) | predict[_var|_cov] | chain (factor_s + solve_lower F + solve_lower_rev + factor_rev)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -41,7 +41,13 @@ if op.startswith("rev_rhs"):   # rev_rhs<nrhs>: solve_lower_rev with that many r
 if op.startswith("solve_rhs"):   # solve_rhs<nrhs>: solve_lower with that many right-hand sides, in place
     d_, Wf, fl_ = ops.factor(t, c, a, U, V)
     Yr = torch.randn((B, N, int(op[9:])), dtype=torch.float64, device=dev)
+idargs = None
+if op.startswith("inverse_diag"):
+    d_, Wf, fl_ = ops.factor(t, c, a, U, V)
+    zq = ops.solve_lower(t, c, U, Wf, Y)[..., 0] if op.endswith("_z") else None
+    idargs = dict(z=zq, q=torch.empty_like(d_), alpha=None if zq is None else torch.empty_like(d_))
 def run():
+    if idargs is not None: return ops.inverse_diag(t, c, U, Wf, d_, **idargs)
     if Yr is not None: return ops.solve_lower(t, c, U, Wf, Yr, Z=Yr)
     if revargs is not None: return ops.solve_lower_rev(*revargs)
     if op == "terms": return ops.loglik_terms(*targs)
