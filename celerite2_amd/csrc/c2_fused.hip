@@ -4,6 +4,7 @@
 // checkpoint/recompute kernels in c2_loglik.hip (tests compare the two) and as the A/B baseline in profiles/.
 #include "c2_common.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 extern "C" int c2_factor_rev_acc(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                  int64_t c_bs, const double *U, const double *d, const double *W, const double *S,

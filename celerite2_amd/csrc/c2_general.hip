@@ -21,6 +21,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2g {
 using namespace c2;

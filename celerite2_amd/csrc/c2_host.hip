@@ -27,8 +27,7 @@
 #include <vector>
 
 #include "../../include/celerite2_amd.h"
-
-extern "C" void c2_internal_set_error(const char *msg);
+#include "c2_internal.hpp"
 
 namespace {
 

@@ -16,216 +16,29 @@
 // q_n <= 1 / D_n bounds it.  The upper solve is internal::backward (internal.hpp:148-189) with one right-hand side:
 //   F <- p_n o (F + u_{n+1} alpha_{n+1}),   alpha_n = z_n / d_n - w_n^T F.
 //
-// Three mappings (the shape of factor / solve_upper in this library):
-//   k_invdiag_lane   J <= 8, chip-filling batches: ONE LANE per series, the packed triangle of M (36 doubles at J = 8),
-//                    F in registers, c in a lane-private column of LDS.  The rows of U, W are read back to front with the non-temporal hint (touched
-//                    once), RA rows ahead; t, d, z arrive as 16-row runs (a whole 128-byte line per lane and stream when
-//                    N is a multiple of 16) into a lane-private column of LDS, where q, alpha take the places of d, z
-//                    and leave as whole lines too (two scalar output streams: the half-line lesson of profiles/r06_halflines.md).
-//   k_invdiag_group  J <= 32, small batches: a GROUP of G lanes per series, lane j owns column j of M (= row j: M is
+// Two mappings, chosen by width alone (a one-lane mapping was measured, lost at every batch and was removed: DESIGN.md
+// section 3):
+//   k_invdiag_group  J <= 32: a GROUP of G lanes per series, lane j owns column j of M (= row j: M is
 //                    symmetric, so h_j = sum_i M_ij v_i is a lane-local dot product against the vector v, which the
 //                    group shares through LDS); s and the solve's w^T F are one interleaved DPP butterfly (gsum2).
 //                    Scalar streams move transposed in time, 16 rows per block, as in k_sweep1.
 //   k_invdiag_wide   33 <= J <= 128: a workgroup per series, M in LDS (128 KiB at J = 128), as csrc/c2_wide.hip.
 // There is no time-parallel form: at one series the sweep is latency-bound like the other row-by-row kernels.
-// No atomics anywhere: two calls give identical bits.  B is in grid.x for all three.
+// No atomics anywhere: two calls give identical bits.  B is in grid.x for both.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <type_traits>
 
 #include "c2_common.hpp"
-#include "c2_dispatch.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
-
-extern "C" void c2_internal_set_error(const char *msg);
+#include "c2_internal.hpp"
 
 namespace c2 {
 namespace invdiag {
 
-typedef double d2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double ld1_nt(const double *p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ void ld2_nt(const double *p, double &a, double &b) {
-  const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(p));
-  a = v.x; b = v.y;
-}
-__device__ __forceinline__ void st1_nt(double *p, double v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void st2_nt(double *p, double a, double b) {
-  d2v w; w.x = a; w.y = b;
-  __builtin_nontemporal_store(w, reinterpret_cast<d2v *>(p));
-}
-
 constexpr int kRows = 16;   // rows per block of the scalar streams: 128 bytes per series
-
-// index of M(i, j), i <= j, in the packed upper triangle
-template <int J>
-__device__ __forceinline__ constexpr int tri(int i, int j) { return i * J - (i * (i - 1)) / 2 + (j - i); }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// One lane per series.  VEC: N even and every array 16-byte aligned (row arrays: J even as well) -> 16-byte requests.
-// RA: rows of U, W in flight ahead of the sweep (divides 16).
-// ---------------------------------------------------------------------------------------------------------------------
-template <int J, bool HASZ, bool VEC, int RA>
-__global__ __launch_bounds__(kWave) void k_invdiag_lane(int64_t B, int64_t N, const double *__restrict__ t, int64_t t_bs,
-                                                        const double *__restrict__ c, int64_t c_bs,
-                                                        const double *__restrict__ U, const double *__restrict__ W,
-                                                        const double *__restrict__ d, const double *z, double *__restrict__ q,
-                                                        double *alpha) {
-  constexpr int T = J * (J + 1) / 2, R = kRows;
-  constexpr bool VROW = VEC && (J % 2 == 0);
-  static_assert(R % RA == 0, "the ring slot of a row must be static");
-  int64_t b = (int64_t)blockIdx.x * kWave + threadIdx.x;
-  const bool valid = b < B;
-  if (!valid) b = B - 1;
-  // three per-lane offsets against the uniform bases instead of seven per-lane pointers (registers)
-  const int64_t ot = b * t_bs, on = b * N, oj = b * N * J;
-  const double *tb = t + ot, *db = d + on, *zb = HASZ ? z + on : nullptr;
-  const double *Ub = U + oj, *Wb = W + oj;
-  double *qb = q + on, *ab = HASZ ? alpha + on : nullptr;
-
-  __shared__ double sC[J][kWave];   // c of this lane's series (lane-private column)
-  double M[T], F[J];   // F: the solve's state with u_{n+1} alpha_{n+1} already added (internal.hpp:183)
-#pragma unroll
-  for (int i = 0; i < J; ++i) { sC[i][threadIdx.x] = c[b * c_bs + i]; F[i] = 0.0; }
-#pragma unroll
-  for (int e = 0; e < T; ++e) M[e] = 0.0;
-  double tnext = tb[N - 1];
-
-  // scalar streams of a block of 16 rows [n0, n0 + 16), clamped to the series: global -> this lane's column of the LDS
-  // tiles ([pair of rows][lane][2]: a lane only ever touches its own column, so no ordering between lanes is needed)
-  __shared__ __attribute__((aligned(16))) double sT[R / 2][kWave][2], sD[R / 2][kWave][2], sZ[HASZ ? R / 2 : 1][kWave][2];
-  const int lane = threadIdx.x;
-  auto load_scalars = [&](int64_t n0) {
-    if constexpr (VEC) {
-#pragma unroll
-      for (int k = 0; k < R; k += 2) {
-        int64_t n = n0 + k;
-        n = n < N - 2 ? n : N - 2;
-        ld2_nt(tb + n, sT[k / 2][lane][0], sT[k / 2][lane][1]);
-        ld2_nt(db + n, sD[k / 2][lane][0], sD[k / 2][lane][1]);
-        if constexpr (HASZ) ld2_nt(zb + n, sZ[k / 2][lane][0], sZ[k / 2][lane][1]);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        int64_t n = n0 + k;
-        n = n < N - 1 ? n : N - 1;
-        sT[k / 2][lane][k % 2] = ld1_nt(tb + n);
-        sD[k / 2][lane][k % 2] = ld1_nt(db + n);
-        if constexpr (HASZ) sZ[k / 2][lane][k % 2] = ld1_nt(zb + n);
-      }
-    }
-  };
-  double ru[RA][J], rw[RA][J];
-  auto load_row = [&](int slot, int64_t n) {
-    n = n > 0 ? n : 0;
-    if constexpr (VROW) {
-#pragma unroll
-      for (int i = 0; i < J; i += 2) {
-        ld2_nt(Ub + n * J + i, ru[slot][i], ru[slot][i + 1]);
-        ld2_nt(Wb + n * J + i, rw[slot][i], rw[slot][i + 1]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < J; ++i) {
-        ru[slot][i] = ld1_nt(Ub + n * J + i);
-        rw[slot][i] = ld1_nt(Wb + n * J + i);
-      }
-    }
-  };
-
-  const int64_t nblk = (N + R - 1) / R;
-  int64_t n0 = (nblk - 1) * R;
-  load_scalars(n0);
-  // slot k of the ring: the last row n <= N - 1 with n mod RA == k
-#pragma unroll
-  for (int k = 0; k < RA; ++k) load_row(k, (N - 1) - (((N - 1) - k) % RA + RA) % RA);
-
-  auto block = [&](auto checked_tag) {
-    constexpr bool CHECKED = decltype(checked_tag)::value;
-#pragma unroll
-    for (int rr = 0; rr < R; ++rr) {
-      const int r = R - 1 - rr;
-      const int64_t n = n0 + r;
-      if (!CHECKED || n < N) {
-        const int slot = r % RA;
-        double (&u)[J] = ru[slot], (&w)[J] = rw[slot];
-        const double tn = sT[r / 2][lane][r % 2], dn = sD[r / 2][lane][r % 2];
-        const double dt = tn - tnext;   // <= 0
-        tnext = tn;
-        double p[J], v[J], h[J];
-#pragma unroll
-        for (int i = 0; i < J; ++i) { p[i] = exp_decay(sC[i][lane] * dt); v[i] = p[i] * w[i]; }
-        double red = 0.0;
-        if constexpr (HASZ) {
-#pragma unroll
-          for (int i = 0; i < J; ++i) {
-            F[i] = p[i] * F[i];   // internal.hpp:186
-            red = fma(w[i], F[i], red);
-          }
-        }
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-          double acc = 0.0;
-#pragma unroll
-          for (int k = 0; k < J; ++k) acc = fma(M[i <= k ? tri<J>(i, k) : tri<J>(k, i)], v[k], acc);
-          h[i] = acc;
-          s = fma(v[i], acc, s);
-          __builtin_amdgcn_sched_barrier(0);   // (row by row: the scheduler's look-ahead costs registers, not time)
-        }
-        const double rd = rcp_nr(dn);
-        const double qn = rd + s;
-        double e[J];
-#pragma unroll
-        for (int i = 0; i < J; ++i) e[i] = fma(qn, u[i], -(p[i] * h[i]));
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-#pragma unroll
-          for (int k = i; k < J; ++k) {
-            const double x = fma(-h[i], u[k], p[k] * M[tri<J>(i, k)]);
-            M[tri<J>(i, k)] = fma(u[i], e[k], p[i] * x);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        sD[r / 2][lane][r % 2] = qn;   // q, alpha take the places of d, z in the tile
-        if constexpr (HASZ) {
-          const double an = fma(sZ[r / 2][lane][r % 2], rd, -red);   // internal.hpp:187
-          sZ[r / 2][lane][r % 2] = an;
-#pragma unroll
-          for (int i = 0; i < J; ++i) F[i] = fma(u[i], an, F[i]);   // :183, for the row below
-        }
-        load_row(slot, n - RA);   // (the slot is free again: its row comes back RA steps from now)
-        __builtin_amdgcn_sched_barrier(0);   // (a step's registers stay a step's: no exponentials of later rows hoisted)
-      }
-    }
-    // q, alpha of the block: whole runs of 16 rows
-    if (valid) {
-      if constexpr (VEC) {
-#pragma unroll
-        for (int k = 0; k < R; k += 2)
-          if (!CHECKED || n0 + k < N) {
-            st2_nt(qb + n0 + k, sD[k / 2][lane][0], sD[k / 2][lane][1]);
-            if constexpr (HASZ) st2_nt(ab + n0 + k, sZ[k / 2][lane][0], sZ[k / 2][lane][1]);
-          }
-      } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k)
-          if (!CHECKED || n0 + k < N) {
-            st1_nt(qb + n0 + k, sD[k / 2][lane][k % 2]);
-            if constexpr (HASZ) st1_nt(ab + n0 + k, sZ[k / 2][lane][k % 2]);
-          }
-      }
-    }
-  };
-
-  for (int64_t blk = nblk - 1; blk >= 0; --blk, n0 -= R) {
-    if (blk == nblk - 1) block(std::true_type{});
-    else block(std::false_type{});
-    if (blk > 0) load_scalars(n0 - R);   // (alpha == z: these rows lie below everything stored so far)
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // A group of G lanes per series; lane j owns column j of M.  J <= G (lanes j >= J idle: zero rows, c = 0).
@@ -449,20 +262,6 @@ inline int wide_lds_ready() {
   return rc[dev] == C2_OK ? C2_OK : C2_ERR_HIP;
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-template <int J, bool HASZ>
-inline void launch_lane(bool vec, int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                        const double *U, const double *W, const double *d, const double *z, double *q, double *alpha,
-                        hipStream_t s) {
-  constexpr int RA = 2;
-  const dim3 grid((unsigned)((B + kWave - 1) / kWave));
-  if (vec)
-    hipLaunchKernelGGL((k_invdiag_lane<J, HASZ, true, RA>), grid, dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs, U, W, d, z, q, alpha);
-  else
-    hipLaunchKernelGGL((k_invdiag_lane<J, HASZ, false, RA>), grid, dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs, U, W, d, z, q, alpha);
-}
-
 template <int G>
 inline void launch_group(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                          const double *U, const double *W, const double *d, const double *z, double *q, double *alpha,
@@ -494,23 +293,6 @@ extern "C" int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t,
       if (int e = wide_lds_ready()) return e;
     hipLaunchKernelGGL(k_invdiag_wide, dim3((unsigned)B), dim3(kWideThreads), bytes, s, N, (int)J, t, t_bs, c, c_bs, U, W, d,
                        z, q, alpha);
-    return launch_ok();
-  }
-  // mapping: one lane per series for chip-filling batches of narrow models, a group of lanes per series otherwise
-  bool lane = J <= 8 && B >= opt::ival(opt::k_invdiag_lanes1_min_batch);
-  if (opt::has(opt::k_invdiag_lanes)) lane = J <= 8 && opt::ival(opt::k_invdiag_lanes) == 1;
-  if (lane) {
-    const bool vec = N % 2 == 0 && t_bs % 2 == 0 && aligned16(t) && aligned16(d) && aligned16(q) && aligned16(U) &&
-                     aligned16(W) && (!z || (aligned16(z) && aligned16(alpha)));
-#define C2_ID_LANE(J_)                                                                                       \
-  case J_:                                                                                                   \
-    if (z) launch_lane<J_, true>(vec, B, N, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s);                       \
-    else launch_lane<J_, false>(vec, B, N, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s);                        \
-    break;
-    switch ((int)J) {
-      C2_ID_LANE(1) C2_ID_LANE(2) C2_ID_LANE(3) C2_ID_LANE(4) C2_ID_LANE(5) C2_ID_LANE(6) C2_ID_LANE(7) C2_ID_LANE(8)
-    }
-#undef C2_ID_LANE
     return launch_ok();
   }
   if ((B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;

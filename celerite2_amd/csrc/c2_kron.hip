@@ -33,13 +33,7 @@
 
 #include "../../include/celerite2_amd.h"
 #include "c2_dispatch.hpp"
-
-extern "C" void c2_internal_set_error(const char *msg);
-extern "C" int c2_internal_loglik_grad_rows(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                            int64_t c_bs, const double *a, const double *U, const double *V,
-                                            const double *y, double *ll, double *bt, double *bc, double *ba, double *bU,
-                                            double *bV, double *by, int32_t *flag, void *work, size_t work_bytes,
-                                            c2_stream_t stream);
+#include "c2_internal.hpp"
 
 namespace c2k {
 

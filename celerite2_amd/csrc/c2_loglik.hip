@@ -26,14 +26,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
-
-extern "C" void c2_internal_set_error(const char *msg);
-extern "C" int c2_loglik_grad_composite(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
-                                        const double *c, int64_t c_bs, const double *a, const double *U,
-                                        const double *V, const double *y, double *ll, double *bt, double *bc,
-                                        double *ba, double *bU, double *bV, double *by, int32_t *flag, void *work,
-                                        size_t work_bytes, c2_stream_t stream);
-extern "C" size_t c2_loglik_grad_composite_workspace_bytes(int64_t B, int64_t N, int64_t J);
+#include "c2_internal.hpp"
 
 #ifdef C2_REV_TIMING
 __device__ unsigned long long c2_dbg[8];
@@ -1242,17 +1235,6 @@ int launch_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, c
 }
 }  // namespace
 
-// Two-columns-per-lane variant for J == 8 (c2_loglik4.hip).
-extern "C" int c2_internal_loglik4(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                   const double *a, const double *U, const double *V, const double *y, double *ll,
-                                   int32_t *flag, c2_stream_t stream);
-// Four lanes per series, gradient pair in the scaled frame (c2_loglik_q4.hip, J == 8)
-extern "C" size_t c2_internal_loglik_q4_record_doubles(int64_t B, int64_t N);
-extern "C" int c2_internal_loglik_q4_grad(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                          const double *a, const double *U, const double *V, const double *y, double *ll,
-                                          double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
-                                          int32_t *flag, double *rec, unsigned long long *guard, c2_stream_t stream);
-
 // Which lane mapping serves (B, J)?  Four lanes per series (two columns per lane, J = 8) carry 16 series per wavefront, so
 // they need twice the batch to fill the chip.  Forward-only (c2_loglik4.hip): 14-15 % faster than the eight-lane kernel from
 // 16384 series up, equal at 8192 (profiles/r01_lanes4.md).  Gradient pair (c2_loglik_q4.hip, scaled frame): the batches that
@@ -1270,35 +1252,10 @@ static bool use_lanes4(int64_t B, int64_t J, bool grad) {
 // wavefront on every SIMD.  Measured on MI355X at N = 4096 (profiles/r02_lane_mappings.md): the forward-only kernel
 // wins from 24576 series up (3.3 vs 4.1 ms; 6.7 vs 10.4 ms at 65536), the gradient pair from 24576 up as well (15.7 vs
 // 16.0 ms; 17.2 vs 21.6 ms at 32768; 28.2 vs 41.8 ms at 65536).  C2_LANES=1 forces it.
-// the same kernels compiled per width (c2_loglik_t.hip with C2T_J = 8, 4, 2; 6 as 8 with two empty columns)
-#define C2_DECL_T(J_)                                                                                                  \
-  extern "C" int c2_internal_loglik_t##J_(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c,       \
-                                          int64_t c_bs, const double *a, const double *U, const double *V,           \
-                                          const double *y, double *ll, int32_t *flag, c2_stream_t stream);           \
-  extern "C" size_t c2_internal_loglik_t_record_doubles##J_(int64_t B, int64_t N);                                   \
-  extern "C" int c2_internal_loglik_t_grad##J_(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, \
-                                               int64_t c_bs, const double *a, const double *U, const double *V,      \
-                                               const double *y, double *ll, double *bt, double *bc, double *ba,      \
-                                               double *bU, double *bV, double *by, int32_t *flag, double *rec,       \
-                                               unsigned long long *guard, c2_stream_t stream);
-C2_DECL_T(8)
-C2_DECL_T(6)   // rows of 6 in memory, computed as rows of 8 (c2_loglik_t6.hip)
-C2_DECL_T(4)
-C2_DECL_T(2)
-#undef C2_DECL_T
 // guard words in front of the records of the one-lane path: the head + one per wavefront, rounded to 16 bytes
 static size_t lanes1_gate_words(int64_t B) { return (size_t)((kGateHeadWords + (B + kWave - 1) / kWave + 1) & ~(int64_t)1); }
 // Two lanes per series (c2_loglik_k2.hip, J == 8): 32 series per wavefront -- the batches that
 // give the one-lane mapping half a chip.  C2_LANES=2 forces it.
-extern "C" int c2_internal_loglik_k2_ok(int64_t B, int64_t N, int64_t J);
-extern "C" int c2_internal_loglik_k2(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                     const double *a, const double *U, const double *V, const double *y, double *ll,
-                                     int32_t *flag, c2_stream_t stream);
-extern "C" size_t c2_internal_loglik_k2_record_doubles(int64_t B, int64_t N);
-extern "C" int c2_internal_loglik_k2_grad(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                          const double *a, const double *U, const double *V, const double *y, double *ll,
-                                          double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
-                                          int32_t *flag, double *rec, unsigned long long *guard, c2_stream_t stream);
 static bool use_lanes2(int64_t B, int64_t N, int64_t J, bool grad) {
   if (!c2_internal_loglik_k2_ok(B, N, J)) return false;
   const int forced = opt::has(opt::k_lanes) ? (int)opt::ival(opt::k_lanes) : 0;
@@ -1315,12 +1272,6 @@ static size_t lanes1_record_doubles(int64_t B, int64_t N, int64_t J) {
 }
 // Time-parallel forward pass (c2_timepar.hip; widths 4 and 2): batches too small to fill the chip row by row -- below the
 // one-lane threshold -- of series long enough to cut into chunks.  C2_TIMEPAR=1 forces it, =0 disables it.
-extern "C" size_t c2_internal_timepar_doubles(int64_t B, int64_t N, int64_t J);
-extern "C" size_t c2_internal_loglik_timepar_doubles(int64_t B, int64_t N, int64_t J);
-extern "C" int c2_internal_loglik_timepar(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                          int64_t c_bs, const double *a, const double *U, const double *V,
-                                          const double *y, double *ll, int32_t *flag, double *work,
-                                          unsigned long long *guard, c2_stream_t stream);
 // The single-rhs SOLVES parallel along time (affine chunk maps): a handful of series (B * J <= 512: every driver.* call) is
 // pure latency row by row -- 0.15-0.24 us per row -- against a fixed 40-130 us: level at ~256 / ~420 / ~900 rows (J = 2 / 4 / 8).
 static int64_t timepar_min_rows(int64_t B, int64_t J) {
@@ -1374,38 +1325,6 @@ extern "C" int c2_internal_use_timepar_solve(int64_t B, int64_t N, int64_t J) {
 // 4e-12) and then time (one series of 1e5 rows 1.42 against 1.25 ms):
 // with 32 rows against 64: one series of 1e5 rows 1.68 -> 1.25 ms, 64 x 4096 1.42 -> 1.16 ms (J = 8); beyond 4096 chunks the
 // longer chains cost more: 1e6 rows 3.8 vs 5.0 ms, 32 x 50000 2.4 vs 3.1 ms  (C2_TPG_ROWS=16|32|64 overrides)
-#define C2_DECL_TPG(R_)                                                                                                    \
-  extern "C" size_t c2_internal_timepar_grad_doubles##R_(int64_t B, int64_t N, int64_t J);                               \
-  extern "C" int c2_internal_loglik_grad_timepar##R_(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,     \
-                                                     const double *c, int64_t c_bs, const double *a, const double *U,    \
-                                                     const double *V, const double *y, double *ll, double *bt,           \
-                                                     double *bc, double *ba, double *bU, double *bV, double *by,         \
-                                                     int32_t *flag, double *work, c2_stream_t stream);                   \
-  extern "C" size_t c2_internal_factor_iter_doubles##R_(int64_t B, int64_t N, int64_t J);                                \
-  extern "C" int c2_internal_factor_iter##R_(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,             \
-                                             const double *c, int64_t c_bs, const double *a, const double *U,            \
-                                             const double *V, double *d, double *W, int32_t *flag, double *work,         \
-                                             const unsigned long long **last_word, c2_stream_t stream);                  \
-  extern "C" size_t c2_internal_loglik_wide_doubles##R_(int64_t B, int64_t N, int64_t J);                                \
-  extern "C" int c2_internal_loglik_wide##R_(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,             \
-                                             const double *c, int64_t c_bs, const double *a, const double *U,            \
-                                             const double *V, const double *y, double *ll, int32_t *flag, double *work,  \
-                                             c2_stream_t stream);                                                        \
-  extern "C" size_t c2_internal_factor_rev_timepar_doubles##R_(int64_t B, int64_t N, int64_t J);                         \
-  extern "C" int c2_internal_factor_rev_timepar##R_(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,      \
-                                                    const double *c, int64_t c_bs, const double *U, const double *V,     \
-                                                    const double *d, const double *W, const double *bd, const double *bW, \
-                                                    double *bt, double *bc, double *ba, double *bU, double *bV,          \
-                                                    double *work, c2_stream_t stream);                                   \
-  extern "C" size_t c2_internal_s_rows_doubles##R_(int64_t B, int64_t N, int64_t J);                                     \
-  extern "C" int c2_internal_s_rows##R_(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, \
-                                        int64_t c_bs, const double *d, const double *W, const int32_t *flag, double *Sw, \
-                                        double *scratch, c2_stream_t stream);
-C2_DECL_TPG(64)
-C2_DECL_TPG(32)
-C2_DECL_TPG(16)
-#undef C2_DECL_TPG
-extern "C" int c2_internal_tpg_short_chunks(int64_t B, int64_t N);
 // 0: chunks of 64 rows, 1: of 32, 2: of 16
 extern "C" int c2_internal_tpg_short_chunks(int64_t B, int64_t N) {
   if (opt::has(opt::k_tpg_rows)) return opt::ival(opt::k_tpg_rows) == 16 ? 2 : (opt::ival(opt::k_tpg_rows) == 32 ? 1 : 0);
@@ -1459,9 +1378,7 @@ static double *g_debug_sink = nullptr;
 extern "C" void c2_internal_set_debug_sink(double *device_ptr) { g_debug_sink = device_ptr; }
 extern "C" double *c2_internal_get_debug_sink() { return g_debug_sink; }
 // C2_VERIFY_FALLBACK=0 (diagnostics only): leave the result of the time-parallel form in place whatever its words say
-static bool verify_fallback_enabled() {
-  return !(opt::has(opt::k_verify_fallback) && opt::ival(opt::k_verify_fallback) == 0);
-}
+static bool verify_fallback_enabled() { return !opt::off(opt::k_verify_fallback); }
 static void c2_internal_debug_capture(const double *words, const double *, hipStream_t s) {
   if (g_debug_sink) (void)hipMemcpyAsync(g_debug_sink, words, kTimeparVerifyWords * sizeof(double), hipMemcpyDeviceToDevice, s);
 }
@@ -1517,25 +1434,8 @@ static bool use_lanes1(int64_t B, int64_t J, bool grad) {
 
 // wide models (c2_wide.hip; C2_FAST_WIDTH < J <= C2_MAX_WIDTH): the log-likelihood from factor + solve_lower + a reduction, its
 // gradient as the literal op chain of c2_fused.hip over the wide kernels, failed series filled with NaN afterwards
-extern "C" size_t c2_wide_loglik_doubles(int64_t B, int64_t N, int64_t J);
-extern "C" int c2_wide_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                              const double *a, const double *U, const double *V, const double *y, double *ll, int32_t *flag,
-                              double *work, c2_stream_t stream);
-extern "C" int c2_wide_nan_failed(int64_t B, int64_t N, int64_t J, const int32_t *flag, double *bt, double *bc, double *ba,
-                                  double *bU, double *bV, double *by, c2_stream_t stream);
-extern "C" size_t c2_loglik_grad_composite_workspace_bytes(int64_t B, int64_t N, int64_t J);
-extern "C" int c2_loglik_grad_composite(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                        int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
-                                        double *ll, double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
-                                        int32_t *flag, void *work, size_t work_bytes, c2_stream_t stream);
 
 extern "C" {
-
-int c2_internal_loglik_grad_replay(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                   int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
-                                   double *ll, double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
-                                   int32_t *flag, void *work, const unsigned long long *gate, c2_stream_t stream);
-size_t c2_internal_loglik_grad_replay_doubles(int64_t B, int64_t N, int64_t J);
 
 int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
               const double *a, const double *U, const double *V, const double *y, double *ll, int32_t *flag,
@@ -1637,16 +1537,12 @@ static int64_t simd_count() {
   return n;
 }
 static bool use_back(int64_t N, int64_t J) {
-  if (opt::has(opt::k_loglik_back) && opt::ival(opt::k_loglik_back) == 0) return false;
+  if (opt::off(opt::k_loglik_back)) return false;
   return group_size(J) <= 8 && N >= 2;
 }
 
 // core::factor without the S workspace (interface.hpp:37-48) on the fused forward kernel: d and W straight
 // into the caller's arrays (d == a and W == V allowed: every row is read blocks ahead of the row being written).
-extern "C" int c2_internal_factor_timepar(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                          int64_t c_bs, const double *a, const double *U, const double *V, double *d,
-                                          double *W, int32_t *flag, double *work, unsigned long long *guard,
-                                          c2_stream_t stream);
 // allow_timepar: 0 row by row only; 1 the dispatch's choice; 2 what the time-parallel gradient builds on: from 2048 rows the
 // scanned chunk elements at widths 4 / 2 (start states exact to rounding) and the Newton iterations at the other widths
 // (1 .. 8), the row-by-row kernel below that
@@ -1678,11 +1574,10 @@ int c2_internal_factor_fused_ws(int64_t B, int64_t N, int64_t J, const double *t
   const bool long_enough = N >= 2048 && B * ((N + 63) / 64) <= 32768;
   bool newton = scan_widths ? false
                 : allow_timepar == 2
-                    ? (J >= 1 && J <= 8 && N >= 2 && (forced_iter || long_enough) &&
-                       !(opt::has(opt::k_factor_iter) && opt::ival(opt::k_factor_iter) == 0))
+                    ? (J >= 1 && J <= 8 && N >= 2 && (forced_iter || long_enough) && !opt::off(opt::k_factor_iter))
                     : use_factor_iter(B, N, J);
   if (J == 8 && !opt::has(opt::k_factor_iter) && !(opt::has(opt::k_lanes) && opt::ival(opt::k_lanes) != 0) &&
-      !(opt::has(opt::k_factor_scan8) && opt::ival(opt::k_factor_scan8) == 0) && B <= 65535) {
+      !opt::off(opt::k_factor_scan8) && B <= 65535) {
     // width 8, round 6: the chunk start states come from the scanned chunk elements, not from Newton iterations -- 0.10 ms +
     // 1.7e-5 per 64 rows against 0.30 us per row walked one by one (tools/scan8_grid.py, ms scan / rows: 1 x 384 0.115 /
     // 0.119, 1 x 1024 0.164 / 0.308, 1 x 4096 0.192 / 1.213, 256 x 512 0.140 / 0.158, 512 x 1024 0.252 / 0.309, 512 x 4096
@@ -1744,17 +1639,12 @@ static bool drop_in_long_shape(int64_t B, int64_t N) {
 // factor_rev on a small batch of long series (widths 1 .. 8): the reverse pass of the time-parallel gradient with the
 // adjoints of d, W handed in (c2_timepar_grad.hip, run_factor_rev); the S workspace is not read -- the states are replayed
 // from d, W.  One series of 1e5 rows, J = 8: 73 ms row by row.  C2_TIMEPAR_GRAD=0 disables it.
-extern "C" int c2_internal_factor_rev_replay(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                             int64_t c_bs, const double *U, const double *d, const double *W,
-                                             const double *S, const double *bd, const double *bW, double *bt, double *bc,
-                                             double *ba, double *bU, double *bV, const unsigned long long *gate,
-                                             c2_stream_t stream);
 extern "C" int c2_internal_factor_rev_long(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                            int64_t c_bs, const double *U, const double *d, const double *W, const double *S,
                                            const double *bd, const double *bW, double *bt, double *bc, double *ba, double *bU,
                                            double *bV, c2_stream_t stream) {
   if (J < 1 || J > 8 || !drop_in_long_shape(B, N)) return C2_ERR_UNSUPPORTED;
-  if (opt::has(opt::k_timepar_grad) && opt::ival(opt::k_timepar_grad) == 0) return C2_ERR_UNSUPPORTED;
+  if (opt::off(opt::k_timepar_grad)) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &capturing);
@@ -1784,7 +1674,7 @@ extern "C" int c2_internal_factor_states_timepar(int64_t B, int64_t N, int64_t J
                                                  const double *V, double *d, double *W, double *S, int32_t *flag,
                                                  c2_stream_t stream) {
   if (J < 1 || J > 8 || !drop_in_long_shape(B, N) || d == a || W == V) return C2_ERR_UNSUPPORTED;
-  if (opt::has(opt::k_factor_iter) && opt::ival(opt::k_factor_iter) == 0) return C2_ERR_UNSUPPORTED;
+  if (opt::off(opt::k_factor_iter)) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &capturing);

@@ -16,6 +16,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 #ifndef C2_FWD4_R0
 #define C2_FWD4_R0 8

@@ -43,6 +43,7 @@
 
 #include "../../include/celerite2_amd.h"
 #include "c2_loglik_helpers.hpp"
+#include "c2_internal.hpp"
 
 namespace c2k2 {
 using namespace c2;

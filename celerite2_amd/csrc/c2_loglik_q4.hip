@@ -24,6 +24,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 #ifndef C2_Q4_LN_R
 #define C2_Q4_LN_R 16   // rows per block of the forward kernel's LN instance (8: scalar requests as 64-byte runs; A/B builds)
@@ -905,11 +906,6 @@ inline Layout layout(int64_t B, int64_t N) {
 }  // namespace c2
 
 using namespace c2;
-
-// (c2_loglik.hip) one workgroup per wavefront of `spw` series: words[2 w] = c_max x the longest span between anchors four
-// segments of C rows apart, words[2 w + 1] the same over single segments; +inf for unsorted / NaN times
-extern "C" int c2_internal_anchor_spans(int64_t B, int64_t N, int64_t J, int C, int spw, const double *t, int64_t t_bs,
-                                        const double *c, int64_t c_bs, unsigned long long *words, c2_stream_t stream);
 
 extern "C" {
 

@@ -25,6 +25,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 // The file is compiled once per width: C2T_J = 8 (default), 4, 2 (c2_loglik_t4.hip / c2_loglik_t2.hip include it).  A
 // tile of the width-J streams is always ONE 128-byte line per series: RT = 16 / J rows.

@@ -23,6 +23,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2m {
 using namespace c2;

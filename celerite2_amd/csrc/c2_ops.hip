@@ -18,6 +18,7 @@
 #include "c2_common.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2 {
 
@@ -1366,75 +1367,8 @@ inline int check_dims(int64_t B, int64_t N, int64_t J) {
     default: { constexpr int G = 32; __VA_ARGS__; } break;      \
   }
 
-// wide models (C2_FAST_WIDTH < J <= C2_MAX_WIDTH): a workgroup per series, the state in LDS (c2_wide.hip)
-extern "C" int c2_wide_factor(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                              const double *a, const double *U, const double *V, double *d, double *W, double *S,
-                              int32_t *flag, c2_stream_t stream);
-extern "C" int c2_wide_sweep(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                             int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V, const double *Y,
-                             double *Z, double *F, int zero_z, c2_stream_t stream);
-extern "C" int c2_wide_sweep_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                                 int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                 const double *Y, const double *Z, const double *F, const double *bZ, double *bt, double *bc,
-                                 double *bU, double *bV, double *bY, c2_stream_t stream);
-extern "C" int c2_wide_factor_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                  int64_t c_bs, const double *U, const double *d, const double *W, const double *S,
-                                  const double *bd, const double *bW, double *bt, double *bc, double *ba, double *bU,
-                                  double *bV, int accumulate, c2_stream_t stream);
-extern "C" int c2_wide_general(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1,
-                               int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c, int64_t c_bs,
-                               const double *U, const double *V, const double *Y, double *Z, double *F, int zero_z,
-                               c2_stream_t stream);
+static bool use_mfma() { return !opt::off(opt::k_mfma); }
 
-extern "C" int c2_internal_matmul_chunked(int lower, int64_t B, int64_t N, int64_t J, int64_t nrhs, int64_t Lc,
-                                          const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                          const double *U, const double *V, const double *Y, double *Z, double *F,
-                                          int zero_z, c2_stream_t stream);
-
-extern "C" int c2_internal_sweep1(int lower, int solve, int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
-                                  const double *c, int64_t c_bs, const double *U, const double *V, const double *Y,
-                                  double *Z, double *F, int zero_z, c2_stream_t stream);
-
-extern "C" int c2_internal_sweepT(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                                  int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                  const double *Y, double *Z, double *F, int zero_z, c2_stream_t stream);
-extern "C" int c2_internal_sweepT_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                                      int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                      const double *Y, const double *Z, const double *F, const double *bZ, double *bt,
-                                      double *bc, double *bU, double *bV, double *bY, c2_stream_t stream);
-extern "C" int c2_internal_sweep1_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, const double *t,
-                                      int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                      const double *Y, const double *Z, const double *F, const double *bZ, double *bt,
-                                      double *bc, double *bU, double *bV, double *bY, c2_stream_t stream);
-
-extern "C" int c2_internal_sweepK(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                                  int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                  const double *Y, double *Z, double *F, int zero_z, c2_stream_t stream);
-
-extern "C" int c2_internal_matmul_lower_mfma(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
-                                             const double *c, int64_t c_bs, const double *U, const double *V,
-                                             const double *d, const double *Y, double *Z, int zero_z,
-                                             c2_stream_t stream);
-static bool use_mfma() {
-  return !(opt::has(opt::k_mfma) && opt::ival(opt::k_mfma) == 0);
-}
-
-extern "C" int c2_internal_use_timepar_solve(int64_t B, int64_t N, int64_t J);
-extern "C" size_t c2_internal_timepar_solve_doubles(int64_t B, int64_t N, int64_t J);
-extern "C" int c2_internal_solve_timepar(int lower, int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
-                                         const double *c, int64_t c_bs, const double *U, const double *W,
-                                         const double *Y, double *Z, double *scratch, c2_stream_t stream);
-extern "C" int c2_internal_tpg_short_chunks(int64_t B, int64_t N);
-#define C2_DECL_SC(R_)                                                                                               \
-  extern "C" size_t c2_internal_solve_chunks_doubles##R_(int64_t B, int64_t N, int64_t J);                          \
-  extern "C" int c2_internal_solve_chunks##R_(int lower, int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, \
-                                              const double *c, int64_t c_bs, const double *U, const double *W,      \
-                                              const double *Y, double *Z, double *scratch, c2_stream_t stream,      \
-                                              int64_t nrhs, double *F);
-C2_DECL_SC(64)
-C2_DECL_SC(32)
-C2_DECL_SC(16)
-#undef C2_DECL_SC
 // shortest series the long-series forms of the solves with F / several right-hand sides and of the reverse sweeps take
 // (C2_LONG_MIN_ROWS overrides; measured below)
 static int64_t long_min_rows() {
@@ -1456,17 +1390,6 @@ static bool matmul_chunked_shape(int64_t B, int64_t N, int64_t J, int64_t nrhs) 
 // 0.63 -> 0.15; 8 right-hand sides: 1 x 1024 0.32 -> 0.27, 1 x 8192 2.56 -> 0.45 (1 x 512: 0.16 -> 0.24, not taken);
 // 2048 x 1024 (32768 chunks) + F 0.20 -> 0.25, not taken; 64 x 4096 with 8 right-hand sides 1.29 -> 0.40; 512 x 4096 with 8:
 // 1.45 -> 1.9, not taken -- the rule below is that cost model
-extern "C" int c2_internal_sweep_cols(int lower, int solve, int64_t B, int64_t N, int64_t Jw, int64_t nrhs, const double *t,
-                                      int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                      const double *Y, double *Z, int64_t *B8, c2_stream_t stream);
-extern "C" int c2_internal_sweep_cols_rev(int lower, int solve, int64_t B, int64_t N, int64_t Jw, int64_t nrhs, const double *t,
-                                          int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                          const double *Y, const double *Z, const double *F, const double *bZ, double *bt,
-                                          double *bc, double *bU, double *bV, double *bY, int64_t *B8, c2_stream_t stream);
-extern "C" size_t c2_internal_solve_cols_doubles(int64_t B, int64_t N, int64_t J, int64_t nrhs);
-extern "C" int c2_internal_solve_cols(int lower, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
-                                      const double *c, int64_t c_bs, const double *U, const double *W, const double *Y,
-                                      double *Z, double *scratch, c2_stream_t stream);
 static bool solve_chunks_shape(int64_t B, int64_t N, int64_t J, int64_t nrhs) {
   if (J > 8 || nrhs > 64 || N < long_min_rows()) return false;
   const int64_t k64 = B * ((N + 63) / 64);   // chunks of one launch: the right-hand sides run one after the other
@@ -1518,7 +1441,7 @@ static bool solve_cols_shape(int64_t B, int64_t N, int64_t J, int64_t nrhs) {
   return cols_ms < rows_ms;
 }
 static bool solve_chunks_enabled() {
-  return !(opt::has(opt::k_timepar) && opt::ival(opt::k_timepar) == 0);   // the switch of the time-parallel solves: 0 keeps them row by row
+  return !opt::off(opt::k_timepar);   // the switch of the time-parallel solves: 0 keeps them row by row
 }
 template <bool LOWER, bool SOLVE>
 static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs, const double *c,
@@ -1642,26 +1565,11 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
   return check_launch();
 }
 
-extern "C" int c2_internal_generalK(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1,
-                                    int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c, int64_t c_bs,
-                                    const double *U, const double *V, const double *Y, double *Z, double *F, int zero_z,
-                                    c2_stream_t stream);
-extern "C" int c2_internal_general_tile(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs,
-                                        const double *t1, int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c,
-                                        int64_t c_bs, const double *U, const double *V, const double *Y, double *Z,
-                                        double *F, double *scratch, c2_stream_t stream);
-extern "C" size_t c2_internal_general_tile_doubles(int64_t B, int64_t M, int64_t J, int64_t nrhs);
-extern "C" int64_t c2_internal_general_chunks_plan(int64_t B, int64_t M, int64_t nrhs);
-extern "C" size_t c2_internal_general_chunks_doubles(int64_t B, int64_t M, int64_t J, int64_t nrhs, int64_t Lc);
-extern "C" int c2_internal_general_chunks(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, int64_t Lc,
-                                          const double *t1, int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c,
-                                          int64_t c_bs, const double *U, const double *V, const double *Y, double *Z,
-                                          double *scratch, c2_stream_t stream);
 static bool use_general_tile() {
-  return !(opt::has(opt::k_general_tile) && opt::ival(opt::k_general_tile) == 0);   // 0: the kernels below (A/B runs, tests of every path)
+  return !opt::off(opt::k_general_tile);   // 0: the kernels below (A/B runs, tests of every path)
 }
 static bool use_generalK() {
-  return !(opt::has(opt::k_generalk) && opt::ival(opt::k_generalk) == 0);   // 0: the first-round kernels (A/B runs, tests of both paths)
+  return !opt::off(opt::k_generalk);   // 0: the first-round kernels (A/B runs, tests of both paths)
 }
 template <bool LOWER>
 static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1, int64_t t1_bs,
@@ -1758,15 +1666,6 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
   }
   return rc;
 }
-extern "C" int c2_internal_sweepK_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t,
-                                      int64_t t_bs, const double *c, int64_t c_bs, const double *U, const double *V,
-                                      const double *Y, const double *Z, const double *F, const double *bZ, double *bt,
-                                      double *bc, double *bU, double *bV, double *bY, c2_stream_t stream);
-extern "C" int c2_internal_sweep_rev_long(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs,
-                                          const double *t, int64_t t_bs, const double *c, int64_t c_bs, const double *U,
-                                          const double *V, const double *Y, const double *Z, const double *F,
-                                          const double *bZ, double *bt, double *bc, double *bU, double *bV, double *bY,
-                                          c2_stream_t stream);
 template <bool LOWER, bool SOLVE>
 static int launch_sweep_rev(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
                             const double *c, int64_t c_bs, const double *U, const double *V, const double *Y,
@@ -1824,7 +1723,7 @@ static int launch_sweep_rev(int64_t B, int64_t N, int64_t J, int64_t nrhs, const
     }
   }
   {  // several right-hand sides: lanes over them (c2_sweep_rev.hip) where the shape fits; C2_SWEEPK_REV=0 for A/B runs
-    if (!(opt::has(opt::k_sweepk_rev) && opt::ival(opt::k_sweepk_rev) == 0)) {
+    if (!opt::off(opt::k_sweepk_rev)) {
       const int e = c2_internal_sweepK_rev(LOWER ? 1 : 0, SOLVE ? 1 : 0, B, N, J, nrhs, t, t_bs, c, c_bs, U, V, Y, Z, F, bZ,
                                            bt, bc, bU, bV, bY, stream);
       if (e != C2_ERR_UNSUPPORTED) return e;
@@ -1869,14 +1768,6 @@ int c2_device_count(void) {
   return n;
 }
 
-int c2_internal_factor_fused(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                             int64_t c_bs, const double *a, const double *U, const double *V, double *d, double *W,
-                             int32_t *flag, int allow_timepar, c2_stream_t stream);
-
-extern "C" int c2_internal_factor_states_timepar(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
-                                                 const double *c, int64_t c_bs, const double *a, const double *U,
-                                                 const double *V, double *d, double *W, double *S, int32_t *flag,
-                                                 c2_stream_t stream);
 int c2_factor(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
               const double *a, const double *U, const double *V, double *d, double *W, double *S, int32_t *flag,
               c2_stream_t stream) {
@@ -1896,7 +1787,7 @@ int c2_factor(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
     if (int e = c2_internal_factor_fused(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, 0, stream)) return e;
     C2_DISPATCH_G(group_size(J), {
       if constexpr (G == 8) {
-        if (((uintptr_t)W) % 16 == 0 && !(opt::has(opt::k_s_replay_lines) && opt::ival(opt::k_s_replay_lines) == 0))
+        if (((uintptr_t)W) % 16 == 0 && !opt::off(opt::k_s_replay_lines))
           hipLaunchKernelGGL((k_s_replay<G, true>), grid_for(B, G), dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs,
                              (const double *)d, (const double *)W, (const int32_t *)flag, S);
         else
@@ -1946,11 +1837,6 @@ int c2_general_matmul_upper(int64_t B, int64_t N, int64_t M, int64_t J, int64_t 
 }
 
 // Internal: factor_rev with optional accumulation into bt/bc/bU (used by c2_loglik_grad).
-int c2_internal_factor_rev_replay(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                  int64_t c_bs, const double *U, const double *d, const double *W, const double *S,
-                                  const double *bd, const double *bW, double *bt, double *bc, double *ba, double *bU,
-                                  double *bV, const unsigned long long *gate, c2_stream_t stream);
-
 int c2_factor_rev_acc(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                       const double *U, const double *d, const double *W, const double *S, const double *bd,
                       const double *bW, double *bt, double *bc, double *ba, double *bU, double *bV, int accumulate,
@@ -1965,10 +1851,6 @@ int c2_factor_rev_acc(int64_t B, int64_t N, int64_t J, const double *t, int64_t 
   return check_launch();
 }
 
-extern "C" int c2_internal_factor_rev_long(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                           int64_t c_bs, const double *U, const double *d, const double *W, const double *S,
-                                           const double *bd, const double *bW, double *bt, double *bc, double *ba, double *bU,
-                                           double *bV, c2_stream_t stream);
 int c2_factor_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                   const double *a, const double *U, const double *V, const double *d, const double *W,
                   const double *S, const double *bd, const double *bW, double *bt, double *bc, double *ba, double *bU,
@@ -2057,7 +1939,7 @@ int c2_kernel_values(int64_t B, int64_t N, int64_t M, int64_t Jr, int64_t Jc, co
   // tiles of 32 x 64 entries (one sincos per tile row and column instead of one per entry) when there is enough of a grid
   // to amortise them and the row phases fit LDS; C2_KERNEL_VALUES_TILE=0: the thread-per-entry kernel
   if (N >= 8 && M >= 8 && B <= 65535 && (N + kKvRows - 1) / kKvRows <= 65535 && lds <= 48 * 1024 &&
-      !(opt::has(opt::k_kernel_values_tile) && opt::ival(opt::k_kernel_values_tile) == 0)) {
+      !opt::off(opt::k_kernel_values_tile)) {
     const dim3 grid((unsigned)((M + kKvCols - 1) / kKvCols), (unsigned)((N + kKvRows - 1) / kKvRows), (unsigned)B);
     hipLaunchKernelGGL(k_kernel_values_tile, grid, dim3(256), lds, (hipStream_t)stream, N, M, (int)Jr, (int)Jc, ar, cr, ac, bc, cc,
                        dc, coef_batched, t1, t1_bs, t2, t2_bs, K);

@@ -21,6 +21,7 @@
 #include "c2_common.hpp"
 #include "c2_rscatter.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2 {
 

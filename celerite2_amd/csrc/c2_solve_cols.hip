@@ -24,6 +24,7 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_common.hpp"
 #include "c2_loglik_helpers.hpp"
+#include "c2_internal.hpp"
 
 namespace c2cols {
 using namespace c2;

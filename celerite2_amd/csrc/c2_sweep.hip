@@ -14,6 +14,7 @@
 #include "c2_dispatch.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2 {
 
@@ -773,8 +774,7 @@ extern "C" int c2_internal_sweep1(int lower, int solve, int64_t B, int64_t N, in
   hipStream_t s = (hipStream_t)stream;
   const int G_ = group_size(J);
   const dim3 grid((unsigned)((B * G_ + kWave - 1) / kWave));
-  const bool lines_ok = N >= 3 && (((uintptr_t)U | (uintptr_t)V) % 16) == 0 &&
-                        !(opt::has(opt::k_sweep1_lines) && opt::ival(opt::k_sweep1_lines) == 0);
+  const bool lines_ok = N >= 3 && (((uintptr_t)U | (uintptr_t)V) % 16) == 0 && !opt::off(opt::k_sweep1_lines);
 #define C2_SW(G, LO, SO)                                                                                           \
   do {                                                                                                             \
     if (J == G && G == 8 && lines_ok) {                                                                            \
@@ -818,7 +818,7 @@ extern "C" int c2_internal_sweep1_rev(int lower, int solve, int64_t B, int64_t N
   const int G_ = group_size(J);
   const dim3 grid((unsigned)((B * G_ + kWave - 1) / kWave));
   if (J == 8 && N >= 3 && (((uintptr_t)U | (uintptr_t)V | (uintptr_t)F | (uintptr_t)bU | (uintptr_t)bV) % 16) == 0 &&
-      !(opt::has(opt::k_sweep1_rev_lines) && opt::ival(opt::k_sweep1_rev_lines) == 0)) {
+      !opt::off(opt::k_sweep1_rev_lines)) {
     // rows by lines; the lower sweeps walk down from row N - 1: which rows open a line depends on the parity of N
 #define C2_SWL(LO, SO, LN_)                                                                                          \
   hipLaunchKernelGGL((k_sweep1_rev<8, 8, LO, SO, false, LN_>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, \
@@ -874,8 +874,7 @@ extern "C" int c2_internal_sweepK(int lower, int solve, int64_t B, int64_t N, in
   if (F && !(nrhs <= KL && J == JM && ((uintptr_t)F) % 16 == 0)) return C2_ERR_UNSUPPORTED;
   // nrhs = J = 8: by lines on the whole wavefronts of the batch (every pointer 16-byte pieces are moved through must allow
   // that), the row-by-row kernel below on the B % 8 series left over
-  if (J == 8 && nrhs == 8 && B >= 8 && N >= 8 &&
-      !(opt::has(opt::k_sweepk_lines) && opt::ival(opt::k_sweepk_lines) == 0) &&
+  if (J == 8 && nrhs == 8 && B >= 8 && N >= 8 && !opt::off(opt::k_sweepk_lines) &&
       (((uintptr_t)U | (uintptr_t)V | (uintptr_t)Y | (uintptr_t)Z | (uintptr_t)F) % 16) == 0) {
     const int64_t B8 = B / 8 * 8;
     const dim3 g8((unsigned)(B8 / 8));

@@ -20,6 +20,7 @@
 #include "c2_dispatch.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "c2_rscatter.hpp"
+#include "c2_internal.hpp"
 
 namespace c2sc {
 using namespace c2;

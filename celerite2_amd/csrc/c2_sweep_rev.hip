@@ -22,6 +22,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "c2_rscatter.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2r {
 using namespace c2;

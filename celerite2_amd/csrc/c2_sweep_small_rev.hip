@@ -8,6 +8,7 @@
 #include "c2_dispatch.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2 {
 
@@ -227,7 +228,7 @@ extern "C" int c2_internal_sweepT_rev(int lower, int solve, int64_t B, int64_t N
                                       double *bc, double *bU, double *bV, double *bY, c2_stream_t stream) {
   if (nrhs < 2 || nrhs > 7 || J > 32 || N < 2) return C2_ERR_UNSUPPORTED;
   if (nrhs > 4 && group_size(J) != 8) return C2_ERR_UNSUPPORTED;
-  if (opt::has(opt::k_sweept_rev) && opt::ival(opt::k_sweept_rev) == 0) return C2_ERR_UNSUPPORTED;
+  if (opt::off(opt::k_sweept_rev)) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int kt = (int)nrhs;
 #define C2_ARGS kt, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, F, bZ, bt, bc, bU, bV, bY, s

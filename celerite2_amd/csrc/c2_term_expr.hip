@@ -23,8 +23,7 @@
 
 #include "../../include/celerite2_amd.h"
 #include "c2_term_leaf.hpp"
-
-extern "C" void c2_internal_set_error(const char *msg);
+#include "c2_internal.hpp"
 
 namespace {
 

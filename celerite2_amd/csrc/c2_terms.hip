@@ -25,8 +25,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
-
-extern "C" void c2_internal_set_error(const char *msg);
+#include "c2_internal.hpp"
 
 namespace c2terms {
 
@@ -204,69 +203,10 @@ using namespace c2terms;
 // memory.  Widths 8, 4, 2.  C2_TERMS_FUSED=1 forces them, =0 disables them; otherwise batches that fill the chip.
 // At width 8 the two-lane pair of c2_loglik_k2.hip has the same form (k_k2_tt_*) and takes the batches in between
 // (C2_TERMS_TWO_LANES, profiles/r06_terms_lanes.md).
-extern "C" {
-#define C2_DECL_TT(J_)                                                                                                 \
-  int c2_internal_loglik_tt##J_(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar, const double *cr, \
-                                const double *ac, const double *bc, const double *cc, const double *dc,               \
-                                const double *x, int64_t x_bs, const double *diag, const double *y, double *ll,       \
-                                int32_t *flag, c2_stream_t stream);                                                   \
-  int c2_internal_loglik_tt_grad##J_(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar,            \
-                                     const double *cr, const double *ac, const double *bc, const double *cc,          \
-                                     const double *dc, const double *x, int64_t x_bs, const double *diag,             \
-                                     const double *y, double *ll, double *bar, double *bcr, double *bac, double *bbc, \
-                                     double *bcc, double *bdc, double *bx, double *bdiag, double *by, int32_t *flag,  \
-                                     double *rec, unsigned long long *guard, c2_stream_t stream);                     \
-  size_t c2_internal_loglik_t_record_doubles##J_(int64_t B, int64_t N);
-C2_DECL_TT(8)
-C2_DECL_TT(4)
-C2_DECL_TT(2)
-#undef C2_DECL_TT
 // the same with two lanes per series (c2_loglik_k2.hip, J == 8): batches that give the one-lane mapping half a chip
-int c2_internal_loglik_k2_tt(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar, const double *cr,
-                             const double *ac, const double *bc, const double *cc, const double *dc, const double *x,
-                             int64_t x_bs, const double *diag, const double *y, double *ll, int32_t *flag, c2_stream_t stream);
-int c2_internal_loglik_k2_tt_grad(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar, const double *cr,
-                                  const double *ac, const double *bc, const double *cc, const double *dc, const double *x,
-                                  int64_t x_bs, const double *diag, const double *y, double *ll, double *bar, double *bcr,
-                                  double *bac, double *bbc, double *bcc, double *bdc, double *bx, double *bdiag, double *by,
-                                  int32_t *flag, double *rec, unsigned long long *guard, c2_stream_t stream);
-size_t c2_internal_loglik_k2_record_doubles(int64_t B, int64_t N);
 // ... and with a group of J = 8, 4 or 2 lanes per series (c2_loglik.hip: k_loglik_fwd / k_loglik_rev<..., TT>): at most one
 // wavefront per SIMD
-size_t c2_internal_loglik_g8_tt_doubles(int64_t B, int64_t N, int64_t J);
-int c2_internal_loglik_g8_tt_ok(int64_t B, int64_t N, int64_t J);
 // ... and with four (c2_loglik_q4.hip: k_q4_fwd / k_q4_rev<..., TT>): the batches between the eight-lane and the two-lane range
-size_t c2_internal_loglik_q4_record_doubles(int64_t B, int64_t N);
-int c2_internal_loglik_q4_tt(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar, const double *ac, const double *bc,
-                             const double *dc, const double *c, const double *x, int64_t x_bs, const double *diag, const double *y,
-                             double *ll, int32_t *flag, unsigned long long *words, unsigned long long *guard, c2_stream_t stream);
-size_t c2_internal_loglik_q4_span_words(int64_t B, int64_t N);
-int c2_internal_loglik_q4_tt_grad(int64_t B, int64_t N, int64_t Jc, int coef_batched, const double *ar, const double *ac,
-                                  const double *bc, const double *dc, const double *c, const double *x, int64_t x_bs,
-                                  const double *diag, const double *y, double *ll, double *bar, double *bcr, double *bac,
-                                  double *bbc, double *bcc, double *bdc, double *bx, double *bdiag, double *by,
-                                  int32_t *flag, double *rec, unsigned long long *guard, c2_stream_t stream);
-int c2_internal_loglik_g8_tt(int64_t B, int64_t N, int64_t J, int64_t Jc, int coef_batched, const double *ar, const double *ac,
-                             const double *bc, const double *dc, const double *c, const double *x, int64_t x_bs,
-                             const double *diag, const double *y, double *ll, int32_t *flag, unsigned long long *guard,
-                             c2_stream_t stream);
-int c2_internal_loglik_g8_gated(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
-                                const double *a, const double *U, const double *V, const double *y, double *ll, int32_t *flag,
-                                const unsigned long long *gate, c2_stream_t stream);
-int c2_internal_loglik_g8_tt_grad(int64_t B, int64_t N, int64_t J, int64_t Jc, int coef_batched, const double *ar, const double *ac,
-                                  const double *bc, const double *dc, const double *c, const double *x, int64_t x_bs,
-                                  const double *diag, const double *y, double *ll, double *bar, double *bcr, double *bac,
-                                  double *bbc, double *bcc, double *bdc, double *bx, double *bdiag, double *by,
-                                  int32_t *flag, double *work, unsigned long long *guard, c2_stream_t stream);
-int c2_internal_matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ar, const double *ac,
-                         const double *bc, const double *dc, int coef_batched, const double *x, int64_t x_bs,
-                         const double *diag, double *a, double *U, double *V, const unsigned long long *gate,
-                         c2_stream_t stream);
-int c2_internal_loglik_grad_replay(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                   int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
-                                   double *ll, double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
-                                   int32_t *flag, void *work, const unsigned long long *gate, c2_stream_t stream);
-}
 static bool fused_width(int64_t J) { return J == 8 || J == 4 || J == 2; }
 // guard words in front of the fused kernels' records: the head + one per wavefront of 64 series, rounded to 16 bytes
 static size_t fused_gate_words(int64_t B) { return (size_t)((c2::kGateHeadWords + (B + 63) / 64 + 1) & ~(int64_t)1); }

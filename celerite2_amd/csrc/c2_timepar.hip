@@ -28,7 +28,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
-
+#include "c2_internal.hpp"
 
 namespace c2tp {
 using namespace c2;
@@ -521,7 +521,7 @@ template <int J>
 struct ElemIO {
   static constexpr int N_ = J * J + 2 * nsym(J) + 2 * J + 3;   // A, G, Q, g, h, q0, prod, ex
   static constexpr int NM = J * J + 2 * nsym(J) + 1;           // A, G, Q, prod (NaN: failed)
-  static constexpr int REC = (N_ + 3) & ~3;                    // a contiguous record per chunk (k_tp_onepass<J, 2>)
+  static constexpr int REC = (N_ + 3) & ~3;                    // a contiguous record per chunk (width 8: k_e8_chunks), in the order of N_
 };
 template <int J>
 __device__ __forceinline__ void elem_store_matrices(const Elem<J> &e, double *__restrict__ base, int64_t W, int64_t at) {
@@ -553,7 +553,7 @@ __device__ __forceinline__ void elem_load_matrices(Elem<J> &e, const double *__r
 
 // rows of the chunks from the zero state -> elements -> the tree.  ONE wavefront per 64 chunks of a series; MODE 0: the
 // series has at most 64 chunks and the wavefront finishes it (ll, flag, gate word); MODE 1: its element goes to `elems`
-// ([entry][series * wavefronts + wavefront]) for k_tp_join; MODE 2: no tree, every chunk's element to `elems` as a record.
+// ([entry][series * wavefronts + wavefront]) for k_tp_join.
 template <int J, int MODE>
 __global__ __launch_bounds__(kThreads) void k_tp_onepass(int64_t B, int64_t N, int64_t K, int R, const double *__restrict__ t,
                                                          int64_t t_bs, const double *__restrict__ c, int64_t c_bs,
@@ -684,34 +684,10 @@ __global__ __launch_bounds__(kThreads) void k_tp_onepass(int64_t B, int64_t N, i
     e.ex = eacc + ex;
   }
   if (!inr) { elem_identity<J>(e); failed = 0.0; }   // (lanes beyond the series ran its last chunk for the loads' sake)
-  if constexpr (MODE != 2) {
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double f2 = __shfl_xor(failed, o, 64);
-      failed = failed == 0.0 ? f2 : (f2 == 0.0 ? failed : fmin(failed, f2));
-    }
-  }
-  if constexpr (MODE == 2) {   // every chunk's element as a record (width 8: combined by k_e8_tree)
-    if (inr) {
-      double *rec = elems + (size_t)(b * K + k) * ElemIO<J>::REC;
-      int q = 0;
-#pragma unroll
-      for (int i = 0; i < J; ++i)
-#pragma unroll
-        for (int j = 0; j < J; ++j) rec[q++] = e.A[i][j];
-#pragma unroll
-      for (int i = 0; i < NS; ++i) rec[q++] = e.G[i];
-#pragma unroll
-      for (int i = 0; i < NS; ++i) rec[q++] = e.Q[i];
-#pragma unroll
-      for (int i = 0; i < J; ++i) rec[q++] = e.g[i];
-#pragma unroll
-      for (int i = 0; i < J; ++i) rec[q++] = e.h[i];
-      rec[q++] = e.q0;
-      rec[q++] = failed != 0.0 ? __longlong_as_double(0x7ff8000000000000ll) : e.prod;
-      rec[q++] = (double)e.ex;
-    }
-    return;
+  for (int o = 32; o >= 1; o >>= 1) {
+    const double f2 = __shfl_xor(failed, o, 64);
+    failed = failed == 0.0 ? f2 : (f2 == 0.0 ? failed : fmin(failed, f2));
   }
   elem_tree<J>(e, lane, (int)((K - ch.k0) < kThreads ? (K - ch.k0) : kThreads));
   if constexpr (MODE == 0) {
@@ -795,7 +771,7 @@ __global__ __launch_bounds__(kThreads) void k_tp_join(int64_t B, int64_t N, int6
 }
 
 // =============================================================================================================
-// Width 8: the elements of the chunks (k_tp_onepass<8, 2>: a record per chunk) combined by WORKGROUPS.  An element of width 8
+// Width 8: the elements of the chunks (k_e8_chunks: a record per chunk) combined by WORKGROUPS.  An element of width 8
 // (155 doubles) does not fit a lane next to the temporaries of a combination, so here a WAVEFRONT combines one pair at a time
 // with lane (i, j) <-> entry (i, j) of the 8 x 8 matrices, everything through its private LDS block: the Cholesky factor of G1,
 // the symmetric positive definite Ks = I - L^T Q2 L inverted in place by Gauss-Jordan (its pivots are the Cholesky pivots
@@ -932,12 +908,13 @@ __device__ __forceinline__ void e8_combine(const double *__restrict__ r1, const 
     ro[kE8ex] = (double)(ex1 + ex2 + ex);
   }
 }
-// ---- width 8: the chunk pass with the element SPREAD OVER THE EIGHT LANES OF A GROUP (round 6).  k_tp_onepass<8, 2> keeps
-// an element (155 doubles) in ONE lane: ~550 instructions per row with eight exponentials, 3.6 us per row.  Here lane j of a
+// ---- width 8: the chunk pass with the element SPREAD OVER THE EIGHT LANES OF A GROUP (round 6).  An element (155 doubles) kept
+// in ONE lane, as k_tp_onepass does at widths 4 and 2, cost ~550 instructions per row with eight exponentials, 3.6 us per row
+// (58.7 -> 11.4 us for the pass, profiles/r06_scan8.md; that instance was removed).  Here lane j of a
 // group owns COLUMN j of A, G and Q in XOR order (slot k = row j ^ k: c2_loglik_helpers.hpp), so that u T, u A are eight
 // multiply-adds on the lane's own registers, d one butterfly sum, and the rank-one updates need the gathered w, r = u A and
 // decay vectors (three DPP gathers); every lane computes ONE exponential.  A wavefront walks eight chunks; the records it
-// writes are those of k_tp_onepass<8, 2> (ElemIO<8>), VEC = false: matrices only (g, h, q0 zero -- `factor`).
+// writes are ElemIO<8> records (kE8A .. kE8ex; prod = NaN: failed), VEC = false: matrices only (g, h, q0 zero -- `factor`).
 template <bool VEC>
 __global__ __launch_bounds__(64) void k_e8_chunks(int64_t B, int64_t N, int64_t K, int R, const double *__restrict__ t,
                                                   int64_t t_bs, const double *__restrict__ c, int64_t c_bs,
@@ -1095,8 +1072,6 @@ __host__ inline int chunk_rows8(int64_t B, int64_t N) {
     if (B * ((N + R - 1) / R) <= 65536) return R;
   return 64;
 }
-// chunk pass at width 8 with the element spread over the lanes of a group (k_e8_chunks) or in one lane (k_tp_onepass<8, 2>)
-static bool e8_group_chunks() { return !(opt::has(opt::k_e8_group_chunks) && opt::ival(opt::k_e8_group_chunks) == 0); }
 struct E8Plan {
   int R, span;
   int64_t K, blocks;
@@ -1122,13 +1097,8 @@ inline int run8(int64_t B, int64_t N, const double *t, int64_t t_bs, const doubl
   const E8Plan p = e8_plan(B, N);
   constexpr size_t REC = ElemIO<8>::REC;
   if (hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return C2_ERR_HIP;
-  const dim3 gc((unsigned)((p.K + kThreads - 1) / kThreads), (unsigned)B);
-  if (e8_group_chunks())
-    hipLaunchKernelGGL((k_e8_chunks<true>), dim3((unsigned)((B * p.K + 7) / 8)), dim3(64), 0, s, B, N, p.K, p.R, t, t_bs, c, c_bs, a, U,
-                       V, y, work + p.rec0);
-  else
-    hipLaunchKernelGGL((k_tp_onepass<8, 2>), gc, dim3(kThreads), 0, s, B, N, p.K, p.R, t, t_bs, c, c_bs, a, U, V, y, work + p.rec0, ll,
-                       flag, guard);
+  hipLaunchKernelGGL((k_e8_chunks<true>), dim3((unsigned)((B * p.K + 7) / 8)), dim3(64), 0, s, B, N, p.K, p.R, t, t_bs, c, c_bs, a, U,
+                     V, y, work + p.rec0);
   const double *in = work + p.rec0;
   int64_t Kin = p.K;
   double *pong[2] = {work + p.rec1, work + p.rec1 + (size_t)B * (size_t)p.blocks * REC};
@@ -1302,13 +1272,8 @@ inline int run8_states(int64_t B, int64_t N, int R, const double *t, int64_t t_b
                        hipStream_t s) {
   const E8StatesPlan p = e8_states_plan(B, N, R);
   if (p.l[p.n - 1].blocks != 1 || B > 65535) return C2_ERR_UNSUPPORTED;
-  const dim3 gc((unsigned)((p.K + kThreads - 1) / kThreads), (unsigned)B);
-  if (e8_group_chunks())
-    hipLaunchKernelGGL((k_e8_chunks<false>), dim3((unsigned)((B * p.K + 7) / 8)), dim3(64), 0, s, B, N, p.K, R, t, t_bs, c, c_bs, a,
-                       U, V, (const double *)nullptr, work + p.rec0);
-  else   // (the records' vectors are computed from `a` in place of y: finite junk nobody reads)
-    hipLaunchKernelGGL((k_tp_onepass<8, 2>), gc, dim3(kThreads), 0, s, B, N, p.K, R, t, t_bs, c, c_bs, a, U, V, a, work + p.rec0,
-                       (double *)nullptr, (int32_t *)nullptr, guard);
+  hipLaunchKernelGGL((k_e8_chunks<false>), dim3((unsigned)((B * p.K + 7) / 8)), dim3(64), 0, s, B, N, p.K, R, t, t_bs, c, c_bs, a, U,
+                     V, (const double *)nullptr, work + p.rec0);
   for (int i = 0; i < p.n; ++i) {
     const E8Launch &q = p.l[i];
     hipLaunchKernelGGL(k_e8_tree, dim3((unsigned)q.blocks, (unsigned)B), dim3(kE8Waves * 64), 0, s, N, q.Kin, q.span,

@@ -37,13 +37,7 @@
 
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
-
-extern "C" int c2_internal_factor_fused_ws(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
-                                           int64_t c_bs, const double *a, const double *U, const double *V, double *d,
-                                           double *W, int32_t *flag, int allow_timepar, double *scratch,
-                                           c2_stream_t stream);
-extern "C" size_t c2_internal_factor_scratch_doubles(int64_t B, int64_t N, int64_t J);
-extern "C" double *c2_internal_get_debug_sink();   // diagnostics (c2_loglik.hip)
+#include "c2_internal.hpp"
 
 // 1: the dispatch's choice of factor kernels (widths 4 / 2 below 32768 rows: the composed maps of c2_timepar.hip, verified
 // to 5e-11 only -- which the gradient inherits: 1.5e-10 / 6.5e-11 of the largest gradient entry on two WELL-conditioned
@@ -1837,10 +1831,6 @@ extern "C" int C2TG_NAME(c2_internal_loglik_grad_timepar)(int64_t B, int64_t N, 
 // factor (d, W) by Newton iterations on the chunk start states (widths 1 .. 8).  work: c2_internal_factor_iter_doubles;
 // its first kNewtonHdr words are the iterations' words (updates, then conditioning) -- the caller launches its row-by-row
 // kernel behind `*last_word`.
-extern "C" size_t c2_internal_e8_states_doubles(int64_t B, int64_t N, int64_t R);
-extern "C" int c2_internal_e8_states(int64_t B, int64_t N, int64_t R, const double *t, int64_t t_bs, const double *c,
-                                     int64_t c_bs, const double *a, const double *U, const double *V, double *X, double *work,
-                                     unsigned long long *guard, c2_stream_t stream);
 extern "C" size_t C2TG_NAME(c2_internal_factor_iter_doubles)(int64_t B, int64_t N, int64_t J) {
   if (J < 1 || J > 8) return 0;
   const size_t K = (size_t)((N + kRows - 1) / kRows);

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "../../include/celerite2_amd.h"
+#include "c2_internal.hpp"
 
 namespace c2w {
 

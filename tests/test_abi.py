@@ -136,3 +136,87 @@ def test_dispatch_options_table(built):
             assert "getenv(" not in open(src).read(), src
     assert subprocess.call([sys.executable, os.path.join(ROOT, "tools", "gen_dispatch_doc.py"), "--check"]) == 0, \
         "INTEGRATION.md section 5 is stale: run python tools/gen_dispatch_doc.py"
+
+
+def test_internal_interface_is_declared_once():
+    """The functions one .hip of csrc/ defines and another calls (c2_internal_*, c2_wide_*, c2_loglik_grad_composite*; C
+    linkage, so a stale private prototype would still link) are declared in csrc/c2_internal.hpp and nowhere else, each
+    name the header declares is defined in exactly one .hip, and that .hip sees the header -- directly or through the
+    .hip it #includes -- so the compiler compares definition and declaration."""
+    import glob
+
+    csrc = os.path.join(ROOT, "celerite2_amd", "csrc")
+    call = re.compile(r"\b(C2TG?_NAME\(\s*\w+\s*\)|(?:c2_internal_|c2_wide_|c2_loglik_grad_composite)\w*(?:##\w+)?)\s*\(")
+    typed = re.compile(r"\b(?:int|int64_t|size_t|void|double|bool|char|long)[\s\\*&]*$")
+
+    def code(path):   # the text without comments and, except on #include lines, string contents
+        s = re.sub(r"//[^\n]*|/\*.*?\*/", " ", open(path).read(), flags=re.S)
+        return re.sub(r'^(?!#include).*$', lambda m: re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', m.group(0)), s, flags=re.M)
+
+    def signatures(s):   # (name, ';' or '{') of every prototype / definition: a return type in front, what follows the ')'
+        for m in call.finditer(s):
+            if not typed.search(s[:m.start()]):
+                continue
+            depth, j = 0, m.end() - 1
+            while True:
+                depth += {"(": 1, ")": -1}.get(s[j], 0)
+                j += 1
+                if depth == 0:
+                    break
+            tail = s[j:].lstrip(" \t\n\\")
+            if tail[:1] in (";", "{"):
+                yield m.group(1), tail[0]
+
+    def macros(s, known):   # object-like #defines with a plain value; the first definition wins (#ifndef defaults)
+        for name, value in re.findall(r"^#define[ \t]+(\w+)[ \t]+(\w+)[ \t]*$", s, flags=re.M):
+            known.setdefault(name, value)
+        return known
+
+    def resolve(name, known):
+        while name in known:
+            name = known[name]
+        return name
+
+    paths = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")) + glob.glob(os.path.join(csrc, "*.cpp")))
+    text = {os.path.basename(p): code(p) for p in paths}
+    header = text.pop("c2_internal.hpp")
+    stray = [(f, n) for f, s in text.items() for n, end in signatures(s) if end == ";"]
+    assert not stray, stray
+
+    declared = set()
+    families = dict(re.findall(r"^#define[ \t]+(C2_DECL_\w+)\(\w+\)((?:.*\\\n)*.*)$", header, flags=re.M))
+    for n, end in signatures(re.sub(r"^#define(?:.*\\\n)*.*$", "", header, flags=re.M)):
+        assert end == ";", n   # declarations only
+        declared.add(n)
+    for fam, body in families.items():
+        suffixes = re.findall(r"^%s\((\w+)\)" % fam, header, flags=re.M)
+        assert suffixes, fam
+        for n, end in signatures(body):
+            assert end == ";" and "##" in n, (fam, n)
+            declared |= {n.split("##")[0] + sfx for sfx in suffixes}
+    assert len(declared) > 100, len(declared)
+
+    defined = {}   # name -> [.hip that is compiled on its own and defines it]
+    included = {f: re.findall(r'^#include "(\w+\.hip)"', s, flags=re.M) for f, s in text.items()}
+    wrapped = {inc for incs in included.values() for inc in incs}
+    for f, s in text.items():
+        if not f.endswith(".hip"):
+            continue
+        known, units = macros(s, {}), [s]
+        for inc in included[f]:
+            macros(text[inc], known)
+            units.append(text[inc])
+        sees_header = any('#include "c2_internal.hpp"' in u for u in units)
+        for u in units:
+            for n, end in signatures(u):
+                if end != "{":
+                    continue
+                m = re.match(r"(C2TG?_NAME)\(\s*(\w+)\s*\)", n)
+                if m:   # stem + suffix: C2T_NAME -> C2T_JS (-> C2T_J), C2TG_NAME -> C2TG_ROWS
+                    n = m.group(2) + resolve("C2T_JS" if m.group(1) == "C2T_NAME" else "C2TG_ROWS", known)
+                if n in declared:
+                    assert sees_header, (f, n)
+                    defined.setdefault(n, []).append(f)
+    assert set(defined) == declared, declared ^ set(defined)
+    assert all(len(fs) == 1 for fs in defined.values()), {n: fs for n, fs in defined.items() if len(fs) != 1}
+    assert wrapped == {"c2_loglik_t.hip", "c2_timepar_grad.hip"}

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""GPU checks of the linear-time inverse diagonal: ops.inverse_diag (c2_inverse_diag, csrc/c2_invdiag.hip) in each of its
-lane mappings, and GaussianProcess.inverse_diagonal / predict_observed / leave_one_out on top of it.
+"""GPU checks of the linear-time inverse diagonal: ops.inverse_diag (c2_inverse_diag, csrc/c2_invdiag.hip) at every
+width (the group kernels up to J = 32, the workgroup kernel beyond), and GaussianProcess.inverse_diagonal / predict_observed / leave_one_out on top of it.
 
 References: the numpy restatement of the recurrence (tests/inverse_diag_ref.py, pinned to np.linalg.inv by
 tests/test_inverse_diag.py) and, up to 150 rows, the dense inverse itself.  Criterion: the standing one,
@@ -35,17 +35,6 @@ def host(x):
 def check(key, x, xo, floor=None, what=None):
     e = R.err(host(x) if hasattr(x, "cpu") else x, xo, floor)
     assert e <= 1.0, (what, key, e)
-
-
-def force(monkeypatch, mapping):
-    """The lane mappings of c2_inverse_diag: "lane" (one lane per series, J <= 8), "group" (a group of lanes per series);
-    "default": the dispatch's own choice."""
-    if mapping != "default":
-        monkeypatch.setenv("C2_INVDIAG_LANES", "1" if mapping == "lane" else "8")
-
-
-def mappings(J):
-    return ["default", "group", "lane"] if J <= 8 else ["default"]
 
 
 def batch(seed, B, N, J, *, per_series_t, gap=False, distinct=5):
@@ -100,30 +89,23 @@ def run_case(ops, bt, *, dense, what):
 
 
 @pytest.mark.parametrize("J", WIDTHS)
-def test_inverse_diag_vs_restatement_and_dense(ops, monkeypatch, J):
-    """Every width, each lane mapping forced through its option and the default, N = 1, 2, 33, 150, shared and per-series
-    times, a padded last wavefront (B = 70: not a multiple of 64 series, nor of 64 / G groups), with and without z, alpha
-    aliasing z, one draw with a gap in time."""
-    for mapping in mappings(J):
-        with monkeypatch.context() as mp:
-            force(mp, mapping)
-            for i, N in enumerate((1, 2, 33, 150)):
-                for B in (3, 70):
-                    per_series_t = bool((i + (B == 70)) % 2)
-                    bt = batch(10 * J + i, B, N, J, per_series_t=per_series_t, gap=(N == 150 and B == 3))
-                    run_case(ops, bt, dense=True, what=(mapping, J, N, B, per_series_t))
+def test_inverse_diag_vs_restatement_and_dense(ops, J):
+    """Every width, N = 1, 2, 33, 150, shared and per-series times, a padded last wavefront (B = 70: not a multiple of 64
+    series, nor of 64 / G groups), with and without z, alpha aliasing z, one draw with a gap in time."""
+    for i, N in enumerate((1, 2, 33, 150)):
+        for B in (3, 70):
+            per_series_t = bool((i + (B == 70)) % 2)
+            bt = batch(10 * J + i, B, N, J, per_series_t=per_series_t, gap=(N == 150 and B == 3))
+            run_case(ops, bt, dense=True, what=(J, N, B, per_series_t))
 
 
 @pytest.mark.parametrize("J", WIDTHS)
-def test_inverse_diag_long_series(ops, monkeypatch, J):
-    """N = 4096 (256 blocks of 16 rows) against the restatement; at widths 8, 32, 128 also N = 4097: a first block of one row
-    and, odd, the scalar-request form of the one-lane kernel."""
-    for mapping in mappings(J):
-        with monkeypatch.context() as mp:
-            force(mp, mapping)
-            for N, per_series_t in ((4096, True), (4097, False)) if J in (8, 32, 128) else ((4096, J % 2 == 0),):
-                bt = batch(77 + J, 2, N, J, per_series_t=per_series_t, distinct=2)
-                run_case(ops, bt, dense=False, what=(mapping, J, N))
+def test_inverse_diag_long_series(ops, J):
+    """N = 4096 (256 blocks of 16 rows) against the restatement; at widths 8, 32, 128 also N = 4097: a first block of one
+    row."""
+    for N, per_series_t in ((4096, True), (4097, False)) if J in (8, 32, 128) else ((4096, J % 2 == 0),):
+        bt = batch(77 + J, 2, N, J, per_series_t=per_series_t, distinct=2)
+        run_case(ops, bt, dense=False, what=(J, N))
 
 
 def _gp_inputs(seed, B, N):
@@ -221,13 +203,11 @@ def test_leave_one_out_vs_deleting_the_point(ops):
         check("loo", mu[b], ref[:, 0] + 0.3, what=("loo mean", b))
 
 
-@pytest.mark.parametrize("mapping", ["default", "lane", "group"])
-def test_seventy_thousand_series(ops, monkeypatch, mapping):
+def test_seventy_thousand_series(ops):
     """B = 70 000 (beyond what a grid's y dimension takes) x N = 16: runs, and the first and last series agree with the
     same series computed alone."""
     import torch
 
-    force(monkeypatch, mapping)
     B, N, J = 70000, 16, 4
     rng = np.random.default_rng(8)
     base = R.draw(8, N, J)
@@ -242,7 +222,6 @@ def test_seventy_thousand_series(ops, monkeypatch, mapping):
     q, alpha = ops.inverse_diag(t, c, Ud, W, d, z=z)
     torch.cuda.synchronize()
     assert int(flag.abs().sum()) == 0 and bool(torch.isfinite(q).all()) and bool(torch.isfinite(alpha).all())
-    monkeypatch.delenv("C2_INVDIAG_LANES", raising=False)
     for b in (0, B - 1):
         s = slice(b, b + 1)
         q1, a1 = ops.inverse_diag(t, c, Ud[s].contiguous(), W[s].contiguous(), d[s].contiguous(), z=z[s].contiguous())
@@ -252,12 +231,10 @@ def test_seventy_thousand_series(ops, monkeypatch, mapping):
         check("q", q[b], np.diag(np.linalg.inv(K)), what=("70000 dense", b))
 
 
-@pytest.mark.parametrize("mapping", ["default", "lane", "group"])
-def test_failed_series_gives_nan_and_leaves_its_neighbours_alone(ops, monkeypatch, mapping):
+def test_failed_series_gives_nan_and_leaves_its_neighbours_alone(ops):
     import torch
     from celerite2_amd import gp as G, terms as T
 
-    force(monkeypatch, mapping)
     B, N = 9, 100
     x, diag, y = _gp_inputs(9, B, N)
     bad = diag.copy()
@@ -276,11 +253,10 @@ def test_failed_series_gives_nan_and_leaves_its_neighbours_alone(ops, monkeypatc
             assert bool(torch.isfinite(want).all())
 
 
-@pytest.mark.parametrize("J,mapping", [(8, "lane"), (8, "group"), (2, "lane"), (32, "default"), (40, "default")])
-def test_two_calls_give_identical_bits(ops, monkeypatch, J, mapping):
+@pytest.mark.parametrize("J", [8, 2, 32, 40])
+def test_two_calls_give_identical_bits(ops, J):
     import torch
 
-    force(monkeypatch, mapping)
     bt = batch(21, 130, 200, J, per_series_t=True, distinct=130 if J <= 8 else 6)
     t, c, a, U, V, y = dev(bt["t"], bt["c"], bt["a"], bt["U"], bt["V"], bt["y"])
     d, W, flag = ops.factor(t, c, a, U, V)

@@ -494,14 +494,14 @@ def test_newton_factor_matches_oracle(ops, oracle, monkeypatch, B, N, J):
     close(d2, d.cpu().numpy()); np.testing.assert_allclose(W2.cpu().numpy(), W.cpu().numpy(), rtol=1e-10, atol=1e-12)
 
 
-@pytest.mark.parametrize("scan8,group", [("1", "1"), ("1", "0"), ("0", "1")])
+@pytest.mark.parametrize("scan8", ["1", "0"])
 @pytest.mark.parametrize("B,N", [(1, 4096), (3, 390), (70, 1000), (2, 8200), (1, 100001), (5, 64), (2, 33)])
-def test_width8_scanned_states_both_sides_of_the_switches(ops, oracle, monkeypatch, B, N, scan8, group):
+def test_width8_scanned_states_both_sides_of_the_switches(ops, oracle, monkeypatch, B, N, scan8):
     """Width 8, round 6: `factor`, the forward log-likelihood and the log-likelihood + gradient on the time-parallel forms with
     the chunk-start states from the scanned chunk elements (C2_FACTOR_SCAN8: up-sweep + k_e8_down) or from Newton iterations
-    (= 0), and the chunk pass with the element spread over a group's lanes (C2_E8_GROUP_CHUNKS: k_e8_chunks) or in one lane
-    (= 0, k_tp_onepass<8, 2>) -- every row of d, W, the log-likelihood and all six gradients against the oracle; a failed
-    series hands the batch to the row-by-row kernel, which reports the reference's flag."""
+    (= 0), the chunk pass with the element spread over a group's lanes (k_e8_chunks) -- every row of d, W, the log-likelihood
+    and all six gradients against the oracle; a failed series hands the batch to the row-by-row kernel, which reports the
+    reference's flag."""
     t, c, a, U, V, y = dense.synthetic_batch(min(B, 4), N, 8)
     if B > 4:
         rng = np.random.default_rng(B)
@@ -510,7 +510,6 @@ def test_width8_scanned_states_both_sides_of_the_switches(ops, oracle, monkeypat
         a = np.ascontiguousarray(np.tile(a, (rep, 1))[:B] * rng.uniform(1.0, 1.3, (B, 1)))
         y = np.ascontiguousarray(np.tile(y, (rep, 1))[:B] + 0.05 * rng.standard_normal((B, N)))
     monkeypatch.setenv("C2_FACTOR_SCAN8", scan8)
-    monkeypatch.setenv("C2_E8_GROUP_CHUNKS", group)
     monkeypatch.setenv("C2_FACTOR_ITER", "1")
     args = dev(t, c, a, U, V)
     d, W, flag = ops.factor(*args)

@@ -6,8 +6,7 @@
 
   (a) ops.inverse_diag, with and without z, at 8192 and 65536 x 4096 x 8 and at 64 x 4096 x {8, 16, 32}; beside it, in the
       same process and alternating step by step, ops.solve_upper with one right-hand side (the existing kernel with the same
-      row traffic) and ops.factor (the existing kernel with the same state size).  At the two large batches both lane
-      mappings are forced in turn as well (option invdiag_lanes), which is where the dispatch threshold comes from.
+      row traffic) and ops.factor (the existing kernel with the same state size).
   (b) gp.predict_observed(return_var=True) against the existing gp.predict(return_var=True) at 16 x 4096 x 8 (the old path
       needs 2 GB of cross-covariance there), and predict_observed alone at 65536 x 4096 x 8, where the old path cannot
       allocate.
@@ -41,7 +40,7 @@ def register_table():
         name = re.sub(r"\(.*", "", name).replace("void ", "").replace("c2::invdiag::", "")
         lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (name, vg, ag, sg, lds, scratch, spill))
     lines += ["", "Largest scratch %d bytes, most spilled registers %d (to accumulation registers where scratch is 0) over %d kernels "
-              "(`lane<J, with z, 16-byte requests, rows ahead>`, `group<lanes per series, with z>`)."
+              "(`group<lanes per series, with z>`)."
               % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows))]
     return "\n".join(lines)
 
@@ -76,7 +75,7 @@ def main():
         return
 
     import torch
-    from celerite2_amd import _lib, gp as G, ops, synth, terms as T
+    from celerite2_amd import gp as G, ops, synth, terms as T
 
     assert torch.cuda.is_available(), "this measures the GPU: there is nothing to fall back to"
     dev = torch.device("cuda:0")
@@ -107,7 +106,7 @@ def main():
     lines = ["# ops.inverse_diag beside solve_upper (one right-hand side) and factor", "",
              "One process, steps alternating between the ops, %d timed steps each after %d warm-up steps; ms: median (min .. max)."
              % (a.steps, a.warmup), "",
-             "| B x N x J | op | mapping | ms | algorithmic bytes per row | GB/s | of the 8 TB/s roofline | time / solve_upper |", "|---|---|---|---|---|---|---|---|"]
+             "| B x N x J | op | ms | algorithmic bytes per row | GB/s | of the 8 TB/s roofline | time / solve_upper |", "|---|---|---|---|---|---|---|"]
     for B, N, J in shapes:
         t, c, av, U, V, y = synth.device_batch_fast(0, B, N, J, dev)
         d, W = torch.empty_like(av), torch.empty_like(V)
@@ -120,25 +119,13 @@ def main():
         q, alpha = torch.empty_like(d), torch.empty_like(d)
         zv = z[..., 0]
 
-        def forced(opt, **kw):
-            def fn():
-                _lib.set_option("invdiag_lanes", opt)
-                ops.inverse_diag(t, c, U, W, d, q=q, **kw)
-            return fn
-
-        runs = {("factor", "dispatch"): lambda: ops.factor(t, c, av, U, V, d=d, W=W),
-                ("solve_upper", "dispatch"): lambda: ops.solve_upper(t, c, U, W, z, Z=zu),
-                ("inverse_diag", "dispatch"): forced(None),
-                ("inverse_diag + z", "dispatch"): forced(None, z=zv, alpha=alpha)}
-        if J <= 8 and B >= 4096:
-            runs[("inverse_diag", "one lane per series")] = forced(1)
-            runs[("inverse_diag + z", "one lane per series")] = forced(1, z=zv, alpha=alpha)
-            runs[("inverse_diag", "group of lanes")] = forced(8)
-            runs[("inverse_diag + z", "group of lanes")] = forced(8, z=zv, alpha=alpha)
+        runs = {"factor": lambda: ops.factor(t, c, av, U, V, d=d, W=W),
+                "solve_upper": lambda: ops.solve_upper(t, c, U, W, z, Z=zu),
+                "inverse_diag": lambda: ops.inverse_diag(t, c, U, W, d, q=q),
+                "inverse_diag + z": lambda: ops.inverse_diag(t, c, U, W, d, q=q, z=zv, alpha=alpha)}
         res = alternate(runs, a.steps)
-        _lib.set_option("invdiag_lanes", None)
-        su = res[("solve_upper", "dispatch")][0]
-        for (op, mapping), st in res.items():
+        su = res["solve_upper"][0]
+        for op, st in res.items():
             if op == "factor":
                 nb = 8 * (2 + 2 * J) + 8 * (1 + J)          # t, a, U, V in; d, W out
             elif op == "solve_upper":
@@ -146,8 +133,8 @@ def main():
             else:
                 nb = row_bytes(J, op.endswith("z"))
             rate = nb * B * N / (st[0] * 1e-3)
-            lines.append("| %d x %d x %d | %s | %s | %.3f (%.3f .. %.3f) | %d | %.0f | %.1f %% | %.2f |"
-                         % (B, N, J, op, mapping, st[0], st[1], st[2], nb, rate / 1e9, 100 * rate / PEAK, st[0] / su))
+            lines.append("| %d x %d x %d | %s | %.3f (%.3f .. %.3f) | %d | %.0f | %.1f %% | %.2f |"
+                         % (B, N, J, op, st[0], st[1], st[2], nb, rate / 1e9, 100 * rate / PEAK, st[0] / su))
             print(lines[-1], flush=True)
         if (B, N, J) == (65536, 4096, 8):   # the frontend at the shape the old path cannot allocate (134 MB per series)
             kernel = T.SHOTerm(S0=1.0, w0=3.0, Q=2.0) + T.SHOTerm(S0=0.5, w0=1.0, Q=1.5) + T.SHOTerm(S0=0.3, w0=0.3, Q=0.8) \

@@ -1,5 +1,5 @@
 """One op of the device ABI a few times, for profilers: python tools/op_run.py <op> <B> <N> <J> [reps]
-op: loglik | loglik_grad | terms | terms_grad (coefficient-level, bench coefficients) | factor | factor_s | inverse_diag[_z] (the mapping: C2_INVDIAG_LANES) | factor_rev | solve_rhs<nrhs> | rev_rhs<nrhs> (solve_lower_rev) | predict[_var|_cov] | chain (factor_s + solve_lower F + solve_lower_rev + factor_rev)"""
+op: loglik | loglik_grad | terms | terms_grad (coefficient-level, bench coefficients) | factor | factor_s | inverse_diag[_z] | factor_rev | solve_rhs<nrhs> | rev_rhs<nrhs> (solve_lower_rev) | predict[_var|_cov] | chain (factor_s + solve_lower F + solve_lower_rev + factor_rev)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 """Width 8 on small batches: factor / loglik / loglik_grad row by row, with the Newton iterations on the chunk start states, and
-with the scanned chunk elements (round 6: C2_FACTOR_SCAN8, C2_E8_GROUP_CHUNKS) -- ms, HIP events at the steady clock.
+with the scanned chunk elements (round 6: C2_FACTOR_SCAN8) -- ms, HIP events at the steady clock.
     python tools/scan8_grid.py [factor|loglik|grad ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
