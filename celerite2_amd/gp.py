@@ -174,6 +174,34 @@ class GaussianProcess:
         q, alpha = self._q_alpha(y)
         return self._nan_failed(y - alpha / q, 1.0 / q)
 
+    # -- the variance at NEW times in linear time (ops.explained_variance; no counterpart in the reference) ------
+    def predict_at(self, y, t, *, return_var=False, include_mean=True, check_sorted=True):
+        """The conditional mean (B, M) of the process at the sorted times `t` ((M,) shared or (B, M)), and with
+        `return_var` its variance (B, M) = k(0) - k*^T (K + D)^-1 k*, from two sweeps over the merge of the data and the
+        query grid: O((N + M) J^2) work and O((N + M) J) memory per series, where `predict(y, t, return_var=True)` builds
+        the N x M cross-covariance and solves against M right-hand sides.  The mean is `predict`'s own (already linear).
+
+        The variance uses the semiseparable form of the kernel on both sides of every query, which a TermConvolution
+        does not have inside its exposure window: such a kernel is refused here -- use `predict`.  Widths J <= 32."""
+        from .terms import TermConvolution
+
+        self._need()
+        self._check_vector(y)
+        if isinstance(self.kernel, TermConvolution):
+            raise ValueError("predict_at does not take a TermConvolution kernel (not semiseparable inside the exposure "
+                             "window): use predict(y, t, return_var=True)")
+        cond = ConditionalDistribution(self, y, t=t, include_mean=include_mean)
+        ts = cond._xs
+        if check_sorted and bool((ts[..., 1:] < ts[..., :-1]).any()):
+            raise ValueError("The prediction coordinates must be sorted")
+        if not return_var:
+            return self._nan_failed(cond.mean)[0]
+        B = self._diag.shape[0]
+        zero = torch.zeros((B, ts.shape[-1]), dtype=torch.float64, device=self._diag.device)
+        _, _, Us, Vs = self.kernel.get_celerite_matrices(ts, zero)
+        r = ops.explained_variance(self._t, ts, self._c, self._U, self._W, self._d, Us, Vs)
+        return self._nan_failed(cond.mean, cond._k0() - r)
+
     # -- conditional distribution, core.py:430-478 ------------------------------------------------------
     def condition(self, y, t=None, *, include_mean=True, kernel=None):
         self._need()

@@ -18,7 +18,7 @@ __all__ = [
     "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "general_matmul_lower",
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
-    "inverse_diag",
+    "inverse_diag", "explained_variance",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
     "noise_mean_shift_apply", "noise_mean_shift_rev",
@@ -430,6 +430,34 @@ def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None):
                                      _p(W), _p(d), _p(z), _p(q), _p(alpha), _stream())
     _lib.check(rc, "inverse_diag")
     return q if z is None else (q, alpha)
+
+
+def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):
+    """r (B, M) = diag(K*^T (K + D)^-1 K*) at the M sorted query times `ts` ((M,) shared or (B, M)) against the factored
+    matrix K + D = L diag(d) L^T on the data times `t`: the predictive variance at `ts` is k(0) - r.  Two sweeps over the
+    merge of the two grids (c2_explained_variance), O((N + M) J^2) per series, no N x M array.  Us, Vs (B, M, J): the
+    kernel's U and V rows at the queries.  Caller-owned `out` (B, M) and `work` (B, M, J) are accepted (nothing is
+    allocated then: capturable in a HIP graph); neither may alias an input or the other.  J <= 32."""
+    B, N, J = _dims(U)
+    if Us.dim() != 3:
+        raise ValueError("Invalid shape: Us (must be (B, M, J))")
+    M = Us.shape[1]
+    out = torch.empty((B, M), dtype=torch.float64, device=U.device) if out is None else out
+    work = torch.empty((B, M, J), dtype=torch.float64, device=U.device) if work is None else work
+    _chk(t, ts, c, U, W, d, Us, Vs, out, work)
+    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J))
+    _shape("W", W, (B, N, J)); _shape("d", d, (B, N)); _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J))
+    _shape("out", out, (B, M)); _shape("work", work, (B, M, J))
+    inputs = [x.data_ptr() for x in (t, ts, c, U, W, d, Us, Vs)]
+    if out.data_ptr() in inputs or out.data_ptr() == work.data_ptr():
+        raise ValueError("Invalid argument: out must not alias an input or work")
+    if work.data_ptr() in inputs:
+        raise ValueError("Invalid argument: work must not alias an input")
+    rc = _lib.load().c2_explained_variance(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts),
+                                           _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(W), _p(d), _p(Us), _p(Vs),
+                                           _p(out), _p(work), _stream())
+    _lib.check(rc, "explained_variance")
+    return out
 
 
 def _kron_args(t, c, a, U, V, alpha, diag, y, method):

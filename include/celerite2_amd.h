@@ -439,6 +439,21 @@ int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_
                     const double *U, const double *W, const double *d, const double *z /* nullable */, double *q,
                     double *alpha /* nullable iff z is */, c2_stream_t stream);
 
+/* Explained variance at NEW times, r[b, m] = k*_m^T (K + D)^-1 k*_m for M sorted query times ts against the matrix
+ * c2_factor factored on the N sorted data times t (csrc/c2_predvar.hip): the predictive variance of the process at ts is
+ * k(0) - r.  Two stream-ordered sweeps over the merge of the two grids -- the forward state of c2_factor rebuilt from d, W,
+ * then the backward state of c2_inverse_diag -- O((N + M) J^2) work and O((N + M) J) memory per series.  No counterpart in
+ * the reference, which forms the N x M cross-covariance and solves against M right-hand sides (core.py:134-140); parity is
+ * pinned by dense algebra and by the reference's own predictive variances.  Us, Vs (B,M,J): the U and V rows of the
+ * queries (c2_get_celerite_matrices at ts); U, W, d: the data's, as c2_inverse_diag takes them.  ts_bs: batch stride of
+ * ts like t_bs (0 = shared).  A query at a data time may fall on either side of it: the value is the same.
+ * work: caller-owned, B * M * J doubles, overwritten.  r (B,M) and work must not alias any input or each other.
+ * J <= C2_FAST_WIDTH; wider models return C2_ERR_UNSUPPORTED.  No atomics (two calls give identical bits), no
+ * allocation, no host read: capturable.  Rows of a series whose factorisation failed hold garbage (never another series'). */
+int c2_explained_variance(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts,
+                          int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *W, const double *d,
+                          const double *Us, const double *Vs, double *r, double *work, c2_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * HOST entry points (B == 1, synchronous) -- what celerite2.driver /
  * celerite2.backprop bind.  Same argument meaning as the pybind11 functions of
