@@ -25,6 +25,7 @@ SYMBOLS = [
     "c2_term_coefficients", "c2_term_coefficients_rev", "c2_noise_mean_apply", "c2_noise_mean_rev",
     "c2_term_expr_workspace_bytes", "c2_term_expr_coefficients", "c2_term_expr_coefficients_rev",
     "c2_noise_mean_shift_apply", "c2_noise_mean_shift_rev", "c2_inverse_diag", "c2_explained_variance",
+    "c2_prior_draw",
     "c2h_factor", "c2h_solve_lower", "c2h_solve_upper", "c2h_matmul_lower", "c2h_matmul_upper",
     "c2h_general_matmul_lower", "c2h_general_matmul_upper", "c2h_factor_rev",
     "c2h_solve_lower_rev", "c2h_solve_upper_rev", "c2h_matmul_lower_rev", "c2h_matmul_upper_rev",

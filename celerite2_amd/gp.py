@@ -202,6 +202,54 @@ class GaussianProcess:
         r = ops.explained_variance(self._t, ts, self._c, self._U, self._W, self._d, Us, Vs)
         return self._nan_failed(cond.mean, cond._k0() - r)
 
+    # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
+    def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
+        """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the
+        sorted times `t` ((M,) shared or (B, M)) given `y`, without the M x M covariance that `condition(y, t).sample`
+        factors.  By Matheron's rule, with (f_t, f_s) a joint draw of the noise-free prior process on the data and the query
+        times (ops.prior_draw, one sweep over the merge of the two grids) and eps ~ N(0, D),
+
+            f_s + K(s, t) (K + D)^-1 (y - mean - f_t - eps)    (+ mean)
+
+        is such a draw: apply_inverse with `size` right-hand sides and the two general products of the conditional mean.
+        O((N + M) (J^2 + J size)) work per series, no array larger than (N + M) x size.
+
+        `normals`: a triple (nt (B, N, K), ns (B, M, K), ne (B, N, K)) of standard normals, K = size (1 for None), for
+        reproducibility; otherwise the three are drawn, in that order, with torch.randn(..., generator=generator).  A
+        query that coincides with a data time or an earlier query takes that point's process value (its normals are not
+        used).  A TermConvolution kernel is refused, for predict_at's reason -- use `condition(y, t).sample`.  J <= 32."""
+        from .terms import TermConvolution
+
+        self._need()
+        self._check_vector(y)
+        if isinstance(self.kernel, TermConvolution):
+            raise ValueError("sample_at does not take a TermConvolution kernel (not semiseparable inside the exposure "
+                             "window): use condition(y, t).sample(...)")
+        cond = ConditionalDistribution(self, y, t=t, include_mean=include_mean)
+        ts = cond._xs
+        if check_sorted and bool((ts[..., 1:] < ts[..., :-1]).any()):
+            raise ValueError("The prediction coordinates must be sorted")
+        (B, N), M, dev = self._diag.shape, ts.shape[-1], self._diag.device
+        K = 1 if size is None else int(size)
+        if normals is None:
+            nt, ns, ne = (torch.randn((B, L, K), dtype=torch.float64, device=dev, generator=generator) for L in (N, M, N))
+            ft, fs = nt, ns      # (ours: drawn in place)
+        else:
+            nt, ns, ne = normals
+            for name, x, L in (("nt", nt, N), ("ns", ns, M), ("ne", ne, N)):
+                if tuple(x.shape) != (B, L, K):
+                    raise ValueError("Invalid shape: normals %s %s, expected %s" % (name, tuple(x.shape), (B, L, K)))
+            ft = fs = None       # (the caller's: left as they are)
+        cond._mats2 = self.kernel.get_celerite_matrices(ts, torch.zeros((B, M), dtype=torch.float64, device=dev))
+        _, _, Us, Vs = cond._mats2
+        ft, fs = ops.prior_draw(self._t, ts, self._c, self._U, self._V, Us, Vs, nt.contiguous(), ns.contiguous(), ft=ft, fs=fs)
+        resid = (y - self.mean)[..., None] - ft - torch.sqrt(self._diag)[..., None] * ne
+        out = cond._do_dot(self.apply_inverse(resid), fs).transpose(1, 2)   # (B, K, M)
+        if include_mean:
+            out = out + self.mean
+        out = self._nan_failed(out.reshape(B, K * M))[0].reshape(B, K, M)
+        return out[:, 0] if size is None else out
+
     # -- conditional distribution, core.py:430-478 ------------------------------------------------------
     def condition(self, y, t=None, *, include_mean=True, kernel=None):
         self._need()

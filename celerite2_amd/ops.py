@@ -18,7 +18,7 @@ __all__ = [
     "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "general_matmul_lower",
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
-    "inverse_diag", "explained_variance",
+    "inverse_diag", "explained_variance", "prior_draw",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
     "noise_mean_shift_apply", "noise_mean_shift_rev",
@@ -458,6 +458,40 @@ def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):
                                            _p(out), _p(work), _stream())
     _lib.check(rc, "explained_variance")
     return out
+
+
+def prior_draw(t, ts, c, U, V, Us, Vs, nt, ns, *, ft=None, fs=None):
+    """(ft (B, N, K), fs (B, M, K)): K joint draws of the NOISE-FREE prior process at the sorted data times `t` ((N,)
+    shared or (B, N)) and the sorted query times `ts` ((M,) or (B, M)) -- the Cholesky factor of the zero-noise kernel
+    matrix on the merged grid applied to the standard normals nt (B, N, K), ns (B, M, K), in one forward sweep
+    (c2_prior_draw), O((N + M) (J^2 + J K)) per series, nothing stored per row.  U, V (B, N, J) and Us, Vs (B, M, J): the
+    kernel's rows on the two grids.  A point that coincides with an earlier one takes that point's value and consumes no
+    normal.  Caller-owned `ft`, `fs` are accepted (nothing is allocated then: capturable in a HIP graph); `ft` may be `nt`
+    and `fs` may be `ns` (a row's normals are read before its draw is stored), any other aliasing is refused.  J <= 32."""
+    B, N, J = _dims(U)
+    if Us.dim() != 3:
+        raise ValueError("Invalid shape: Us (must be (B, M, J))")
+    if nt.dim() != 3:
+        raise ValueError("Invalid shape: nt (must be (B, N, K))")
+    M, K = Us.shape[1], nt.shape[2]
+    ft = torch.empty((B, N, K), dtype=torch.float64, device=U.device) if ft is None else ft
+    fs = torch.empty((B, M, K), dtype=torch.float64, device=U.device) if fs is None else fs
+    _chk(t, ts, c, U, V, Us, Vs, nt, ns, ft, fs)
+    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J)); _shape("V", V, (B, N, J))
+    _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J)); _shape("nt", nt, (B, N, K)); _shape("ns", ns, (B, M, K))
+    _shape("ft", ft, (B, N, K)); _shape("fs", fs, (B, M, K))
+    # the only aliasing the sweep allows is ft == nt and fs == ns
+    inputs = {name: x.data_ptr() for name, x in (("t", t), ("ts", ts), ("c", c), ("U", U), ("V", V), ("Us", Us), ("Vs", Vs),
+                                                   ("nt", nt), ("ns", ns))}
+    if ft.data_ptr() in [p for name, p in inputs.items() if name != "nt"] or ft.data_ptr() == fs.data_ptr():
+        raise ValueError("Invalid argument: ft must not alias an input other than nt, or fs")
+    if fs.data_ptr() in [p for name, p in inputs.items() if name != "ns"]:
+        raise ValueError("Invalid argument: fs must not alias an input other than ns")
+    rc = _lib.load().c2_prior_draw(_i64(B), _i64(N), _i64(M), _i64(J), _i64(K), _p(t), _i64(_bs(t, N)), _p(ts),
+                                   _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(V), _p(Us), _p(Vs), _p(nt), _p(ns),
+                                   _p(ft), _p(fs), _stream())
+    _lib.check(rc, "prior_draw")
+    return ft, fs
 
 
 def _kron_args(t, c, a, U, V, alpha, diag, y, method):

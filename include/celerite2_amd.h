@@ -454,6 +454,22 @@ int c2_explained_variance(int64_t B, int64_t N, int64_t M, int64_t J, const doub
                           int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *W, const double *d,
                           const double *Us, const double *Vs, double *r, double *work, c2_stream_t stream);
 
+/* Joint draw of the NOISE-FREE prior process on the merge of the N sorted data times t and the M sorted query times ts
+ * (csrc/c2_priordraw.hip): ft (B,N,K) and fs (B,M,K) = the Cholesky factor of the zero-noise kernel matrix on the merged
+ * grid (data first on a tie) applied to the standard normals nt (B,N,K), ns (B,M,K) -- K independent draws per series.
+ * It is the missing piece of a posterior draw at new times by Matheron's rule,
+ * fs + K(ts, t) (K + D)^-1 (y - mean - ft - sqrt(D) ne), whose other steps are c2_solve_lower / c2_solve_upper and
+ * c2_general_matmul_lower / _upper.  One forward sweep, O((N + M) (J^2 + J K)) work per series, nothing stored per row.  No
+ * counterpart in the reference, which factors the dense M x M conditional covariance (numpy.py:27-32); parity is pinned
+ * by dense algebra.  U, V (B,N,J) and Us, Vs (B,M,J): the kernel's rows at t and ts (c2_get_celerite_matrices; the
+ * diagonal is not used).  A point whose pivot is <= 2^-44 k(0) -- one that coincides with an earlier point -- is
+ * determined by the points in front of it and consumes no normal.  ft may alias nt and fs may alias ns (a row's normals
+ * are read before its draw is stored); no other aliasing.  J <= C2_FAST_WIDTH; wider models return C2_ERR_UNSUPPORTED,
+ * as do more than 65535 register blocks of draws (8 draws a block; 2 at J = 1).  One launch, no atomics (two calls give identical bits), no allocation, no host read: capturable. */
+int c2_prior_draw(int64_t B, int64_t N, int64_t M, int64_t J, int64_t K, const double *t, int64_t t_bs, const double *ts,
+                  int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *V, const double *Us,
+                  const double *Vs, const double *nt, const double *ns, double *ft, double *fs, c2_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * HOST entry points (B == 1, synchronous) -- what celerite2.driver /
  * celerite2.backprop bind.  Same argument meaning as the pybind11 functions of
