@@ -9,6 +9,7 @@ Outputs (git-ignored, but they travel to the GPU box with the tree):
     celerite2_amd/driver.cpython-*.so                  pybind11, mirrors celerite2.driver
     celerite2_amd/backprop.cpython-*.so                pybind11, mirrors celerite2.backprop
 """
+import glob
 import os
 import subprocess
 import sys
@@ -19,7 +20,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libcelerite2_amd.so")
 HIP_SOURCES = ["c2_dispatch.hip", "c2_ops.hip", "c2_fused.hip", "c2_loglik.hip", "c2_loglik4.hip", "c2_loglik_q4.hip", "c2_loglik_t.hip", "c2_loglik_k2.hip", "c2_loglik_t6.hip", "c2_loglik_t4.hip", "c2_loglik_t2.hip", "c2_timepar.hip", "c2_timepar_grad.hip", "c2_timepar_grad32.hip", "c2_timepar_grad16.hip", "c2_sweep.hip", "c2_sweep_rev.hip", "c2_sweep_small.hip", "c2_sweep_small_rev.hip", "c2_solve_cols.hip", "c2_sweep_cols.hip", "c2_scan.hip", "c2_general.hip", "c2_general_tile.hip", "c2_mfma.hip", "c2_wide.hip", "c2_kron.hip", "c2_terms.hip", "c2_term_params.hip", "c2_term_expr.hip", "c2_invdiag.hip", "c2_predvar.hip", "c2_priordraw.hip", "c2_host.hip"]
-HIP_HEADERS = ["c2_common.hpp", "c2_dispatch.hpp", "c2_internal.hpp", "c2_loglik_helpers.hpp", "c2_rscatter.hpp", "c2_term_leaf.hpp", os.path.join(INCLUDE, "celerite2_amd.h")]
+# every header of csrc/ makes every object stale (py_common.hpp among them: harmless), and so does the public header
+HIP_HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(INCLUDE, "celerite2_amd.h")]
 # sources that are #included by other sources (one compilation per width / chunk length): extra dependencies of those only
 HIP_INCLUDED = {"c2_loglik_t.hip": ["c2_loglik_t2.hip", "c2_loglik_t4.hip", "c2_loglik_t6.hip"],
                 "c2_timepar_grad.hip": ["c2_timepar_grad16.hip", "c2_timepar_grad32.hip"]}
@@ -46,22 +48,22 @@ def build_hip(force=False):
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HIP_HEADERS]
+    deps = srcs + HIP_HEADERS
     if not (force or _stale(LIB, deps)):
         return LIB
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     cflags = [f for f in HIPFLAGS if f != "-shared"]
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HIP_HEADERS]
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         extra = [os.path.join(CSRC, inc) for inc, users in HIP_INCLUDED.items() if os.path.basename(src) in users]
-        if force or _stale(obj, [src] + hdrs + extra):
+        if force or _stale(obj, [src] + HIP_HEADERS + extra):
             _run([HIPCC] + cflags + ["-c", src, "-o", obj])
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as pool:
+    # (at most 16 compilers: on a shared host os.cpu_count() is the whole machine, not this process's share)
+    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1, 16)) as pool:
         objs = list(pool.map(compile_one, srcs))
     _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB])
     return LIB

@@ -5,6 +5,7 @@
 #include "c2_common.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 extern "C" int c2_factor_rev_acc(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                  int64_t c_bs, const double *U, const double *d, const double *W, const double *S,
@@ -46,7 +47,6 @@ __global__ __launch_bounds__(256) void k_seeds(int64_t N, const double *__restri
 using namespace c2;
 
 namespace {
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP; }
 struct GradWork {
   double *d, *W, *S, *z, *F, *bd, *bz, *bW;
   size_t bytes;

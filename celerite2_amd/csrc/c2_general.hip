@@ -22,6 +22,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2g {
 using namespace c2;
@@ -364,7 +365,7 @@ extern "C" int c2_internal_general_chunks(int lower, int64_t B, int64_t N, int64
   else if (JM == 16) { if (lower) C2_GC(16, true); else C2_GC(16, false); }
   else { if (lower) C2_GC(32, true); else C2_GC(32, false); }
 #undef C2_GC
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // lower != 0: general_matmul_lower, else upper.  Returns C2_ERR_UNSUPPORTED for shapes the mapping does not cover.
@@ -402,5 +403,5 @@ extern "C" int c2_internal_generalK(int lower, int64_t B, int64_t N, int64_t M, 
   }
 #undef C2_GK
 #undef C2_GK1
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }

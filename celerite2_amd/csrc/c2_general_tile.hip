@@ -27,6 +27,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2gt {
 using namespace c2;
@@ -499,5 +500,5 @@ extern "C" int c2_internal_general_tile(int lower, int64_t B, int64_t N, int64_t
 #undef C2_GT
 #undef C2_GT1
 #undef C2_GT2
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }

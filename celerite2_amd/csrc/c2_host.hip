@@ -28,6 +28,7 @@
 
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace {
 
@@ -95,8 +96,7 @@ struct Staging {
 
   bool fail(hipError_t e) {
     if (e == hipSuccess) return false;
-    c2_internal_set_error(hipGetErrorString(e));
-    err = C2_ERR_HIP;
+    err = c2::hip_check(e);
     return true;
   }
   // Register a host array; returns its handle (shared when the host pointer repeats).  -1: absent.

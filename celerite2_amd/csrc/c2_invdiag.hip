@@ -34,6 +34,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2 {
 namespace invdiag {
@@ -237,29 +238,21 @@ __global__ __launch_bounds__(kWideThreads) void k_invdiag_wide(int64_t N, int J,
   }
 }
 
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
-
 // The wide kernel's dynamic LDS beyond 64 KiB needs the function attribute raised: once per device, to what the widest model
 // takes, on the first wide call -- not on every call (a later call may sit inside a stream capture).
 inline size_t wide_lds_bytes(int64_t J) { return sizeof(double) * ((size_t)J * J + 5 * J + 8); }
 inline int wide_lds_ready() {
   constexpr int kMaxDev = 64;
   static std::once_flag once[kMaxDev];
-  static int rc[kMaxDev];
+  static hipError_t err[kMaxDev];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return (void)launch_ok(), C2_ERR_HIP;
+  if (int e = hip_check(hipGetDevice(&dev))) return e;
+  if (dev < 0 || dev >= kMaxDev) return hip_check(hipErrorInvalidDevice);
   std::call_once(once[dev], [dev] {
-    rc[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(k_invdiag_wide), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)wide_lds_bytes(C2_MAX_WIDTH)) == hipSuccess
-                  ? C2_OK
-                  : launch_ok();
+    err[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(k_invdiag_wide), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)wide_lds_bytes(C2_MAX_WIDTH));
   });
-  return rc[dev] == C2_OK ? C2_OK : C2_ERR_HIP;
+  return hip_check(err[dev]);
 }
 
 template <int G>
@@ -296,13 +289,6 @@ extern "C" int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t,
     return launch_ok();
   }
   if ((B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
-  switch (group_size(J)) {
-    case 1: launch_group<1>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-    case 2: launch_group<2>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-    case 4: launch_group<4>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-    case 8: launch_group<8>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-    case 16: launch_group<16>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-    default: launch_group<32>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); break;
-  }
+  dispatch_group(J, [&](auto g) { launch_group<decltype(g)::value>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); });
   return launch_ok();
 }

@@ -34,6 +34,7 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_dispatch.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2k {
 
@@ -366,12 +367,6 @@ static void launch_collapse_rev(int64_t B, int64_t N, int64_t M, const double *a
 #undef C2K_R
 }
 
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
 inline size_t al2(size_t n) { return (n + 1) & ~(size_t)1; }  // keep sub-arrays 16-byte aligned
 
 struct Plan {  // carve-up of the caller's workspace, in doubles
@@ -446,18 +441,18 @@ int c2_kron_loglik(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, 
     const int64_t total = B * N * M * J;
     hipLaunchKernelGGL(k_kron_expand, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, N, (int)M, (int)J, t,
                        t_bs, a, U, V, alpha, alpha_bs, diag, w + p.t2, w + p.a2, w + p.U2, w + p.V2);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     return c2_loglik(B, N * M, J, w + p.t2, t_bs ? N * M : 0, c, c_bs, w + p.a2, w + p.U2, w + p.V2, y, ll, flag,
                      stream);
   }
   int32_t *badflag = reinterpret_cast<int32_t *>(w + p.badflag);
-  if (hipMemsetAsync(badflag, 0, sizeof(int32_t) * (size_t)B, s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = c2::hip_check(hipMemsetAsync(badflag, 0, sizeof(int32_t) * (size_t)B, s))) return e;
   launch_collapse(B, N, M, a, alpha, alpha_bs, diag, y, w + p.a_eff, w + p.y_eff, w + p.part, badflag, p.nch, s);
-  if (int e = launch_ok()) return e;
+  if (int e = c2::launch_ok()) return e;
   if (int e = c2_loglik(B, N, J, t, t_bs, c, c_bs, w + p.a_eff, U, V, w + p.y_eff, ll, flag, stream)) return e;
   hipLaunchKernelGGL(k_kron_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, p.nch, w + p.part, badflag,
                      ll, flag);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_kron_loglik_grad(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *c,
@@ -477,7 +472,7 @@ int c2_kron_loglik_grad(int64_t B, int64_t N, int64_t M, int64_t J, const double
     const int64_t R = N * M, total = B * R * J;
     hipLaunchKernelGGL(k_kron_expand, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, N, (int)M, (int)J, t,
                        t_bs, a, U, V, alpha, alpha_bs, diag, w + p.t2, w + p.a2, w + p.U2, w + p.V2);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     // by of the interleaved series IS by (B, N, M); bc is shared by both views
     if (int e = c2_internal_loglik_grad_rows(B, R, J, w + p.t2, t_bs ? R : 0, c, c_bs, w + p.a2, w + p.U2, w + p.V2, y, ll,
                                w + p.bt2, bc, w + p.ba2, w + p.bU2, w + p.bV2, by, flag, w + p.one_d,
@@ -486,27 +481,27 @@ int c2_kron_loglik_grad(int64_t B, int64_t N, int64_t M, int64_t J, const double
     hipLaunchKernelGGL(k_kron_expand_rev, dim3((unsigned)p.nch, (unsigned)B), dim3(kThreads), 0, s, B, N, (int)M,
                        (int)J, a, U, V, alpha, alpha_bs, w + p.bt2, w + p.ba2, w + p.bU2, w + p.bV2, bt, ba, bU, bV,
                        bdiag, w + p.part, p.nch);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
   } else {
     int32_t *badflag = reinterpret_cast<int32_t *>(w + p.badflag);
-    if (hipMemsetAsync(badflag, 0, sizeof(int32_t) * (size_t)B, s) != hipSuccess) return C2_ERR_HIP;
+    if (int e = c2::hip_check(hipMemsetAsync(badflag, 0, sizeof(int32_t) * (size_t)B, s))) return e;
     // the GP-free partial sums reuse the head of the (B, nch, M) partial array: they are consumed by k_kron_finish
     // before k_kron_collapse_rev overwrites it
     launch_collapse(B, N, M, a, alpha, alpha_bs, diag, y, w + p.a_eff, w + p.y_eff, w + p.part, badflag, p.nch, s);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     // a_eff = a + 1/A, so d ll / d a = d ll / d a_eff: the 1-D pass writes the caller's ba directly
     if (int e = c2_loglik_grad(B, N, J, t, t_bs, c, c_bs, w + p.a_eff, U, V, w + p.y_eff, ll, bt, bc, ba, bU, bV,
                                w + p.g_y, flag, w + p.one_d, c2_loglik_grad_workspace_bytes(B, N, J), stream))
       return e;
     hipLaunchKernelGGL(k_kron_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, p.nch, w + p.part,
                        badflag, ll, flag);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     launch_collapse_rev(B, N, M, alpha, alpha_bs, diag, y, ba, w + p.g_y, badflag, bdiag, by, w + p.part, p.nch, s);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
   }
   hipLaunchKernelGGL(k_kron_balpha, dim3((unsigned)((B * M + 255) / 256)), dim3(256), 0, s, B, (int)M, p.nch,
                      w + p.part, balpha);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 }  // extern "C"

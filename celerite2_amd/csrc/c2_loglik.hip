@@ -27,6 +27,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 #ifdef C2_REV_TIMING
 __device__ unsigned long long c2_dbg[8];
@@ -1200,7 +1201,6 @@ using namespace c2;
 
 static int64_t simd_count();
 namespace {
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP; }
 template <int MODE>
 int launch_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                const double *a, const double *U, const double *V, const double *y, double *ll, int32_t *flag,
@@ -1452,9 +1452,9 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
       return C2_ERR_UNSUPPORTED;
     }
     void *tmp = nullptr;
-    if (c2::temp_alloc(&tmp, c2_wide_loglik_doubles(B, N, J) * sizeof(double), ws) != hipSuccess) return C2_ERR_HIP;
+    if (int e = hip_check(c2::temp_alloc(&tmp, c2_wide_loglik_doubles(B, N, J) * sizeof(double), ws))) return e;
     int rc = c2_wide_loglik(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
-    if (hipFreeAsync(tmp, ws) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+    rc = keep_first(rc, hipFreeAsync(tmp, ws));
     return rc;
   }
   if (use_lanes2(B, N, J, false)) return c2_internal_loglik_k2(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
@@ -1477,7 +1477,7 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
     void *tmp = nullptr;
     if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
       int rc = c2_internal_loglik_wide(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
-      if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+      rc = keep_first(rc, hipFreeAsync(tmp, s));
       return rc;
     }
     (void)hipGetLastError();
@@ -1493,7 +1493,7 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
       int rc = c2_internal_loglik_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp + 2, guard, stream);
       if (rc == C2_OK)
         rc = launch_fwd<0>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, nullptr, 0, nullptr, nullptr, s, guard + 1);
-      if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+      rc = keep_first(rc, hipFreeAsync(tmp, s));
       return rc;
     }
     (void)hipGetLastError();
@@ -1564,7 +1564,7 @@ int c2_internal_factor_fused_ws(int64_t B, int64_t N, int64_t J, const double *t
     return may_alloc && c2::temp_alloc(tmp, nd * sizeof(double), s) == hipSuccess;
   };
   auto release = [&](void *tmp, int rc) {
-    if (!scratch && hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+    if (!scratch) rc = keep_first(rc, hipFreeAsync(tmp, s));
     return rc;
   };
   // allow_timepar == 2 (the time-parallel gradient builds on d, W): the time-parallel forms from 2048 rows (Newton forced:
@@ -1663,7 +1663,7 @@ extern "C" int c2_internal_factor_rev_long(int64_t B, int64_t N, int64_t J, cons
     rc = c2_internal_factor_rev_replay(B, N, J, t, t_bs, c, c_bs, U, d, W, S, bd, bW, bt, bc, ba, bU, bV,
                                        (const unsigned long long *)tmp, stream);
   c2_internal_debug_capture((const double *)tmp, nullptr, s);
-  if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+  rc = keep_first(rc, hipFreeAsync(tmp, s));
   return rc;
 }
 // factor WITH the S workspace of the drop-in on a small batch of long series (widths 1 .. 8): d, W by the Newton iterations
@@ -1688,7 +1688,7 @@ extern "C" int c2_internal_factor_states_timepar(int64_t B, int64_t N, int64_t J
   int rc = c2_internal_factor_fused_ws(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, /*Newton iterations*/ 2, nullptr, stream);
   if (rc == C2_OK)
     rc = C2_TPG_PICK(c2_internal_s_rows)(B, N, J, t, t_bs, c, c_bs, d, W, flag, S, (double *)tmp, stream);
-  if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+  rc = keep_first(rc, hipFreeAsync(tmp, s));
   return rc;
 }
 
@@ -1796,7 +1796,7 @@ static int loglik_grad_impl(int64_t B, int64_t N, int64_t J, const double *t, in
     // Two lanes per series: as below, the two wavefronts of a group of 64 series raising its guard word together
     hipStream_t s = (hipStream_t)stream;
     unsigned long long *guard = (unsigned long long *)work;
-    if (hipMemsetAsync(guard, 0, 8 * lanes1_gate_words(B), s) != hipSuccess) return C2_ERR_HIP;
+    if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * lanes1_gate_words(B), s))) return e;
     work = (double *)work + lanes1_gate_words(B);
     if (int e = c2_internal_loglik_k2_grad(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
                                            (double *)work, guard, stream))
@@ -1810,7 +1810,7 @@ static int loglik_grad_impl(int64_t B, int64_t N, int64_t J, const double *t, in
     // produces the gradients of those series (same outputs; its workspace overlays the records, which nobody reads any
     // more by then; decided on the device).
     unsigned long long *guard = (unsigned long long *)work;
-    if (hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s) != hipSuccess) return C2_ERR_HIP;
+    if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
     work = (double *)work + lanes1_gate_words(B);
     auto one_lane = J == 8 ? c2_internal_loglik_t_grad8
                   : J == 6 ? c2_internal_loglik_t_grad6
@@ -1933,7 +1933,7 @@ int c2_internal_loglik_g8_tt_grad(int64_t B, int64_t N, int64_t J, int64_t Jc, i
   unsigned long long *tgate = guard + kGateHeadWords;
   hipLaunchKernelGGL(k_anchor_spans, grid, dim3(256), 0, s, B, N, (int)J, C_, kWave / (int)J, x, x_bs, c, J, segg);
   if (int e = launch_ok()) return e;
-  if (hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
   hipLaunchKernelGGL(k_tt8_gate, dim3((unsigned)((B + 63) / 64)), dim3(kWave), 0, s, B, N, (int64_t)grid.x, (int)J,
                      (const unsigned long long *)segg, T, x, x_bs, guard, tgate);
   if (int e = launch_ok()) return e;
@@ -1965,7 +1965,7 @@ int c2_internal_loglik_g8_tt(int64_t B, int64_t N, int64_t J, int64_t Jc, int co
   const dim3 grid((unsigned)((B * J + kWave - 1) / kWave));
   const TermsArgs8 T{ar, ac, bc, dc, coef_batched, (int)Jc};
   unsigned long long *tgate = guard + kGateHeadWords;
-  if (hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
   hipLaunchKernelGGL(k_tt8_gate, dim3((unsigned)((B + 63) / 64)), dim3(kWave), 0, s, B, N, (int64_t)grid.x, (int)J,
                      (const unsigned long long *)nullptr, T, x, x_bs, guard, tgate);
   if (int e = launch_ok()) return e;

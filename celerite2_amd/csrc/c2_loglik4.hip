@@ -17,6 +17,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 #ifndef C2_FWD4_R0
 #define C2_FWD4_R0 8
@@ -217,10 +218,6 @@ __global__ __launch_bounds__(kWave, C2_FWD4_OCC) void k_loglik4_fwd(int64_t B, i
 
 using namespace c2;
 
-namespace {
-inline int launch_ok4() { return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP; }
-}  // namespace
-
 extern "C" {
 
 int c2_internal_loglik4(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
@@ -230,7 +227,7 @@ int c2_internal_loglik4(int64_t B, int64_t N, const double *t, int64_t t_bs, con
   const dim3 grid((unsigned)((B * LG + kWave - 1) / kWave));
   hipLaunchKernelGGL((k_loglik4_fwd<LG, C2_FWD4_R0>), grid, dim3(kWave), 0, (hipStream_t)stream, B, N, t, t_bs, c, c_bs, a, U, V, y, ll,
                      flag);
-  return launch_ok4();
+  return launch_ok();
 }
 
 }  // extern "C"

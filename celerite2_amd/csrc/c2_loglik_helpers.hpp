@@ -1,5 +1,5 @@
-// c2_loglik_helpers.hpp -- device helpers shared by the fused log-likelihood kernels (c2_loglik.hip: one column per
-// lane; c2_loglik4.hip: two columns per lane).
+// c2_loglik_helpers.hpp -- device helpers shared by the row-by-row kernels: written for the fused log-likelihood kernels
+// (the gates, the XOR-ordered gathers), but every sweep file includes it for Geo, rcp_nr, exp_decay and lds_order.
 #pragma once
 #include <cstdint>
 #include "c2_dispatch.hpp"

@@ -44,6 +44,7 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_loglik_helpers.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2k2 {
 using namespace c2;
@@ -927,7 +928,7 @@ int c2_internal_loglik_k2(int64_t B, int64_t N, const double *t, int64_t t_bs, c
   Rec R{};
   hipLaunchKernelGGL((k_k2_fwd<false>), dim3((unsigned)((B + SPW - 1) / SPW)), dim3(kWave), 0, (hipStream_t)stream, B, N, t, t_bs, c, c_bs,
                      a, U, V, y, ll, flag, (double *)nullptr, R, (unsigned long long *)nullptr);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 size_t c2_internal_loglik_k2_record_doubles(int64_t B, int64_t N) { return rec_layout(B, N).total; }
@@ -942,10 +943,10 @@ int c2_internal_loglik_k2_grad(int64_t B, int64_t N, const double *t, int64_t t_
   const Rec R = rec_layout(B, N);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL((k_k2_fwd<true>), grid, dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, rec, R, guard);
-  if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+  if (int e = launch_ok()) return e;
   hipLaunchKernelGGL(k_k2_rev, grid, dim3(kWave), 0, s, B, N, c, c_bs, U, (const int32_t *)flag, (const double *)rec, R,
                      (const unsigned long long *)guard, bt, bc, ba, bU, bV, by);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Coefficient-level forms (J = Jr + 2 Jc == 8; same arguments as c2_internal_loglik_tt8 / _tt_grad8 of c2_loglik_t.hip).
@@ -957,7 +958,7 @@ int c2_internal_loglik_k2_tt(int64_t B, int64_t N, int64_t Jc, int coef_batched,
   Rec R{};
   hipLaunchKernelGGL((k_k2_tt_fwd<false>), dim3((unsigned)((B + SPW - 1) / SPW)), dim3(kWave), 0, (hipStream_t)stream, B, N, x, x_bs,
                      T, diag, y, ll, flag, (double *)nullptr, R, (unsigned long long *)nullptr);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // `guard`: kGateHeadWords + ceil(B / 64) words, ALL zeroed by the caller on the same stream (see c2_internal_loglik_k2_grad).
@@ -973,10 +974,10 @@ int c2_internal_loglik_k2_tt_grad(int64_t B, int64_t N, int64_t Jc, int coef_bat
   const Rec R = rec_layout(B, N);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL((k_k2_tt_fwd<true>), grid, dim3(kWave), 0, s, B, N, x, x_bs, T, diag, y, ll, flag, rec, R, guard);
-  if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+  if (int e = launch_ok()) return e;
   hipLaunchKernelGGL(k_k2_tt_rev, grid, dim3(kWave), 0, s, B, N, x, x_bs, T, (const int32_t *)flag, (const double *)rec, R,
                      (const unsigned long long *)guard, G, bx, bdiag, by);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 }  // extern "C"

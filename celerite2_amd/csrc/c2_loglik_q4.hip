@@ -25,6 +25,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 #ifndef C2_Q4_LN_R
 #define C2_Q4_LN_R 16   // rows per block of the forward kernel's LN instance (8: scalar requests as 64-byte runs; A/B builds)
@@ -944,7 +945,7 @@ int c2_internal_loglik_q4_grad(int64_t B, int64_t N, const double *t, int64_t t_
   }
 #undef C2_Q4_FWD_ARGS
 #undef C2_Q4_REV_ARGS
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Coefficient-level forward only: the forward kernel without its records.  `guard`: kGateHeadWords + ceil(B / 64) words, written
@@ -960,13 +961,13 @@ int c2_internal_loglik_q4_tt(int64_t B, int64_t N, int64_t Jc, int coef_batched,
   const dim3 grid((unsigned)l.waves);
   const q4::TermsArgsQ T{ar, ac, bc, dc, coef_batched, (int)Jc};
   if (int e = c2_internal_anchor_spans(B, N, q4::J, q4::C, q4::SPW, x, x_bs, c, 8, words, stream)) return e;
-  if (hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
   hipLaunchKernelGGL(q4::k_q4_gate_tt, dim3((unsigned)((l.waves + 3) / 4)), dim3(kWave), 0, s, B, N, (int64_t)l.waves,
                      (const unsigned long long *)words, T, x, x_bs, guard, gate);
   hipLaunchKernelGGL((q4::k_q4_fwd<false, 16, true, false>), grid, dim3(kWave), 0, s, B, N, x, x_bs, c, (int64_t)8, diag,
                      (const double *)nullptr, (const double *)nullptr, y, ll, flag, (double2 *)nullptr, l.nslot, (double2 *)nullptr,
                      (double2 *)nullptr, (const unsigned long long *)gate, T);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 size_t c2_internal_loglik_q4_span_words(int64_t B, int64_t N) { return q4::layout(B, N).words; }
 
@@ -990,7 +991,7 @@ int c2_internal_loglik_q4_tt_grad(int64_t B, int64_t N, int64_t Jc, int coef_bat
   const q4::TermsArgsQ T{ar, ac, bc, dc, coef_batched, (int)Jc};
   const q4::TermsGradsQ G{bar, bcr, bac, bbc, bcc, bdc};
   if (int e = c2_internal_anchor_spans(B, N, q4::J, q4::C, q4::SPW, x, x_bs, c, 8, words, stream)) return e;
-  if (hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
   hipLaunchKernelGGL(q4::k_q4_gate_tt, dim3((unsigned)((l.waves + 3) / 4)), dim3(kWave), 0, s, B, N, (int64_t)l.waves,
                      (const unsigned long long *)words, T, x, x_bs, guard, gate);
   hipLaunchKernelGGL((q4::k_q4_fwd<false, 16, true>), grid, dim3(kWave), 0, s, B, N, x, x_bs, c, (int64_t)8, diag,
@@ -999,7 +1000,7 @@ int c2_internal_loglik_q4_tt_grad(int64_t B, int64_t N, int64_t Jc, int coef_bat
   hipLaunchKernelGGL((q4::k_q4_rev<false, true>), grid, dim3(kWave), 0, s, B, N, x, x_bs, c, (int64_t)8, (const double *)nullptr,
                      (const double2 *)W, (const double2 *)DZ, (const double2 *)ck, l.nslot, l.nseg, (const int32_t *)flag, bx,
                      (double *)nullptr, bdiag, (double *)nullptr, (double *)nullptr, by, (const unsigned long long *)gate, T, G);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 // The file is compiled once per width: C2T_J = 8 (default), 4, 2 (c2_loglik_t4.hip / c2_loglik_t2.hip include it).  A
 // tile of the width-J streams is always ONE 128-byte line per series: RT = 16 / J rows.
@@ -1344,7 +1345,7 @@ int C2T_NAME(c2_internal_loglik_t)(int64_t B, int64_t N, const double *t, int64_
   Rec R{};
   hipLaunchKernelGGL((k_loglik_t_fwd<false>), grid, dim3(kWave), 0, (hipStream_t)stream, B, N, t, t_bs, c, c_bs, a, U,
                      V, y, ll, flag, (double *)nullptr, R, (unsigned long long *)nullptr);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Records of the fwd/rev pair, in doubles (the caller overlays them with the replay kernels' workspace: only one of
@@ -1364,10 +1365,10 @@ int C2T_NAME(c2_internal_loglik_t_grad)(int64_t B, int64_t N, const double *t, i
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL((k_loglik_t_fwd<true>), grid, dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, rec,
                      R, guard);
-  if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+  if (int e = launch_ok()) return e;
   hipLaunchKernelGGL(k_loglik_t_rev, grid, dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs, U, (const int32_t *)flag,
                      (const double *)rec, R, (const unsigned long long *)guard, bt, bc, ba, bU, bV, by);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Coefficient-level forward (J = Jr + 2 Jc == 8): log-likelihood straight from (ar, cr, ac, bc, cc, dc, x, diag, y),
@@ -1397,7 +1398,7 @@ int C2T_NAME(c2_internal_loglik_tt)(int64_t B, int64_t N, int64_t Jc, int coef_b
     default: return C2_ERR_UNSUPPORTED;
   }
 #undef C2_TT
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Coefficient-level forward with records + reverse sweep (see c2_internal_loglik_t_grad for `guard`).
@@ -1415,7 +1416,7 @@ int C2T_NAME(c2_internal_loglik_tt_grad)(int64_t B, int64_t N, int64_t Jc, int c
   do {                                                                                                                   \
     hipLaunchKernelGGL((k_loglik_tt_fwd<JC_, true>), grid, dim3(kWave), 0, s, B, N, x, x_bs, T, diag, y, ll, flag, rec, R, \
                        guard);                                                                                           \
-    if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;                                                              \
+    if (int e = launch_ok()) return e;                                                                                   \
     hipLaunchKernelGGL((k_loglik_tt_rev<JC_>), grid, dim3(kWave), 0, s, B, N, x, x_bs, T, (const int32_t *)flag,           \
                        (const double *)rec, R, (const unsigned long long *)guard, G, bx, bdiag, by);                     \
   } while (0)
@@ -1434,7 +1435,7 @@ int C2T_NAME(c2_internal_loglik_tt_grad)(int64_t B, int64_t N, int64_t Jc, int c
     default: return C2_ERR_UNSUPPORTED;
   }
 #undef C2_TT
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 #ifdef C2T_PROF

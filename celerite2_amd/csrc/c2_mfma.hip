@@ -24,6 +24,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2m {
 using namespace c2;
@@ -296,7 +297,7 @@ int run(int64_t B, int64_t N, int64_t nrhs, const double *t, int64_t t_bs, const
   if (c2::temp_alloc((void **)&carry, bytes, s) != hipSuccess) {
     (void)hipGetLastError();
     async = false;
-    if (hipMalloc((void **)&carry, bytes) != hipSuccess) return C2_ERR_HIP;
+    if (int e = hip_check(hipMalloc((void **)&carry, bytes))) return e;
   }
   const dim3 grid((unsigned)(B * nchunk));
   double *Dc = carry + n_carry, *rs = Dc + n_dc;
@@ -309,9 +310,9 @@ int run(int64_t B, int64_t N, int64_t nrhs, const double *t, int64_t t_bs, const
   hipLaunchKernelGGL((k_mm_mfma_scan<3>), g13, dim3(kWave), 0, s, nchunk, NT * 4, m, carry, (const double *)Dc, rs);
   hipLaunchKernelGGL((k_mm_mfma<NT, true, SCALE>), grid, dim3(kWave), 0, s, B, N, nrhs, Lc, nchunk, t, t_bs, c, c_bs, U,
                      V, d, Y, Z, carry, Dc, zero_z);
-  int rc = (hipGetLastError() == hipSuccess) ? C2_OK : C2_ERR_HIP;
+  int rc = launch_ok();
   if (async) {
-    if (hipFreeAsync(carry, s) != hipSuccess) rc = C2_ERR_HIP;
+    rc = keep_first(rc, hipFreeAsync(carry, s));
   } else {
     (void)hipStreamSynchronize(s);
     (void)hipFree(carry);

@@ -19,6 +19,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2 {
 
@@ -1340,12 +1341,6 @@ using namespace c2;
 
 namespace {
 thread_local char g_err[256] = "";
-inline int hip_check(hipError_t e) {
-  if (e == hipSuccess) return C2_OK;
-  snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
-inline int check_launch() { return hip_check(hipGetLastError()); }
 inline dim3 grid_for(int64_t B, int G, int64_t ytiles = 1) {
   const int64_t lanes = B * G;
   return dim3((unsigned)((lanes + kWave - 1) / kWave), (unsigned)ytiles, 1);
@@ -1484,7 +1479,7 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
       void *tmp = nullptr;
       if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
         int rc = c2_internal_solve_cols(LOWER ? 1 : 0, B, N, J, nrhs, t, t_bs, c, c_bs, U, V, Y, Z, (double *)tmp, stream);
-        if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+        rc = keep_first(rc, hipFreeAsync(tmp, s));
         if (rc != C2_ERR_UNSUPPORTED) return rc;
       }
       (void)hipGetLastError();
@@ -1504,7 +1499,7 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
       if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
         int rc = (sh == 2 ? c2_internal_solve_chunks16 : (sh == 1 ? c2_internal_solve_chunks32 : c2_internal_solve_chunks64))(LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V,
                                                                                Y, Z, (double *)tmp, stream, nrhs, F);
-        if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+        rc = keep_first(rc, hipFreeAsync(tmp, s));
         return rc;
       }
       (void)hipGetLastError();
@@ -1521,7 +1516,7 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
       void *tmp = nullptr;
       if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
         int rc = c2_internal_solve_timepar(LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, (double *)tmp, stream);
-        if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+        rc = keep_first(rc, hipFreeAsync(tmp, s));
         return rc;
       }
       (void)hipGetLastError();
@@ -1556,13 +1551,13 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
     C2_DISPATCH_G(group_size(J),
                   hipLaunchKernelGGL((k_sweep<G, KT, LOWER, SOLVE>), grid_for(B, G, 1), dim3(kWave), 0, s, B, N, (int)J,
                                      nrhs, t, t_bs, c, c_bs, U, V, Y, Z, F, zero_z));
-    return check_launch();
+    return launch_ok();
   }
   constexpr int KT = 4;
   C2_DISPATCH_G(group_size(J),
                 hipLaunchKernelGGL((k_sweep<G, KT, LOWER, SOLVE>), grid_for(B, G, (nrhs + KT - 1) / KT), dim3(kWave), 0,
                                    s, B, N, (int)J, nrhs, t, t_bs, c, c_bs, U, V, Y, Z, F, zero_z));
-  return check_launch();
+  return launch_ok();
 }
 
 static bool use_general_tile() {
@@ -1600,7 +1595,7 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
       if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
         int rc = c2_internal_general_chunks(LOWER ? 1 : 0, B, N, M, J, nrhs, Lc, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, (double *)tmp,
                                             stream);
-        if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
+        rc = keep_first(rc, hipFreeAsync(tmp, s));
         if (rc != C2_ERR_UNSUPPORTED) return rc;
       }
       (void)hipGetLastError();
@@ -1621,7 +1616,7 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
     }
     int e = c2_internal_general_tile(LOWER ? 1 : 0, B, N, M, J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F,
                                      (double *)tmp, stream);
-    if (tmp && hipFreeAsync(tmp, s) != hipSuccess && e == C2_OK) e = C2_ERR_HIP;
+    if (tmp) e = keep_first(e, hipFreeAsync(tmp, s));
     if (e != C2_ERR_UNSUPPORTED) return e;
   }
   // three or more right-hand sides: lanes over the right-hand sides, one merge event per iteration (c2_general.hip)
@@ -1646,7 +1641,7 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
       C2_DISPATCH_G(group_size(J),
                     hipLaunchKernelGGL((k_general<G, KT, LOWER>), grid_for(B, G, (nrhs + KT - 1) / KT), dim3(kWave), 0,
                                        s, B, N, M, (int)J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F));
-      return check_launch();
+      return launch_ok();
     }
   }
   C2_DISPATCH_G(group_size(J), {
@@ -1659,10 +1654,9 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
     hipLaunchKernelGGL((k_gm_emit<G, LOWER>), grid_for(B * N, G), dim3(kWave), 0, s, B, N, M, (int)J, nrhs, t1, t1_bs,
                        t2, t2_bs, c, c_bs, U, V, Y, (const double *)Fw, Z);
   });
-  int rc = check_launch();
+  int rc = launch_ok();
   if (!F) {
-    const int rf = hip_check(hipFreeAsync(Fw, s));
-    if (rc == C2_OK) rc = rf;
+    rc = keep_first(rc, hipFreeAsync(Fw, s));
   }
   return rc;
 }
@@ -1732,7 +1726,7 @@ static int launch_sweep_rev(int64_t B, int64_t N, int64_t J, int64_t nrhs, const
   C2_DISPATCH_G(group_size(J),
                 hipLaunchKernelGGL((k_sweep_rev<G, 4, LOWER, SOLVE>), grid_for(B, G), dim3(kWave), 0, s, B, N, (int)J,
                                    nrhs, t, t_bs, c, c_bs, U, V, Y, Z, F, bZ, bt, bc, bU, bV, bY));
-  return check_launch();
+  return launch_ok();
 }
 
 // kappa[b] = max_n a_n / d_n of a factored slice (one workgroup per series); a failed factorisation (flag != 0): +inf.
@@ -1797,11 +1791,11 @@ int c2_factor(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
         hipLaunchKernelGGL((k_s_replay<G, false>), grid_for(B, G), dim3(kWave), 0, s, B, N, t, t_bs, c, c_bs,
                            (const double *)d, (const double *)W, (const int32_t *)flag, S);
     });
-    return check_launch();
+    return launch_ok();
   }
   C2_DISPATCH_G(group_size(J), hipLaunchKernelGGL(k_factor<G>, grid_for(B, G), dim3(kWave), 0, s, B, N, (int)J, t,
                                                   t_bs, c, c_bs, a, U, V, d, W, S, flag));
-  return check_launch();
+  return launch_ok();
 }
 
 int c2_solve_lower(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs, const double *c,
@@ -1848,7 +1842,7 @@ int c2_factor_rev_acc(int64_t B, int64_t N, int64_t J, const double *t, int64_t 
   hipStream_t s = (hipStream_t)stream;
   C2_DISPATCH_G(group_size(J), hipLaunchKernelGGL(k_factor_rev<G>, grid_for(B, G), dim3(kWave), 0, s, B, N, (int)J, t,
                                                   t_bs, c, c_bs, U, d, W, S, bd, bW, bt, bc, ba, bU, bV, accumulate));
-  return check_launch();
+  return launch_ok();
 }
 
 int c2_factor_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
@@ -1908,7 +1902,7 @@ int c2_internal_matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
   const int64_t by = gate ? (B < 512 ? B : 512) : (B < 65535 ? B : 65535);
   hipLaunchKernelGGL(k_matrices, dim3((unsigned)((N + rows_per_block - 1) / rows_per_block), (unsigned)by), dim3(256), 0, (hipStream_t)stream, B, N,
                      (int)Jr, (int)Jc, ar, ac, bc, dc, coef_batched, x, x_bs, diag, a, U, V, gate);
-  if (int e = check_launch()) return e;
+  if (int e = launch_ok()) return e;
   if (Jc > 0) {
     int64_t nb = (B * N + 255) / 256;
     if (gate && nb > 4096) nb = 4096;
@@ -1921,7 +1915,7 @@ int c2_internal_matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
       hipLaunchKernelGGL(k_matrices_big<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, B, N, (int)Jr, (int)Jc, ac, bc,
                          dc, coef_batched, x, x_bs, U, V, gate);
   }
-  return check_launch();
+  return launch_ok();
 }
 int c2_get_celerite_matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ar, const double *ac,
                              const double *bc, const double *dc, int coef_batched, const double *x, int64_t x_bs,
@@ -1943,12 +1937,12 @@ int c2_kernel_values(int64_t B, int64_t N, int64_t M, int64_t Jr, int64_t Jc, co
     const dim3 grid((unsigned)((M + kKvCols - 1) / kKvCols), (unsigned)((N + kKvRows - 1) / kKvRows), (unsigned)B);
     hipLaunchKernelGGL(k_kernel_values_tile, grid, dim3(256), lds, (hipStream_t)stream, N, M, (int)Jr, (int)Jc, ar, cr, ac, bc, cc,
                        dc, coef_batched, t1, t1_bs, t2, t2_bs, K);
-    return check_launch();
+    return launch_ok();
   }
   if ((total + 255) / 256 > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_kernel_values, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, N, M,
                      (int)Jr, (int)Jc, ar, cr, ac, bc, cc, dc, coef_batched, t1, t1_bs, t2, t2_bs, K);
-  return check_launch();
+  return launch_ok();
 }
 
 int c2_colsumsq_over_d(int64_t B, int64_t N, int64_t M, const double *Z, const double *d, double *out, c2_stream_t stream) {
@@ -1956,7 +1950,7 @@ int c2_colsumsq_over_d(int64_t B, int64_t N, int64_t M, const double *Z, const d
   if (B > 65535) return C2_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_colsumsq_over_d, dim3((unsigned)((M + 63) / 64), (unsigned)B), dim3(1024), 0, (hipStream_t)stream, N, M, Z, d,
                      out);
-  return check_launch();
+  return launch_ok();
 }
 
 int c2_dot_tril(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs, const double *c,
@@ -1972,7 +1966,7 @@ int c2_dot_tril(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, 
   const int64_t total = B * N * nrhs;
   hipLaunchKernelGGL(k_scale_sqrt, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total,
                      nrhs, d, Y, Z);
-  if (int e = check_launch()) return e;
+  if (int e = launch_ok()) return e;
   return launch_sweep<true, false>(B, N, J, nrhs, t, t_bs, c, c_bs, U, W, Z, Z, nullptr, 0, stream);
 }
 
@@ -1985,9 +1979,9 @@ int c2_condition(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
   hipStream_t s = (hipStream_t)stream;
   const int64_t slice = B < 4096 ? B : 4096;
   double *tmp = nullptr;
-  if (temp_alloc((void **)&tmp, sizeof(double) * (size_t)slice * (size_t)N * (size_t)(J + 1), s) != hipSuccess) {
+  if (int e = hip_check(temp_alloc((void **)&tmp, sizeof(double) * (size_t)slice * (size_t)N * (size_t)(J + 1), s))) {
     (void)hipGetLastError();
-    return C2_ERR_HIP;
+    return e;
   }
   double *d = tmp, *W = tmp + (size_t)slice * (size_t)N;
   int rc = C2_OK;
@@ -1998,10 +1992,9 @@ int c2_condition(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
     if (rc != C2_OK) break;
     hipLaunchKernelGGL(k_condition, dim3((unsigned)nb), dim3(256), 0, s, N, a + b0 * N, (const double *)d,
                        (const int32_t *)(flag + b0), kappa + b0);
-    rc = check_launch();
+    rc = launch_ok();
   }
-  const int rf = hip_check(hipFreeAsync(tmp, s));
-  return rc == C2_OK ? rf : rc;
+  return keep_first(rc, hipFreeAsync(tmp, s));
 }
 
 }  // extern "C"

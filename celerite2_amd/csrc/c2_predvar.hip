@@ -19,20 +19,11 @@
 //                 solve); a query event adds x^T R x to r_m.  Reads t, d, U, W, ts, X.
 // Mapping of k_invdiag_group: a group of G lanes per series (J <= G <= 32), lane j owns column j of the symmetric state,
 // the state-times-vector product is a lane-local dot product against a vector the group shares through LDS, the scalar
-// of an event is one DPP butterfly.  The merge runs ONE EVENT PER ITERATION with both event kinds predicated, as
-// c2_general.hip does: every series of a wavefront either takes its next data row or its next query, so series whose
-// grids interleave differently do not serialise each other.  A data event and a query event are the same arithmetic with
-// different operands -- h = (state) v, s = v^T h with v = p o w or e o X (backward), the rank-one update with a zero
-// coefficient and a unit decay for a query (forward) -- so predication costs selects, not a second body.  Which grid
-// advances depends on the two current times only (data first on a tie going up, query first going down: the same n).
-//
-// Eight rows of both streams are resident in an LDS ring per series (slot = position mod 8).  The row eight positions
-// down the moving stream is requested at the top of an event and written into the ring four events later (the loop is
-// unrolled by four, so the pending row sits in registers with a static name): nobody waits for a load, and every event
-// issues the same loads so the compiler counts them.  Per-series ring stride = G (mod 32) doubles: the 32/G groups of
-// a half-wavefront that read the same slot land in distinct banks (ds_read_b64: banks of 4 bytes, modulus 64, per 32-lane
-// half); series at different slots conflict at random.  The broadcast vectors are [kWave] doubles, group g at g G: 32/G
-// distinct addresses 2 G banks apart per half -- conflict-free as they stand.
+// of an event is one DPP butterfly.  The merge of the two grids, one event per iteration with both kinds predicated, the
+// tie rule and the request-ahead LDS ring the rows come through are described in c2_merge_ring.hpp.  A data event and a query
+// event are the same arithmetic with different operands -- h = (state) v, s = v^T h with v = p o w or e o X (backward),
+// the rank-one update with a zero coefficient and a unit decay for a query (forward) -- so predication costs selects, not
+// a second body.
 //
 // No atomics: every r_m and X_m is written by exactly one lane, two calls give identical bits.  No lane reads another
 // series.  No allocation, no host read: the pair can be captured in a graph.  B is in grid.x.
@@ -44,26 +35,11 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
+#include "c2_merge_ring.hpp"
 
 namespace c2 {
 namespace predvar {
-
-constexpr int kRing = 8;    // rows of either stream resident per series
-constexpr int kPend = 4;    // events between the request of a row and its arrival in the ring (= the unroll)
-constexpr int kSlots = 2 * kRing + 1;   // data slots, query slots, and one where the request of a finished series goes
-
-// doubles per series: [time: kSlots (+1)][d: kSlots (+1)][row A: kSlots x G][row B: kSlots x G], padded to G (mod 32)
-template <int G>
-struct RingLayout {
-  static constexpr int kScal = kSlots + (kSlots & 1);
-  static constexpr int kRaw = 2 * kScal + 2 * kSlots * G;
-  static constexpr int kStride = kRaw + (((G % 32) - kRaw % 32) + 32) % 32;
-};
-
-// The state's update stays in the event that made it: left to itself the compiler sinks it behind the event's predicated
-// store into the next event, where the vectors it needs (three per column) no longer fit the registers beside the next
-// event's own at G = 32.
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
 
 // DA, DB: the two rows of a data point (forward: W, W; backward: W, U).  QA, QB: those of a query (forward: Us, Vs;
 // backward: X, X).  Forward writes r and X; backward reads a query's r_m eight positions ahead with its row (the d slot of
@@ -76,9 +52,8 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
                                                    const double *__restrict__ DB, const double *QA, const double *QB,
                                                    double *r, double *X) {
   constexpr int SPW = kWave / G, RD = kRing, PD = kPend, NS = kSlots;
-  using Lay = RingLayout<G>;
+  using Lay = RingLayout<G, 2, 0, 4>;   // scalars: time and d; the four vectors below
   constexpr int RS = Lay::kStride;
-  static_assert(RS % 32 == G % 32 && RS >= Lay::kRaw && SPW * RS * 8 + 4 * kWave * 8 <= 64 * 1024, "ring layout");
   __shared__ __attribute__((aligned(16))) double ring[SPW * RS];
   __shared__ __attribute__((aligned(16))) double sv[kWave], sp[kWave], su[kWave], sh[kWave];
   const Geo<G> L(B, J);
@@ -130,7 +105,7 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
       }
       const double tn = rgT[n & (RD - 1)], tq = rgT[RD + (m & (RD - 1))];
       const bool hasn = n < N, hasm = m < M;
-      const bool isd = hasn && (!hasm || (BACK ? tn > tq : tn <= tq));
+      const bool isd = hasn && (!hasm || (BACK ? tn > tq : tn <= tq));   // (the tie rule: c2_merge_ring.hpp)
       const bool isq = !isd && hasm;
       const int pos = isd ? n : m, len1 = (isd ? N : M) - 1;
       const int so = (isd || isq) ? (pos & (RD - 1)) + (isd ? 0 : RD) : 2 * RD;
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
         const double dw = isd ? dn * ea : 0.0;
         sv[L.lane] = v; sp[L.lane] = pj;
         lds_order();
-        double h = 0.0;
+        double h = 0.0;   // (the product and the update in one pass over the columns)
 #pragma unroll
         for (int i = 0; i < G; ++i) {
           const double vi = sv[g0 + i];
@@ -216,13 +191,6 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
   }
 }
 
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
-
 template <int G>
 inline void launch(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts, int64_t ts_bs,
                    const double *c, int64_t c_bs, const double *U, const double *W, const double *d, const double *Us,
@@ -249,13 +217,6 @@ extern "C" int c2_explained_variance(int64_t B, int64_t N, int64_t M, int64_t J,
   if (!t || !ts || !c || !U || !W || !d || !Us || !Vs || !r || !work) return C2_ERR_INVALID;
   if (N + M > 0x7ffffff0LL || (B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  switch (group_size(J)) {
-    case 1: launch<1>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-    case 2: launch<2>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-    case 4: launch<4>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-    case 8: launch<8>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-    case 16: launch<16>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-    default: launch<32>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); break;
-  }
+  dispatch_group(J, [&](auto g) { launch<decltype(g)::value>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); });
   return launch_ok();
 }

@@ -18,11 +18,9 @@
 //
 // Mapping of k_predvar<G, false> (c2_predvar.hip): a group of G lanes per series (J <= G <= 32), lane j owns column j of
 // the symmetric S and row j of F; h is a lane-local dot product against u shared through LDS; d, a and the K values f
-// are DPP butterflies.  ONE EVENT PER ITERATION with both kinds predicated (data first on a tie): they are the same
-// arithmetic with different operand pointers.  Rows come through the request-ahead LDS ring of c2_predvar.hip (eight
-// positions of both streams resident, the row eight positions down the moving stream requested at the top of an event
-// and written into the ring four events later); the normals of a row travel with its row (lane j carries normals
-// j, j + G, ...).  Per-series ring stride = G (mod 32) doubles, as there.
+// are DPP butterflies.  The merge (one event per iteration with both kinds predicated, data first on a tie: they are the
+// same arithmetic with different operand pointers) and the request-ahead LDS ring the rows come through are those of
+// c2_merge_ring.hpp, walking upwards; the normals of a row travel with its row (lane j carries normals j, j + G, ...).
 //
 // The K draws are covered in blocks of KB held in registers (F: KB doubles per lane): KB = 8 (2 at G = 1), and KB = 1
 // for a single draw; block number in grid.y, so a larger K is more wavefronts of ONE launch, each of which recomputes S
@@ -40,29 +38,17 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
+#include "c2_merge_ring.hpp"
 
 namespace c2 {
 namespace priordraw {
 
-constexpr int kRing = 8;    // rows of either stream resident per series
-constexpr int kPend = 4;    // events between the request of a row and its arrival in the ring (= the unroll)
-constexpr int kSlots = 2 * kRing + 1;   // data slots, query slots, and one where the request of a finished series goes
 // draws per register block (K > 1).  One lane per series (G = 1) takes 2: 64 series' rings with eight normals a row
 // would need 98 KB of LDS, and at J = 1 the S a further block recomputes is one number.
 template <int G>
 constexpr int kBlock = G == 1 ? 2 : 8;
 constexpr double kTau = 0x1p-44;   // a point with d <= kTau a is determined by the points in front of it
-
-// doubles per series: [time: kSlots (+1)][u: kSlots x G][v: kSlots x G][z: kSlots x KB], padded to G (mod 32)
-template <int G, int KB>
-struct RingLayout {
-  static constexpr int kScal = kSlots + (kSlots & 1);
-  static constexpr int kRaw = kScal + 2 * kSlots * G + kSlots * KB;
-  static constexpr int kStride = kRaw + (((G % 32) - kRaw % 32) + 32) % 32;
-};
-
-// (as in c2_predvar.hip: the state's update stays in the event that made it)
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
 
 // nt, ns, ft, fs carry no __restrict__: ft may be nt and fs may be ns.
 template <int G, int KB>
@@ -75,9 +61,8 @@ __global__ __launch_bounds__(kWave) void k_priordraw(int64_t B, int N, int M, in
   constexpr int SPW = kWave / G, RD = kRing, PD = kPend, NS = kSlots;
   constexpr int ZL = (KB + G - 1) / G;   // normals a lane carries per row: j, j + G, ...
   constexpr bool ZALL = (ZL * G == KB);  // every lane's every index is inside the block
-  using Lay = RingLayout<G, KB>;
+  using Lay = RingLayout<G, 1, KB, 3>;   // scalar: the time; a slot's KB normals behind the rows; the three vectors below
   constexpr int RS = Lay::kStride;
-  static_assert(RS % 32 == G % 32 && RS >= Lay::kRaw && SPW * RS * 8 + 3 * kWave * 8 <= 64 * 1024, "ring layout");
   __shared__ __attribute__((aligned(16))) double ring[SPW * RS];
   __shared__ __attribute__((aligned(16))) double su[kWave], sp[kWave], sw[kWave];
   const Geo<G> L(B, J);
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(kWave) void k_priordraw(int64_t B, int N, int M, in
       }
       const double tn = rgT[n & (RD - 1)], tq = rgT[RD + (m & (RD - 1))];
       const bool hasn = n < N, hasm = m < M;
-      const bool isd = hasn && (!hasm || tn <= tq);
+      const bool isd = hasn && (!hasm || tn <= tq);   // (the tie rule: c2_merge_ring.hpp)
       const bool isq = !isd && hasm;
       const bool ev = isd || isq;
       const int pos = isd ? n : m, len1 = (isd ? N : M) - 1;
@@ -188,7 +173,7 @@ __global__ __launch_bounds__(kWave) void k_priordraw(int64_t B, int N, int M, in
       const double e = exp_decay(cj * dt);
       su[L.lane] = uj; sp[L.lane] = e;
       lds_order();
-      double h = 0.0;
+      double h = 0.0;   // (the decay and the product in one pass over the columns)
 #pragma unroll
       for (int i = 0; i < G; ++i) {
         St[i] = (sp[g0 + i] * e) * St[i];
@@ -241,13 +226,6 @@ __global__ __launch_bounds__(kWave) void k_priordraw(int64_t B, int N, int M, in
   }
 }
 
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
-
 template <int G>
 inline int launch(int64_t B, int64_t N, int64_t M, int64_t J, int64_t K, const double *t, int64_t t_bs, const double *ts,
                    int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *V, const double *Us,
@@ -279,12 +257,7 @@ extern "C" int c2_prior_draw(int64_t B, int64_t N, int64_t M, int64_t J, int64_t
   if (!t || !ts || !c || !U || !V || !Us || !Vs || !nt || !ns || !ft || !fs) return C2_ERR_INVALID;
   if (N + M > 0x7ffffff0LL || (B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  switch (group_size(J)) {
-    case 1: return launch<1>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-    case 2: return launch<2>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-    case 4: return launch<4>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-    case 8: return launch<8>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-    case 16: return launch<16>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-    default: return launch<32>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
-  }
+  return dispatch_group(J, [&](auto g) {
+    return launch<decltype(g)::value>(B, N, M, J, K, t, t_bs, ts, ts_bs, c, c_bs, U, V, Us, Vs, nt, ns, ft, fs, s);
+  });
 }

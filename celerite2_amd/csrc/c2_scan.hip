@@ -22,6 +22,7 @@
 #include "c2_rscatter.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2 {
 
@@ -190,7 +191,7 @@ int run_chunked(int64_t B, int64_t N, int64_t J, int64_t nrhs, int64_t Lc, const
   if (c2::temp_alloc((void **)&carry, bytes, s) != hipSuccess) {
     (void)hipGetLastError();
     async = false;
-    if (hipMalloc((void **)&carry, bytes) != hipSuccess) return C2_ERR_HIP;
+    if (int e = hip_check(hipMalloc((void **)&carry, bytes))) return e;
   }
   const int G_ = group_size(J);
   // lanes of a unit: G x KG, KG = 64/G column groups when there are enough right-hand sides to feed them
@@ -232,9 +233,9 @@ int run_chunked(int64_t B, int64_t N, int64_t J, int64_t nrhs, int64_t Lc, const
   hipLaunchKernelGGL((k_mm_carry<LOWER>), dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, B, N, (int)J, nrhs, Lc,
                      nchunk, t, t_bs, c, c_bs, carry);
   pass(std::true_type{});
-  int rc = (hipGetLastError() == hipSuccess) ? C2_OK : C2_ERR_HIP;
+  int rc = launch_ok();
   if (async) {
-    if (hipFreeAsync(carry, s) != hipSuccess) rc = C2_ERR_HIP;
+    rc = keep_first(rc, hipFreeAsync(carry, s));
   } else {
     (void)hipStreamSynchronize(s);
     (void)hipFree(carry);

@@ -25,6 +25,7 @@
 #include "c2_common.hpp"
 #include "c2_loglik_helpers.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2cols {
 using namespace c2;
@@ -302,7 +303,7 @@ int c2_internal_solve_cols(int lower, int64_t B, int64_t N, int64_t J, int64_t n
   if (p.JM == 8) { if (lower) C2_COLS(8, true); else C2_COLS(8, false); }
   else { if (lower) C2_COLS(16, true); else C2_COLS(16, false); }
 #undef C2_COLS
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2 {
 
@@ -807,7 +808,7 @@ extern "C" int c2_internal_sweep1(int lower, int solve, int64_t B, int64_t N, in
   }
 #undef C2_SW_G
 #undef C2_SW
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 extern "C" int c2_internal_sweep1_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, const double *t,
@@ -830,7 +831,7 @@ extern "C" int c2_internal_sweep1_rev(int lower, int solve, int64_t B, int64_t N
       if (solve) C2_SWL(false, true, 0); else C2_SWL(false, false, 0);
     }
 #undef C2_SWL
-    return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+    return launch_ok();
   }
 #define C2_SWR(G, LO, SO)                                                                                             \
   do {                                                                                                                \
@@ -857,7 +858,7 @@ extern "C" int c2_internal_sweep1_rev(int lower, int solve, int64_t B, int64_t N
   }
 #undef C2_SWR_G
 #undef C2_SWR
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // Multi-rhs sweeps with lanes over the right-hand sides.  Returns C2_ERR_UNSUPPORTED when the shape does not fit the
@@ -894,7 +895,7 @@ extern "C" int c2_internal_sweepK(int lower, int solve, int64_t B, int64_t N, in
     }
 #undef C2_S8F
 #undef C2_S8
-    if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+    if (int e = launch_ok()) return e;
     if (B8 == B) return C2_OK;
     const int64_t o = B8 * N;   // rows of the series already done
     t += B8 * t_bs; c += B8 * c_bs;
@@ -929,5 +930,5 @@ extern "C" int c2_internal_sweepK(int lower, int solve, int64_t B, int64_t N, in
   }
 #undef C2_SK
 #undef C2_SK1
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }

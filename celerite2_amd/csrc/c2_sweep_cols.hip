@@ -21,6 +21,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "c2_rscatter.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2sc {
 using namespace c2;
@@ -656,7 +657,7 @@ extern "C" int c2_internal_sweep_cols(int lower, int solve, int64_t B, int64_t N
 #undef C2_SC_D
 #undef C2_SC_V
 #undef C2_SC
-  if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+  if (int e = launch_ok()) return e;
   *B8 = nb * 8;
   return C2_OK;
 }
@@ -694,7 +695,7 @@ extern "C" int c2_internal_sweep_cols_rev(int lower, int solve, int64_t B, int64
 #undef C2_SCR_V
 #undef C2_SCR
   }
-  if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+  if (int e = launch_ok()) return e;
   *B8 = nb * 8;
   return C2_OK;
 }

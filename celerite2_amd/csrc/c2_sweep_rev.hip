@@ -23,6 +23,7 @@
 #include "c2_rscatter.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2r {
 using namespace c2;
@@ -496,7 +497,7 @@ extern "C" int c2_internal_sweepK_rev(int lower, int solve, int64_t B, int64_t N
     if (lower) { if (solve) C2_SL(true, true); else C2_SL(true, false); }
     else { if (solve) C2_SL(false, true); else C2_SL(false, false); }
 #undef C2_SL
-    if (hipGetLastError() != hipSuccess) return C2_ERR_HIP;
+    if (int e = launch_ok()) return e;
     if (B8 == B) return C2_OK;
     const int64_t o = B8 * N;   // rows of the series already done
     t += B8 * t_bs; c += B8 * c_bs;
@@ -523,7 +524,7 @@ extern "C" int c2_internal_sweepK_rev(int lower, int solve, int64_t B, int64_t N
   else C2_SKR(16, 16);
 #undef C2_SKR
 #undef C2_SKR1
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // ---- the four reverse sweeps on a small batch of LONG series --------------------------------------------------------------
@@ -680,8 +681,7 @@ extern "C" int c2_internal_sweep_rev_long(int lower, int solve, int64_t B, int64
 #undef C2_RLJ
 #undef C2_RL
     hipLaunchKernelGGL(k_rev_bc, dim3((unsigned)(B * J)), dim3(kWave), 0, s, (int)J, nblk, (const double *)part, bc);
-    if (hipGetLastError() != hipSuccess) rc = C2_ERR_HIP;
+    rc = launch_ok();
   }
-  if (hipFreeAsync(tmp, s) != hipSuccess && rc == C2_OK) rc = C2_ERR_HIP;
-  return rc;
+  return keep_first(rc, hipFreeAsync(tmp, s));
 }

@@ -9,6 +9,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2 {
 
@@ -247,6 +248,6 @@ extern "C" int c2_internal_sweepT_rev(int lower, int solve, int64_t B, int64_t N
   }
 #undef C2_ST1
 #undef C2_ARGS
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 

@@ -24,17 +24,11 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_term_leaf.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace {
 
 using namespace c2leaf;
-
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
 
 // One field of the registers of ONE series: element k is `stride` doubles after element k - 1.
 struct Strided {
@@ -468,7 +462,7 @@ int c2_term_expr_coefficients(const c2_term_expr *expr, int64_t B, const double 
   if (work_bytes < slots_bytes(expr, B, 1)) return C2_ERR_INVALID;
   hipLaunchKernelGGL(k_expr_coefficients, dim3(blocks_for(B)), dim3(256), 0, (hipStream_t)stream, *expr, B, P, p_bs, ar, cr,
                      ac, bc, cc, dc, shift, flag, (double *)work);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_term_expr_coefficients_rev(const c2_term_expr *expr, int64_t B, const double *P, int64_t p_bs, const double *bar,
@@ -482,7 +476,7 @@ int c2_term_expr_coefficients_rev(const c2_term_expr *expr, int64_t B, const dou
   if (work_bytes < slots_bytes(expr, B, 2)) return C2_ERR_INVALID;
   hipLaunchKernelGGL(k_expr_coefficients_rev, dim3(blocks_for(B)), dim3(256), 0, (hipStream_t)stream, *expr, B, P, p_bs, bar,
                      bcr, bac, bbc, bcc, bdc, bshift, tflag, lflag, ll, bP, (double *)work);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 }  // extern "C"

@@ -23,17 +23,11 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_term_leaf.hpp"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace {
 
 using namespace c2leaf;
-
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
 
 __global__ __launch_bounds__(256) void k_coefficients(c2_term_program prog, int64_t B, const double *__restrict__ P,
                                                       int64_t p_bs, double *__restrict__ ar, double *__restrict__ cr,
@@ -184,7 +178,7 @@ int c2_term_coefficients(const c2_term_program *prog, int64_t B, const double *P
   if ((prog->Jr && (!ar || !cr)) || (prog->Jc && (!ac || !bc || !cc || !dc))) return C2_ERR_INVALID;
   hipLaunchKernelGGL(k_coefficients, dim3(blocks_for(B)), dim3(256), 0, (hipStream_t)stream, *prog, B, P, p_bs, ar, cr, ac,
                      bc, cc, dc, flag);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_term_coefficients_rev(const c2_term_program *prog, int64_t B, const double *P, int64_t p_bs, const double *bar,
@@ -196,7 +190,7 @@ int c2_term_coefficients_rev(const c2_term_program *prog, int64_t B, const doubl
   if ((prog->Jr && (!bar || !bcr)) || (prog->Jc && (!bac || !bbc || !bcc || !bdc))) return C2_ERR_INVALID;
   hipLaunchKernelGGL(k_coefficients_rev, dim3(blocks_for(B)), dim3(256), 0, (hipStream_t)stream, *prog, B, P, p_bs, bar, bcr,
                      bac, bbc, bcc, bdc, tflag, lflag, ll, bP);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_noise_mean_shift_apply(int64_t B, int64_t N, const double *yerr, int yerr_is_sigma, const double *jitter,
@@ -218,7 +212,7 @@ int c2_noise_mean_shift_apply(int64_t B, int64_t N, const double *yerr, int yerr
     else C2_NM_APPLY(false, false);
   }
 #undef C2_NM_APPLY
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_noise_mean_apply(int64_t B, int64_t N, const double *yerr, int yerr_is_sigma, const double *jitter,
@@ -237,7 +231,7 @@ int c2_noise_mean_shift_rev(int64_t B, int64_t N, const double *jitter, const do
   else
     hipLaunchKernelGGL(k_noise_mean_rev<false>, grid, dim3(256), 0, (hipStream_t)stream, B, N, jitter, bdiag, by, flag, tflag,
                        bjitter, bmean, bshift);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 int c2_noise_mean_rev(int64_t B, int64_t N, const double *jitter, const double *bdiag, const double *by,

@@ -26,6 +26,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2terms {
 
@@ -158,12 +159,6 @@ __global__ void k_terms_rev_finish(int Jr, int Jc, int nsplit, const double *__r
   }
 }
 
-inline int launch_ok() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return C2_OK;
-  c2_internal_set_error(hipGetErrorString(e));
-  return C2_ERR_HIP;
-}
 inline size_t al2(size_t n) { return (n + 1) & ~(size_t)1; }
 
 struct Plan {
@@ -274,7 +269,7 @@ static int matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *
   const int64_t J = Jr + 2 * Jc;
   hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc,
                      coef_batched, w + p.c, gate);
-  if (int e = launch_ok()) return e;
+  if (int e = c2::launch_ok()) return e;
   return c2_internal_matrices(B, N, Jr, Jc, ar, ac, bc, dc, coef_batched, x, x_bs, diag, w + p.a, w + p.U, w + p.V, gate,
                               (c2_stream_t)s);
 }
@@ -316,7 +311,7 @@ int c2_loglik_terms(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *
     const Plan p = plan(B, N, J, 0);
     hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
                        w + p.c, (const unsigned long long *)nullptr);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     if (four_f) {
       unsigned long long *words = (unsigned long long *)(w + p.total);   // (behind the plan: k_anchor_spans' scratch)
       if (int e = c2_internal_loglik_q4_tt(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, flag, words, guard, stream))
@@ -365,7 +360,7 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
     w += fused_gate_words(B);
     hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
                        w + p.c, (const unsigned long long *)nullptr);
-    if (int e = launch_ok()) return e;
+    if (int e = c2::launch_ok()) return e;
     if (int e = four ? c2_internal_loglik_q4_tt_grad(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar, bcr,
                                                      bac, bbc, bcc, bdc, bx, bdiag, by, flag, w + al2((size_t)B * 8), guard, stream)
                      : c2_internal_loglik_g8_tt_grad(B, N, J, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar,
@@ -379,7 +374,7 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
     // composed chain below -- every kernel of it behind the same word -- produces the gradients instead.
     unsigned long long *guard = (unsigned long long *)work;
     // (two lanes per series: the two wavefronts of a group of 64 series raise its word together -- every word starts at zero)
-    if (hipMemsetAsync(guard, 0, 8 * (two ? fused_gate_words(B) : (size_t)c2::kGateHeadWords), s) != hipSuccess) return C2_ERR_HIP;
+    if (int e = c2::hip_check(hipMemsetAsync(guard, 0, 8 * (two ? fused_gate_words(B) : (size_t)c2::kGateHeadWords), s))) return e;
     w += fused_gate_words(B);
     auto fused = two ? c2_internal_loglik_k2_tt_grad
                      : (J == 8 ? c2_internal_loglik_tt_grad8 : (J == 4 ? c2_internal_loglik_tt_grad4 : c2_internal_loglik_tt_grad2));
@@ -415,7 +410,7 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
   if (nsplit > 1)
     hipLaunchKernelGGL(k_terms_rev_finish, dim3((unsigned)B), dim3(64), 0, s, (int)Jr, (int)Jc, nsplit,
                        (const double *)part, (const double *)(w + p.bc), bar, bcr, bac, bbc, bcc, bdc, gate);
-  return launch_ok();
+  return c2::launch_ok();
 }
 
 }  // extern "C"

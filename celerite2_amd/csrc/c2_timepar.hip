@@ -29,6 +29,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2tp {
 using namespace c2;
@@ -1096,7 +1097,7 @@ inline int run8(int64_t B, int64_t N, const double *t, int64_t t_bs, const doubl
                 unsigned long long *guard, hipStream_t s) {
   const E8Plan p = e8_plan(B, N);
   constexpr size_t REC = ElemIO<8>::REC;
-  if (hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s))) return e;
   hipLaunchKernelGGL((k_e8_chunks<true>), dim3((unsigned)((B * p.K + 7) / 8)), dim3(64), 0, s, B, N, p.K, p.R, t, t_bs, c, c_bs, a, U,
                      V, y, work + p.rec0);
   const double *in = work + p.rec0;
@@ -1111,7 +1112,7 @@ inline int run8(int64_t B, int64_t N, const double *t, int64_t t_bs, const doubl
     in = pong[it & 1];
     Kin = blocks;
   }
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // ---- width 8: the EXACT chunk-start states (what `factor`, `factor + S` and the factor stage of the time-parallel gradient
@@ -1286,7 +1287,7 @@ inline int run8_states(int64_t B, int64_t N, int R, const double *t, int64_t t_b
                        (const double *)(work + q.in), (const double *)(work + q.scr), Tin, i == 0 ? X : work + q.T,
                        work + q.tscr, guard);
   }
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // ---- `factor`: chunk-start states.  The matrices of the chunk elements (no right-hand side) and an inclusive scan inside the
@@ -1595,7 +1596,7 @@ int run(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, in
   const int R = chunk_rows(N);
   const int64_t K = (N + R - 1) / R;
   const dim3 gc((unsigned)((K + kThreads - 1) / kThreads), (unsigned)B), gs((unsigned)B);   // lane <-> chunk
-  if (hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s))) return e;
   if (K <= kThreads) {
     hipLaunchKernelGGL((k_tp_onepass<J, 0>), gc, dim3(kThreads), 0, s, B, N, K, R, t, t_bs, c, c_bs, a, U, V, y, work, ll, flag,
                        guard);
@@ -1604,7 +1605,7 @@ int run(int64_t B, int64_t N, const double *t, int64_t t_bs, const double *c, in
                        guard);
     hipLaunchKernelGGL((k_tp_join<J>), gs, dim3(kThreads), 0, s, B, N, (int64_t)gc.x, (const double *)work, ll, flag, guard);
   }
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // scratch of `factor` (doubles): the chunk-start states; for series of more than 64 chunks also the prefix elements and the
@@ -1622,7 +1623,7 @@ int run_factor(int64_t B, int64_t N, const double *t, int64_t t_bs, const double
   const int64_t K = (N + R - 1) / R, G = B * K, Wn = (K + kThreads - 1) / kThreads;
   double *starts = work, *pref = starts + (size_t)nsym(J) * G, *tin = pref + (size_t)ElemIO<J>::NM * G;
   const dim3 gc((unsigned)Wn, (unsigned)B), gs((unsigned)B);
-  if (hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(guard, 0, 2 * sizeof(unsigned long long), s))) return e;
   if (Wn <= 1) {
     hipLaunchKernelGGL((k_tp_states<J, true>), gc, dim3(kThreads), 0, s, B, N, K, R, t, t_bs, c, c_bs, a, U, V, starts,
                        (double *)nullptr, guard);
@@ -1635,7 +1636,7 @@ int run_factor(int64_t B, int64_t N, const double *t, int64_t t_bs, const double
   }
   hipLaunchKernelGGL((k_tp_factor<J>), gc, dim3(kThreads), 0, s, B, N, K, R, t, t_bs, c, c_bs, a, U, V, (const double *)starts, d,
                      W, flag, guard);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 
@@ -1929,7 +1930,7 @@ int run_solve(int64_t B, int64_t N, const double *t, int64_t t_bs, const double 
     hipLaunchKernelGGL((k_tps_apply<J, LOWER>), gc, dim3(kThreads), 0, s, B, N, K, t, t_bs, c, c_bs, A, Bm, Y, Z,
                        (const double *)scratch);
   }
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 }  // namespace c2tp

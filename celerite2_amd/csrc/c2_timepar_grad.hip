@@ -38,6 +38,7 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 // 1: the dispatch's choice of factor kernels (widths 4 / 2 below 32768 rows: the composed maps of c2_timepar.hip, verified
 // to 5e-11 only -- which the gradient inherits: 1.5e-10 / 6.5e-11 of the largest gradient entry on two WELL-conditioned
@@ -1135,7 +1136,7 @@ static int run(int64_t B, int64_t N, const double *t, int64_t t_bs, const double
   const int64_t K = (N + kRows - 1) / kRows;
   double *d = work + L.d, *W = work + L.W, *z = work + L.z;
   unsigned long long *vw = reinterpret_cast<unsigned long long *>(work + L.vw);
-  if (hipMemsetAsync(vw, 0, kVerifyWords * sizeof(double), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(vw, 0, kVerifyWords * sizeof(double), s))) return e;
   if (int e = c2_internal_factor_fused_ws(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, C2TG_FACTOR_MODE, work + L.fs,
                                           (c2_stream_t)s))
     return e;
@@ -1180,7 +1181,7 @@ static int run(int64_t B, int64_t N, const double *t, int64_t t_bs, const double
                      (const double *)(work + L.dT), (const int32_t *)flag, bt);
   hipLaunchKernelGGL((k_finish_c<J>), dim3((unsigned)(B * J)), dim3(kWave), 0, s, K, (const double *)(work + L.bcp),
                      (const int32_t *)flag, bc);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // ---- factor by Newton iterations on the chunk start states (widths 1 .. 8) --------------------------------------------------
@@ -1757,8 +1758,8 @@ static int run_factor_rev(int64_t B, int64_t N, const double *t, int64_t t_bs, c
   int32_t *flag = reinterpret_cast<int32_t *>(work + L.total);
   double *ll = work + L.z;   // (unused pieces of the layout: the log-likelihood k_starts writes, the F junk)
   unsigned long long *vw = reinterpret_cast<unsigned long long *>(work + L.vw);
-  if (hipMemsetAsync(flag, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess) return C2_ERR_HIP;
-  if (hipMemsetAsync(vw, 0, kVerifyWords * sizeof(double), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(flag, 0, (size_t)B * sizeof(int32_t), s))) return e;
+  if (int e = hip_check(hipMemsetAsync(vw, 0, kVerifyWords * sizeof(double), s))) return e;
   const dim3 cgrid((unsigned)((B * K + kWave - 1) / kWave));
   hipLaunchKernelGGL((k_local<J>), cgrid, dim3(kWave), 0, s, B, N, K, t, t_bs, c, c_bs, d, W, d, work + L.loc, work + L.llp);
   if (K >= kTwoLevelMin) {
@@ -1788,7 +1789,7 @@ static int run_factor_rev(int64_t B, int64_t N, const double *t, int64_t t_bs, c
                      (const double *)(work + L.dT), (const int32_t *)flag, bt);
   hipLaunchKernelGGL((k_finish_c<J>), dim3((unsigned)(B * J)), dim3(kWave), 0, s, K, (const double *)(work + L.bcp),
                      (const int32_t *)flag, bc);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 }  // namespace c2tg
 
@@ -1863,7 +1864,7 @@ static int run_factor_iter(int64_t B, int64_t N, const double *t, int64_t t_bs, 
   unsigned long long *words = (unsigned long long *)work;
   const size_t BK = (size_t)B * K;
   double *X = work + kNewtonHdr, *E = X + BK * NS, *Phi = E + BK * NS;
-  if (hipMemsetAsync(work, 0, ((size_t)kNewtonHdr + BK * NS) * sizeof(double), s) != hipSuccess) return C2_ERR_HIP;
+  if (int e = hip_check(hipMemsetAsync(work, 0, ((size_t)kNewtonHdr + BK * NS) * sizeof(double), s))) return e;
   const dim3 grid((unsigned)((B * K + kWave - 1) / kWave));
   if constexpr (J == 8) {
     if (K >= 2 && use_e8_states(B, N)) {
@@ -1873,7 +1874,7 @@ static int run_factor_iter(int64_t B, int64_t N, const double *t, int64_t t_bs, 
         hipLaunchKernelGGL((k_newton_pass<J, true>), grid, dim3(kWave), 0, s, B, N, K, t, t_bs, c, c_bs, a, U, V, d, W, flag,
                            (const double *)X, E, Phi, (const unsigned long long *)nullptr, words + 1, words + (kNewtonMax + 2) + 1);
         *last_word = words + 1;
-        return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+        return launch_ok();
       }
       if (e != C2_ERR_UNSUPPORTED) return e;
     }
@@ -1898,7 +1899,7 @@ static int run_factor_iter(int64_t B, int64_t N, const double *t, int64_t t_bs, 
     }
   }
   *last_word = words + P;
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 extern "C" int C2TG_NAME(c2_internal_factor_iter)(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                        int64_t c_bs, const double *a, const double *U, const double *V, double *d,
@@ -1945,7 +1946,7 @@ extern "C" int C2TG_NAME(c2_internal_loglik_wide)(int64_t B, int64_t N, int64_t 
   hipLaunchKernelGGL(k_ll_chunks, cgrid, dim3(kWave), 0, s, B, N, K, (const double *)d, (const double *)z, llp);
   hipLaunchKernelGGL(k_ll_series, dim3((unsigned)B), dim3(kWave), 0, s, N, K, (const double *)llp,
                      (const int32_t *)flag, ll);
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 extern "C" size_t C2TG_NAME(c2_internal_factor_rev_timepar_doubles)(int64_t B, int64_t N, int64_t J) {
@@ -1997,7 +1998,7 @@ extern "C" int C2TG_NAME(c2_internal_s_rows)(int64_t B, int64_t N, int64_t J, co
     case 8: run_s_rows<8>(B, N, t, t_bs, c, c_bs, d, W, flag, Sw, scratch, s); break;
     default: return C2_ERR_UNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }
 
 // solve_lower / solve_upper (every right-hand side, optional workspace) by chunk maps (long series of a small batch: the chains in two
@@ -2031,5 +2032,5 @@ extern "C" int C2TG_NAME(c2_internal_solve_chunks)(int lower, int64_t B, int64_t
     default: return C2_ERR_UNSUPPORTED;
   }
 #undef C2TG_SOLVE
-  return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP;
+  return launch_ok();
 }

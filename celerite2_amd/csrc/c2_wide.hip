@@ -20,6 +20,7 @@
 
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
+#include "c2_launch.hpp"
 
 namespace c2w {
 
@@ -453,13 +454,11 @@ __global__ __launch_bounds__(kThreads) void k_ll(int64_t N, const double *__rest
   if (threadIdx.x == 0) ll[b] = flag[b] ? -INFINITY : -0.5 * (s + (double)N * 1.8378770664093454835606594728112);
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? C2_OK : C2_ERR_HIP; }
 inline bool fits(size_t doubles) { return doubles * sizeof(double) <= 160 * 1024; }
 template <class K>
 inline int set_lds(K kern, size_t bytes) {
   if (bytes <= 64 * 1024) return C2_OK;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess
-             ? C2_OK : C2_ERR_HIP;
+  return c2::hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
 }  // namespace c2w
@@ -476,7 +475,7 @@ int c2_wide_factor(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_b
   if (int e = set_lds(k_factor, nd * 8)) return e;
   hipLaunchKernelGGL(k_factor, dim3((unsigned)B), dim3(kThreads), nd * 8, (hipStream_t)stream, N, (int)J, t, t_bs, c, c_bs, a, U,
                      V, d, W, S, flag);
-  return ok();
+  return c2::launch_ok();
 }
 
 int c2_wide_sweep(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
@@ -495,7 +494,7 @@ int c2_wide_sweep(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t
   else if (solve) C2W_SW(false, true);
   else C2W_SW(false, false);
 #undef C2W_SW
-  return ok();
+  return c2::launch_ok();
 }
 
 int c2_wide_sweep_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
@@ -515,7 +514,7 @@ int c2_wide_sweep_rev(int lower, int solve, int64_t B, int64_t N, int64_t J, int
   else if (solve) C2W_SR(false, true);
   else C2W_SR(false, false);
 #undef C2W_SR
-  return ok();
+  return c2::launch_ok();
 }
 
 int c2_wide_factor_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
@@ -527,7 +526,7 @@ int c2_wide_factor_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t
   if (int e = set_lds(k_factor_rev, nd * 8)) return e;
   hipLaunchKernelGGL(k_factor_rev, dim3((unsigned)B), dim3(kThreads), nd * 8, (hipStream_t)stream, N, (int)J, t, t_bs, c, c_bs,
                      U, d, W, S, bd, bW, bt, bc, ba, bU, bV, accumulate);
-  return ok();
+  return c2::launch_ok();
 }
 
 int c2_wide_general(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1, int64_t t1_bs,
@@ -544,7 +543,7 @@ int c2_wide_general(int lower, int64_t B, int64_t N, int64_t M, int64_t J, int64
     hipLaunchKernelGGL((k_general<false>), grid, dim3(kThreads), nd * 8, (hipStream_t)stream, N, M, (int)J, nrhs, t1, t1_bs, t2,
                        t2_bs, c, c_bs, U, V, Y, Z, F, zero_z);
   }
-  return ok();
+  return c2::launch_ok();
 }
 
 // fused log-likelihood of a wide model: factor + solve_lower + reduction; work: B N (J + 2) doubles
@@ -557,14 +556,14 @@ int c2_wide_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_b
   if (int e = c2_wide_sweep(1, 1, B, N, J, 1, t, t_bs, c, c_bs, U, W, y, z, nullptr, 0, stream)) return e;
   hipLaunchKernelGGL(k_ll, dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, N, (const double *)d, (const double *)z,
                      (const int32_t *)flag, ll);
-  return ok();
+  return c2::launch_ok();
 }
 
 int c2_wide_nan_failed(int64_t B, int64_t N, int64_t J, const int32_t *flag, double *bt, double *bc, double *ba, double *bU,
                        double *bV, double *by, c2_stream_t stream) {
   hipLaunchKernelGGL(k_nan_failed, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, B, N, (int)J, flag, bt, bc, ba, bU, bV,
                      by);
-  return ok();
+  return c2::launch_ok();
 }
 
 }  // extern "C"

@@ -105,8 +105,97 @@ def test_fails_loudly_without_gpu(built):
         pytest.skip("a GPU is visible here")
     N, J = 5, 2
     t = np.arange(N, dtype=float)
-    with pytest.raises(RuntimeError, match="HIP error"):
+    with pytest.raises(RuntimeError, match=r"HIP error[^:]*: \S"):   # (the text of the HIP error behind the colon, not the colon alone)
         driver.factor(t, np.ones(J), np.ones(N), np.zeros((N, J)), np.zeros((N, J)), np.ones(N), np.zeros((N, J)))
+
+
+def test_every_entry_point_names_its_hip_error(built):
+    """C2_ERR_HIP never comes without text: without a device every device entry point, handed valid small host arrays
+    (B = 1, N = 4, J = 2, one right-hand side and eight; nothing is launched, so they are never dereferenced), returns
+    C2_ERR_HIP and leaves the HIP error's text in c2_last_error() (csrc/c2_launch.hpp)."""
+    from celerite2_amd import _lib
+
+    lib = _lib.load()
+    if lib.c2_device_count() > 0:
+        pytest.skip("a GPU is visible here")
+    B, N, M, J = 1, 4, 3, 2
+    i64, null = ctypes.c_int64, ctypes.c_void_p(0)
+    keep = []
+
+    def a(*shape):   # a fresh array of ones; the pointer stays valid for the whole test
+        keep.append(np.ones(shape))
+        return keep[-1].ctypes.data_as(ctypes.c_void_p)
+
+    t, ts, c = np.arange(N, dtype=float), np.arange(M, dtype=float) + 0.5, np.ones(J)
+    keep += [t, ts, c]
+    tp, tsp, cp = (x.ctypes.data_as(ctypes.c_void_p) for x in (t, ts, c))
+    flag = np.zeros(B, dtype=np.int32)
+    fp = flag.ctypes.data_as(ctypes.c_void_p)
+    tc = (tp, i64(N), cp, i64(J))   # t, t_bs, c, c_bs
+    sizes = (i64(B), i64(N), i64(J))
+
+    def work(nbytes):
+        keep.append(np.zeros(max(int(nbytes), 8) // 8 + 1))
+        return keep[-1].ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(int(nbytes))
+
+    calls = [("c2_factor", lambda: lib.c2_factor(*sizes, *tc, a(N), a(N, J), a(N, J), a(N), a(N, J), null, fp, null)),
+             ("c2_factor_rev", lambda: lib.c2_factor_rev(*sizes, *tc, a(N), a(N, J), a(N, J), a(N), a(N, J), a(N, J, J), a(N), a(N, J),
+                                                        a(N), a(J), a(N), a(N, J), a(N, J), null)),
+             ("c2_loglik", lambda: lib.c2_loglik(*sizes, *tc, a(N), a(N, J), a(N, J), a(N), a(B), fp, null)),
+             ("c2_loglik_grad", lambda: lib.c2_loglik_grad(*sizes, *tc, a(N), a(N, J), a(N, J), a(N), a(B), a(N), a(J), a(N), a(N, J),
+                                                          a(N, J), a(N), fp, *work(lib.c2_loglik_grad_workspace_bytes(B, N, J)), null)),
+             ("c2_get_celerite_matrices", lambda: lib.c2_get_celerite_matrices(i64(B), i64(N), i64(0), i64(1), null, a(1), a(1), a(1),
+                                                                              ctypes.c_int(0), tp, i64(N), a(N), a(N), a(N, J), a(N, J), null)),
+             ("c2_loglik_terms", lambda: lib.c2_loglik_terms(i64(B), i64(N), i64(0), i64(1), null, null, a(1), a(1), a(1), a(1),
+                                                            ctypes.c_int(0), tp, i64(N), a(N), a(N), a(B), fp,
+                                                            *work(lib.c2_loglik_terms_workspace_bytes(B, N, 0, 1, 0)), null)),
+             ("c2_kron_loglik", lambda: lib.c2_kron_loglik(i64(B), i64(N), i64(2), i64(J), *tc, a(N), a(N, J), a(N, J), a(2), i64(2),
+                                                          a(N, 2), a(N, 2), a(B), fp, ctypes.c_int(0),
+                                                          *work(lib.c2_kron_loglik_workspace_bytes(B, N, 2, J, 0, 0)), null)),
+             ("c2_inverse_diag", lambda: lib.c2_inverse_diag(*sizes, *tc, a(N, J), a(N, J), a(N), null, a(N), null, null)),
+             ("c2_explained_variance", lambda: lib.c2_explained_variance(i64(B), i64(N), i64(M), i64(J), tp, i64(N), tsp, i64(M), cp, i64(J),
+                                                                        a(N, J), a(N, J), a(N), a(M, J), a(M, J), a(M), a(M, J), null))]
+    for K in (1, 8):   # right-hand sides / draws
+        k = i64(K)
+        tail = lambda: (a(N, J), a(N, J), a(N, K), a(N, K))   # U, V | W, Y, Z
+        rev = lambda: (a(N, J), a(N, J), a(N, K), a(N, K), a(N, J, K), a(N, K), a(N), a(J), a(N, J), a(N, J), a(N, K))
+        calls += [("c2_solve_lower[%d]" % K, lambda k=k, tail=tail: lib.c2_solve_lower(*sizes, k, *tc, *tail(), null, null)),
+                  ("c2_solve_upper[%d]" % K, lambda k=k, tail=tail: lib.c2_solve_upper(*sizes, k, *tc, *tail(), null, null)),
+                  ("c2_matmul_lower[%d]" % K, lambda k=k, tail=tail: lib.c2_matmul_lower(*sizes, k, *tc, *tail(), null, ctypes.c_int(1), null)),
+                  ("c2_matmul_upper[%d]" % K, lambda k=k, tail=tail: lib.c2_matmul_upper(*sizes, k, *tc, *tail(), null, ctypes.c_int(1), null)),
+                  ("c2_general_matmul_lower[%d]" % K,
+                   lambda k=k, K=K: lib.c2_general_matmul_lower(i64(B), i64(N), i64(M), i64(J), k, tp, i64(N), tsp, i64(M), cp, i64(J), a(N, J),
+                                                                a(M, J), a(M, K), a(N, K), null, ctypes.c_int(1), null)),
+                  ("c2_solve_lower_rev[%d]" % K, lambda k=k, rev=rev: lib.c2_solve_lower_rev(*sizes, k, *tc, *rev(), null)),
+                  ("c2_matmul_lower_rev[%d]" % K, lambda k=k, rev=rev: lib.c2_matmul_lower_rev(*sizes, k, *tc, *rev(), null)),
+                  ("c2_prior_draw[%d]" % K,
+                   lambda k=k, K=K: lib.c2_prior_draw(i64(B), i64(N), i64(M), i64(J), k, tp, i64(N), tsp, i64(M), cp, i64(J), a(N, J), a(N, J),
+                                                      a(M, J), a(M, J), a(N, K), a(M, K), a(N, K), a(M, K), null))]
+    assert {n.split("[")[0] for n, _ in calls} == {
+        "c2_factor", "c2_solve_lower", "c2_solve_upper", "c2_matmul_lower", "c2_matmul_upper", "c2_general_matmul_lower",
+        "c2_factor_rev", "c2_solve_lower_rev", "c2_matmul_lower_rev", "c2_loglik", "c2_loglik_grad", "c2_get_celerite_matrices",
+        "c2_loglik_terms", "c2_kron_loglik", "c2_inverse_diag", "c2_explained_variance", "c2_prior_draw"}
+    set_error = ctypes.CFUNCTYPE(None, ctypes.c_char_p)(("c2_internal_set_error", lib))   # (a prototype of this test's own)
+    for name, call in calls:
+        set_error(b"")
+        rc = call()
+        assert rc == _lib.C2_ERR_HIP, (name, rc)
+        assert lib.c2_last_error().decode().strip(), name
+
+
+def test_one_launch_error_path():
+    """csrc/c2_launch.hpp is the only place that turns a HIP error into C2_ERR_HIP (and records its text): no .hip names the
+    code, and hipGetLastError appears elsewhere only where a sticky error is cleared on purpose."""
+    import glob
+
+    csrc = os.path.join(ROOT, "celerite2_amd", "csrc")
+    for src in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if os.path.basename(src) == "c2_launch.hpp":
+            continue
+        text = open(src).read()
+        assert "hipGetLastError" not in text.replace("(void)hipGetLastError()", ""), src
+        if src.endswith(".hip"):
+            assert "C2_ERR_HIP" not in text, src
 
 
 def test_dispatch_options_table(built):
