@@ -25,7 +25,8 @@ SYMBOLS = [
     "c2_term_coefficients", "c2_term_coefficients_rev", "c2_noise_mean_apply", "c2_noise_mean_rev",
     "c2_term_expr_workspace_bytes", "c2_term_expr_coefficients", "c2_term_expr_coefficients_rev",
     "c2_noise_mean_shift_apply", "c2_noise_mean_shift_rev", "c2_inverse_diag", "c2_explained_variance",
-    "c2_prior_draw",
+    "c2_prior_draw", "c2_inverse_diag_fwd", "c2_inverse_diag_rev",
+    "c2_get_celerite_matrices_rev_workspace_bytes", "c2_get_celerite_matrices_rev",
     "c2h_factor", "c2h_solve_lower", "c2h_solve_upper", "c2h_matmul_lower", "c2h_matmul_upper",
     "c2h_general_matmul_lower", "c2h_general_matmul_upper", "c2h_factor_rev",
     "c2h_solve_lower_rev", "c2h_solve_upper_rev", "c2h_matmul_lower_rev", "c2h_matmul_upper_rev",
@@ -110,6 +111,8 @@ def load():
     lib.c2_kron_loglik_workspace_bytes.argtypes = [ctypes.c_int64] * 4 + [ctypes.c_int] * 2
     lib.c2_term_expr_workspace_bytes.restype = ctypes.c_size_t
     lib.c2_term_expr_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    lib.c2_get_celerite_matrices_rev_workspace_bytes.restype = ctypes.c_size_t
+    lib.c2_get_celerite_matrices_rev_workspace_bytes.argtypes = [ctypes.c_int64] * 4
     lib.c2_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     lib.c2_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     lib.c2_option_count.restype = ctypes.c_int

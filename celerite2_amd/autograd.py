@@ -6,14 +6,19 @@ c2_loglik_grad once (value and the six cotangents come out of the same checkpoin
 reference's PyMC/JAX ops do in two steps -- pymc/ops.py:104-141), backward just scales the saved gradients by
 the incoming cotangent.  Shared `t` (N,) / `c` (J,) receive the batch-summed gradient.
 
+`loo_log_predictive[_kernel]` is the leave-one-out log predictive density (Rasmussen & Williams 5.4.2) as a training
+objective, through `inverse_diag` and its reverse sweep (csrc/c2_invdiag_rev.hip).
+
 `factor`, `solve_lower`, `solve_upper`, `matmul_lower`, `matmul_upper` are the reference's five differentiable ops
 (python/celerite2/pymc/ops.py:61-141, jax/ops.py:33-172: forward = `backprop.<op>_fwd` with its workspace, gradient =
 `backprop.<op>_rev`), batched, on the device kernels -- for models that compose the ops themselves."""
+import math
+
 import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -258,3 +263,129 @@ solve_lower = _sweep("solve_lower")
 solve_upper = _sweep("solve_upper")
 matmul_lower = _sweep("matmul_lower")
 matmul_upper = _sweep("matmul_upper")
+
+
+class _InverseDiag(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, c, U, W, d, z):
+        args = [None if x is None else x.detach().contiguous() for x in (t, c, U, W, d, z)]
+        out = ops.inverse_diag(*args, workspace=True)
+        q, alpha, (Mws, Fws) = (out[0], None, out[1]) if z is None else out
+        ctx.hz = z is not None
+        ctx.save_for_backward(*[x for x in (*args, q, alpha, Mws, Fws) if x is not None])
+        return q if z is None else (q, alpha)
+
+    @staticmethod
+    def backward(ctx, bq, balpha=None):
+        if ctx.hz:
+            t, c, U, W, d, z, q, alpha, Mws, Fws = ctx.saved_tensors
+            balpha = balpha.contiguous()
+        else:
+            t, c, U, W, d, q, Mws = ctx.saved_tensors
+            z = alpha = Fws = balpha = None
+        bt, bc, bU, bW, bd, bz = ops.inverse_diag_rev(t, c, U, W, d, z, q, alpha, (Mws, Fws), bq.contiguous(), balpha)
+        return _reduce(bt, t), _reduce(bc, c), bU, bW, bd, bz
+
+
+def inverse_diag(t, c, U, W, d, z=None):
+    """q (B, N) = diag((K + D)^-1) from the factors (d, W) -- and with z (B, N), solve_lower of a residual, also
+    alpha = (K + D)^-1 (y - mean): (q, alpha) -- differentiable in every argument (c2_inverse_diag_fwd forward,
+    c2_inverse_diag_rev backward; a shared t / c receives the batch sum).  Composes with `factor` and `solve_lower`.
+    The forward call keeps 8 B N J (J + 1) bytes for the backward pass: 2.4 MB per series at N = 4096, J = 8 -- chunk large
+    batches.  J <= 32."""
+    return _InverseDiag.apply(t, c, U, W, d, z)
+
+
+def _loo_objective(q, alpha):
+    return 0.5 * (torch.log(q) - alpha * alpha / q).sum(dim=1) - 0.5 * q.shape[1] * math.log(2.0 * math.pi)
+
+
+def loo_log_predictive(t, c, a, U, V, y):
+    """Leave-one-out log predictive density (B,), sum_n log N(y_n | y_n - alpha_n / q_n, 1 / q_n) with
+    q = diag((K + D)^-1) and alpha = (K + D)^-1 y, differentiable in all six arguments: the chain
+    factor -> solve_lower -> inverse_diag of this module (O(N J^2) per series each way).  Raises LinAlgError when a
+    factorisation fails (as `factor`).  Workspace: see `inverse_diag`."""
+    d, W = factor(t, c, a, U, V)
+    z = solve_lower(t, c, U, W, y[..., None])[..., 0]
+    q, alpha = inverse_diag(t, c, U, W, d, z)
+    return _loo_objective(q, alpha)
+
+
+class _LooKernel(torch.autograd.Function):
+    """term_coefficients -> noise_mean[_shift]_apply -> get_celerite_matrices -> factor -> solve_lower -> inverse_diag ->
+    the objective -> inverse_diag_rev -> solve_lower_rev -> factor_rev -> get_celerite_matrices_rev ->
+    noise_mean[_shift]_rev / term_coefficients_rev as ONE node: the gradients come out of the forward call (as in
+    _LogLikKernel), backward scales them by the incoming cotangent."""
+
+    @staticmethod
+    def forward(ctx, program, is_sigma, P, x, yerr, jitter, mean, y):
+        tens = (P, x, yerr, jitter, mean, y)
+        Pd, xd, ed, jd, md, yd = [None if v is None else v.detach().contiguous() for v in tens]
+        B = y.shape[0]
+        expr = isinstance(program, ops.TermExpr)
+        grad = any(v is not None and v.requires_grad for v in tens)
+        if expr:
+            coefs, tflag, shift = ops.term_coefficients(program, Pd, B)
+            diag, r = ops.noise_mean_shift_apply(ed, jd, md, shift, yd, yerr_is_sigma=is_sigma)
+        else:
+            diag, r = ops.noise_mean_apply(ed, jd, md, yd, yerr_is_sigma=is_sigma)
+            coefs, tflag = ops.term_coefficients(program, Pd, B)
+        ar, cr, ac, bc, cc, dc = coefs
+        a, U, V = ops.get_celerite_matrices(ar, ac, bc, dc, xd, diag)
+        c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1).contiguous()   # (terms.py:171-173)
+        r3 = r[..., None]
+        neg_inf = torch.full((B,), -math.inf, dtype=torch.float64, device=y.device)
+        if not grad:
+            d, W, flag = ops.factor(xd, c, a, U, V)
+            z = ops.solve_lower(xd, c, U, W, r3)[..., 0]
+            q, alpha = ops.inverse_diag(xd, c, U, W, d, z=z, alpha=z)
+            return torch.where((flag != 0) | (tflag != 0), neg_inf, _loo_objective(q, alpha))
+        d, W, S, flag = ops.factor(xd, c, a, U, V, workspace=True)
+        z3, F = ops.solve_lower(xd, c, U, W, r3, workspace=True)
+        z = z3[..., 0]
+        q, alpha, ws = ops.inverse_diag(xd, c, U, W, d, z=z, workspace=True)
+        loo = torch.where(flag != 0, neg_inf, _loo_objective(q, alpha))
+        bq = 0.5 / q + 0.5 * alpha * alpha / (q * q)
+        balpha = -alpha / q
+        bt, bcv, bU, bW, bd, bz = ops.inverse_diag_rev(xd, c, U, W, d, z, q, alpha, ws, bq, balpha)
+        bt2, bc2, bU2, bW2, bY = ops.solve_lower_rev(xd, c, U, W, r3, z3, F, bz[..., None])
+        bt3, bc3, ba, bU3, bV = ops.factor_rev(xd, c, a, U, V, d, W, S, bd, bW + bW2)
+        bar, bcr, bac, bbc, bcc, bdc, bx, bdiag = ops.get_celerite_matrices_rev(
+            ac, bc, dc, xd, V, bt + bt2 + bt3, bcv + bc2 + bc3, ba, bU + bU2 + bU3, bV, program.Jr)
+        by = bY[..., 0].contiguous()
+        cots = [bar, bcr, bac, bbc, bcc, bdc]
+        if expr:
+            bj, bm, bs = ops.noise_mean_shift_rev(jd, bdiag, by, flag=flag, tflag=tflag)
+            bP = ops.term_coefficients_rev(program, Pd, cots, tflag=tflag, lflag=flag, ll=loo, bshift=bs)
+        else:
+            bP = ops.term_coefficients_rev(program, Pd, cots, tflag=tflag, lflag=flag, ll=loo)
+            bj, bm = ops.noise_mean_rev(jd, bdiag, by, flag=flag)
+        ctx.shared_P, ctx.shared_x = P.dim() == 1, x.dim() == 1
+        ctx.has = (jitter is not None, mean is not None)
+        be = bdiag if not is_sigma else (2.0 * ed * bdiag if yerr.requires_grad else None)
+        ctx.has_e = be is not None
+        ctx.save_for_backward(flag, bP, bj, bm, bx, by, *([be] if be is not None else []))
+        return loo
+
+    backward = staticmethod(_LogLikKernel.backward)   # (the same saved tensors: dead series masked, shared P / x summed)
+
+
+def loo_log_predictive_kernel(kernel, x, y, *, yerr=None, diag=None, jitter=None, mean=None):
+    """Leave-one-out log predictive density (B,) as a differentiable function of the HYPER-PARAMETERS: the arguments and
+    conventions of `log_likelihood_kernel` (tensor parameters of `kernel`, TermExpr kernels with their diagonal shift,
+    `jitter` in quadrature, `mean`, x, yerr | diag, y), the objective of `loo_log_predictive`.  One autograd node; every step
+    between the parameters and the gradient is a device kernel, the reverse of the inverse diagonal among them
+    (csrc/c2_invdiag_rev.hip).  A series whose factorisation fails, or whose Q is on the wrong side of an SHO term's regime,
+    has the value -inf and contributes zero gradient; the others are untouched.  The forward call keeps the workspaces of
+    factor, solve_lower and inverse_diag, 8 B N J (2 J + 2) bytes together (inverse_diag's share: 8 B N J (J + 1), 2.4 MB per
+    series at N = 4096, J = 8): chunk large batches.  J <= 32."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, N) is required")
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B = y.shape[0]
+    if not kernel._has_tensors():
+        raise TypeError("loo_log_predictive_kernel: the kernel has no tensor parameter (give its parameters as device tensors)")
+    P = kernel.parameter_matrix(B)
+    return _LooKernel.apply(kernel.program, yerr is not None, P, x, yerr if diag is None else diag,
+                            _per_series(jitter, B, y), _per_series(mean, B, y), y)

@@ -45,12 +45,15 @@ constexpr int kRows = 16;   // rows per block of the scalar streams: 128 bytes p
 // A group of G lanes per series; lane j owns column j of M.  J <= G (lanes j >= J idle: zero rows, c = 0).
 // LDS: the four width-G vectors of a step (v = p o w, p, u, h) and the transposed scalar streams of two blocks.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int G, bool HASZ>
+// WS: row n also stores the state ENTERING it, before its decay is applied -- column j of M into Mws[b, n, j, :] (lane j
+// writes its own J consecutive doubles, the group J^2) and, with z, F_j into Fws[b, n, j]: what c2_inverse_diag_rev reads.
+template <int G, bool HASZ, bool WS = false>
 __global__ __launch_bounds__(kWave) void k_invdiag_group(int64_t B, int64_t N, int J, const double *__restrict__ t,
                                                          int64_t t_bs, const double *__restrict__ c, int64_t c_bs,
                                                          const double *__restrict__ U, const double *__restrict__ W,
                                                          const double *__restrict__ d, const double *z, double *__restrict__ q,
-                                                         double *alpha) {
+                                                         double *alpha, double *__restrict__ Mws = nullptr,
+                                                         double *__restrict__ Fws = nullptr) {
   constexpr int SPW = kWave / G, R = kRows, NV = (R + G - 1) / G, RD = G >= 32 ? 4 : 8;   // RD: rows of U, W in flight
   __shared__ __attribute__((aligned(16))) double sv[kWave], sp[kWave], su[kWave], sh[kWave];
   __shared__ __attribute__((aligned(16))) double sc[2][3][SPW][R];
@@ -114,6 +117,15 @@ __global__ __launch_bounds__(kWave) void k_invdiag_group(int64_t B, int64_t N, i
         const double tn = sc[buf][0][grp][r], dn = sc[buf][1][grp][r], zn = sc[buf][2][grp][r];
         const double un = ru[r % RD], wn = rw[r % RD];
         load_row(r % RD, n - RD);
+        if constexpr (WS) {
+          if (L.valid && act) {
+            double *mw = Mws + ((L.b * N + n) * J + j) * J;
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+              if (i < J) mw[i] = Mc[i];
+            if constexpr (HASZ) Fws[(L.b * N + n) * J + j] = F;
+          }
+        }
         const double p = exp_decay(cj * (tn - tnext));
         tnext = tn;
         const double v = p * wn;
@@ -256,14 +268,29 @@ inline int wide_lds_ready() {
 }
 
 template <int G>
+inline void launch_group_ws(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
+                            const double *U, const double *W, const double *d, const double *z, double *q, double *alpha,
+                            double *Mws, double *Fws, hipStream_t s) {
+  const dim3 grid((unsigned)((B * G + kWave - 1) / kWave));
+  if (z)
+    hipLaunchKernelGGL((k_invdiag_group<G, true, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q,
+                       alpha, Mws, Fws);
+  else
+    hipLaunchKernelGGL((k_invdiag_group<G, false, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q,
+                       alpha, Mws, Fws);
+}
+
+template <int G>
 inline void launch_group(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
                          const double *U, const double *W, const double *d, const double *z, double *q, double *alpha,
                          hipStream_t s) {
   const dim3 grid((unsigned)((B * G + kWave - 1) / kWave));
   if (z)
-    hipLaunchKernelGGL((k_invdiag_group<G, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q, alpha);
+    hipLaunchKernelGGL((k_invdiag_group<G, true>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q, alpha,
+                       (double *)nullptr, (double *)nullptr);
   else
-    hipLaunchKernelGGL((k_invdiag_group<G, false>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q, alpha);
+    hipLaunchKernelGGL((k_invdiag_group<G, false>), grid, dim3(kWave), 0, s, B, N, (int)J, t, t_bs, c, c_bs, U, W, d, z, q, alpha,
+                       (double *)nullptr, (double *)nullptr);
 }
 
 }  // namespace invdiag
@@ -290,5 +317,18 @@ extern "C" int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t,
   }
   if ((B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
   dispatch_group(J, [&](auto g) { launch_group<decltype(g)::value>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, s); });
+  return launch_ok();
+}
+
+extern "C" int c2_inverse_diag_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
+                                   int64_t c_bs, const double *U, const double *W, const double *d, const double *z, double *q,
+                                   double *alpha, double *Mws, double *Fws, c2_stream_t stream) {
+  if (B < 1 || N < 1 || J < 1) return C2_ERR_INVALID;
+  if (J > C2_FAST_WIDTH) return C2_ERR_UNSUPPORTED;   // (J^2 doubles per row: 131 KB at J = 128)
+  if (!t || !c || !U || !W || !d || !q || !Mws || ((z == nullptr) != (alpha == nullptr)) || ((z == nullptr) != (Fws == nullptr)))
+    return C2_ERR_INVALID;
+  if ((B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  dispatch_group(J, [&](auto g) { launch_group_ws<decltype(g)::value>(B, N, J, t, t_bs, c, c_bs, U, W, d, z, q, alpha, Mws, Fws, s); });
   return launch_ok();
 }

@@ -413,4 +413,41 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
   return c2::launch_ok();
 }
 
+// k_terms_rev on its own: the reverse of c2_get_celerite_matrices for callers that run another chain between the matrices
+// and their cotangents (autograd.loo_log_predictive_kernel).  No gate; the same split over a handful of long series.
+static int rev_nsplit(int64_t B, int64_t N) {
+  if (!(B < 64 && N >= 8192)) return 1;
+  const int64_t n = (N + 2047) / 2048;
+  return (int)(n > 256 ? 256 : n);
+}
+
+size_t c2_get_celerite_matrices_rev_workspace_bytes(int64_t B, int64_t N, int64_t Jr, int64_t Jc) {
+  if (check(B, N, Jr, Jc)) return 0;
+  const int nsplit = rev_nsplit(B, N);
+  return nsplit > 1 ? sizeof(double) * (size_t)B * nsplit * (Jr + Jc) * 4 : 0;
+}
+
+int c2_get_celerite_matrices_rev(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ac, const double *bc,
+                                 const double *dc, int coef_batched, const double *x, int64_t x_bs, const double *V,
+                                 const double *bt, const double *bcv, const double *ba, const double *bU, const double *bV,
+                                 double *bar, double *bcr, double *bac, double *bbc, double *bcc, double *bdc, double *bx,
+                                 double *bdiag, void *work, size_t work_bytes, c2_stream_t stream) {
+  if (int e = check(B, N, Jr, Jc)) return e;
+  if (!x || !V || !bt || !bcv || !ba || !bU || !bV || !bx || !bdiag || (Jr && (!bar || !bcr)) ||
+      (Jc && (!ac || !bc || !dc || !bac || !bbc || !bcc || !bdc)))
+    return C2_ERR_INVALID;
+  const int nsplit = rev_nsplit(B, N);
+  if (nsplit > 1 && (!work || work_bytes < c2_get_celerite_matrices_rev_workspace_bytes(B, N, Jr, Jc))) return C2_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned long long *gate = nullptr;
+  double *part = (double *)work;
+  const int64_t trb = B < 0x7fffffff ? B : 0x7fffffff;
+  hipLaunchKernelGGL(k_terms_rev, dim3((unsigned)trb, (unsigned)nsplit), dim3(kThreads), 0, s, B, N, (int)Jr, (int)Jc, ac, bc, dc,
+                     coef_batched, x, x_bs, V, bt, bcv, ba, bU, bV, bar, bcr, bac, bbc, bcc, bdc, bx, bdiag, gate, nsplit, part);
+  if (nsplit > 1)
+    hipLaunchKernelGGL(k_terms_rev_finish, dim3((unsigned)B), dim3(64), 0, s, (int)Jr, (int)Jc, nsplit, (const double *)part, bcv,
+                       bar, bcr, bac, bbc, bcc, bdc, gate);
+  return c2::launch_ok();
+}
+
 }  // extern "C"

@@ -174,6 +174,25 @@ class GaussianProcess:
         q, alpha = self._q_alpha(y)
         return self._nan_failed(y - alpha / q, 1.0 / q)
 
+    def loo_log_predictive(self, y):
+        """Leave-one-out log predictive density (B,), sum_n log N(y_n | mean_n, var_n) of `leave_one_out(y)`
+        (Rasmussen & Williams 5.4.2): sum_n (log q_n - alpha_n^2 / q_n) / 2 - N log(2 pi) / 2, from one solve_lower and one
+        inverse_diag pass.  Not differentiable (`loo_log_predictive_kernel` is); a failed series gets -inf."""
+        self._need()
+        q, alpha = self._q_alpha(y)
+        v = 0.5 * (torch.log(q) - alpha * alpha / q).sum(dim=1) - 0.5 * self._size * math.log(2 * math.pi)
+        return torch.where(self._flag != 0, torch.full_like(v, -math.inf), v)
+
+    def loo_log_predictive_kernel(self, y, *, jitter=None):
+        """The leave-one-out log predictive density (B,) of `y` as a differentiable function of the kernel's tensor
+        hyper-parameters, of `jitter` and of a tensor `mean`: autograd.loo_log_predictive_kernel on this GP's t, diag and
+        mean (as `log_likelihood_kernel` is for the marginal likelihood)."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.loo_log_predictive_kernel(self.kernel, self._t, y, diag=self._diag, jitter=jitter, mean=self.mean)
+
     # -- the variance at NEW times in linear time (ops.explained_variance; no counterpart in the reference) ------
     def predict_at(self, y, t, *, return_var=False, include_mean=True, check_sorted=True):
         """The conditional mean (B, M) of the process at the sorted times `t` ((M,) shared or (B, M)), and with

@@ -18,7 +18,7 @@ __all__ = [
     "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "general_matmul_lower",
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
-    "inverse_diag", "explained_variance", "prior_draw",
+    "inverse_diag", "inverse_diag_rev", "get_celerite_matrices_rev", "explained_variance", "prior_draw",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
     "noise_mean_shift_apply", "noise_mean_shift_rev",
@@ -404,11 +404,28 @@ def dot_tril(t, c, U, W, d, Y, Z=None):
 _KRON_METHODS = {"collapsed": 0, "interleaved": 1}
 
 
-def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None):
+def _no_alias(outs, ins):
+    """No output may share its first byte with an input or another output ("<name> must not alias <name>")."""
+    seen = [(nm, x.data_ptr()) for nm, x in ins if x is not None and x.numel()]
+    for nm, x in outs:
+        if x is None or not x.numel():
+            continue
+        for other, ptr in seen:
+            if x.data_ptr() == ptr:
+                raise ValueError("Invalid argument: %s must not alias %s" % (nm, other))
+        seen.append((nm, x.data_ptr()))
+
+
+def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None, *, workspace=False, ws=None):
     """q (B, N), the diagonal of the inverse of the factored matrix K + D = L diag(d) L^T, in one backward sweep over
     d, W (c2_inverse_diag).  With z (B, N) -- solve_lower of a residual -- the same pass also returns
     alpha = L^-T (z / d) = (K + D)^-1 (y - mean): (q, alpha); `alpha` may be `z` itself (the only aliasing allowed).  Caller-owned outputs `q`,
-    `alpha` are accepted (nothing is allocated then: capturable in a HIP graph)."""
+    `alpha` are accepted (nothing is allocated then: capturable in a HIP graph).
+
+    `workspace=True` (c2_inverse_diag_fwd): the same q and alpha, bit for bit, and the states inverse_diag_rev reads --
+    returns (q, ws) or (q, alpha, ws) with ws = (Mws (B, N, J, J), Fws (B, N, J) | None without z): 8 B N J (J + 1) bytes,
+    2.4 MB per series at N = 4096, J = 8; callers with large batches chunk the batch.  Caller-owned `ws` is accepted.
+    J <= 32, and no output may alias an input or another output (alpha == z included)."""
     B, N, J = _dims(U)
     q = torch.empty_like(d) if q is None else q
     if z is None:
@@ -419,6 +436,21 @@ def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None):
     _chk(t, c, U, W, d, z, q, alpha)
     _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
     _shape("z", z, (B, N)); _shape("q", q, (B, N)); _shape("alpha", alpha, (B, N))
+    if workspace or ws is not None:
+        if ws is None:
+            ws = (torch.empty((B, N, J, J), dtype=torch.float64, device=U.device),
+                  None if z is None else torch.empty((B, N, J), dtype=torch.float64, device=U.device))
+        Mws, Fws = ws
+        if (Fws is None) != (z is None):
+            raise ValueError("Invalid shape: Fws (given exactly when z is)")
+        _chk(Mws, Fws)
+        _shape("Mws", Mws, (B, N, J, J)); _shape("Fws", Fws, (B, N, J))
+        _no_alias([("q", q), ("alpha", alpha), ("Mws", Mws), ("Fws", Fws)],
+                  [("t", t), ("c", c), ("U", U), ("W", W), ("d", d), ("z", z)])
+        rc = _lib.load().c2_inverse_diag_fwd(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
+                                             _p(W), _p(d), _p(z), _p(q), _p(alpha), _p(Mws), _p(Fws), _stream())
+        _lib.check(rc, "inverse_diag")
+        return (q, (Mws, Fws)) if z is None else (q, alpha, (Mws, Fws))
     # the only aliasing the sweep allows is alpha == z (a row's z is read before its alpha is stored)
     if q.data_ptr() == d.data_ptr():
         raise ValueError("Invalid argument: q must not alias d")
@@ -430,6 +462,72 @@ def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None):
                                      _p(W), _p(d), _p(z), _p(q), _p(alpha), _stream())
     _lib.check(rc, "inverse_diag")
     return q if z is None else (q, alpha)
+
+
+def inverse_diag_rev(t, c, U, W, d, z, q, alpha, ws, bq, balpha, *, out=None):
+    """The reverse of inverse_diag (c2_inverse_diag_rev): cotangents bq (B, N) of q and balpha (B, N) of alpha ->
+    (bt (B, N), bc (B, J), bU, bW (B, N, J), bd (B, N), bz (B, N)), per series also when t or c is shared (the caller
+    sums).  q, alpha, ws: what inverse_diag(..., workspace=True) returned for the same inputs -- ws holds
+    8 B N J (J + 1) bytes, 2.4 MB per series at N = 4096, J = 8.  z, alpha, balpha and ws[1] are None together (bz is then
+    None).  `out`: the six tensors of a previous call to write into (nothing is allocated then: capturable).  J <= 32; no
+    output may alias an input or another output.  No atomics: two calls give identical bits."""
+    B, N, J = _dims(U)
+    Mws, Fws = ws
+    f64 = dict(dtype=torch.float64, device=U.device)
+    if out is None:
+        out = (torch.empty((B, N), **f64), torch.empty((B, J), **f64), torch.empty((B, N, J), **f64),
+               torch.empty((B, N, J), **f64), torch.empty((B, N), **f64), None if z is None else torch.empty((B, N), **f64))
+    bt, bc, bU, bW, bd, bz = out
+    hz = z is not None
+    for nm, v in (("alpha", alpha), ("Fws", Fws), ("balpha", balpha), ("bz", bz)):
+        if (v is not None) != hz:
+            raise ValueError("Invalid shape: %s (given exactly when z is)" % nm)
+    _chk(t, c, U, W, d, z, q, alpha, Mws, Fws, bq, balpha, bt, bc, bU, bW, bd, bz)
+    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
+    _shape("z", z, (B, N)); _shape("q", q, (B, N)); _shape("alpha", alpha, (B, N)); _shape("Mws", Mws, (B, N, J, J))
+    _shape("Fws", Fws, (B, N, J)); _shape("bq", bq, (B, N)); _shape("balpha", balpha, (B, N))
+    _shape("bt", bt, (B, N)); _shape("bc", bc, (B, J)); _shape("bU", bU, (B, N, J)); _shape("bW", bW, (B, N, J))
+    _shape("bd", bd, (B, N)); _shape("bz", bz, (B, N))
+    _no_alias([("bt", bt), ("bc", bc), ("bU", bU), ("bW", bW), ("bd", bd), ("bz", bz)],
+              [("t", t), ("c", c), ("U", U), ("W", W), ("d", d), ("z", z), ("q", q), ("alpha", alpha), ("Mws", Mws),
+               ("Fws", Fws), ("bq", bq), ("balpha", balpha)])
+    rc = _lib.load().c2_inverse_diag_rev(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
+                                         _p(W), _p(d), _p(z), _p(q), _p(alpha), _p(Mws), _p(Fws), _p(bq), _p(balpha), _p(bt),
+                                         _p(bc), _p(bU), _p(bW), _p(bd), _p(bz), _stream())
+    _lib.check(rc, "inverse_diag_rev")
+    return bt, bc, bU, bW, bd, bz
+
+
+def get_celerite_matrices_rev(ac, bc, dc, x, V, bt, bcv, ba, bU, bV, Jr, *, work=None):
+    """The reverse of get_celerite_matrices (c2_get_celerite_matrices_rev): cotangents bt (B, N), bcv (B, J), ba (B, N),
+    bU, bV (B, N, J) of (t, c, a, U, V), J = Jr + 2 Jc, and the V the forward call returned ->
+    (bar, bcr (B, Jr), bac, bbc, bcc, bdc (B, Jc), bx (B, N), bdiag (B, N)), per series also for shared coefficients.
+    ac, bc, dc (Jc,) | (B, Jc); x (N,) | (B, N).  No output aliases an input; fixed summation order."""
+    B, N, J = _dims(V)
+    Jc = ac.shape[-1]
+    if Jr + 2 * Jc != J:
+        raise ValueError("Invalid shape: V (got width %d, expected Jr + 2 Jc = %d)" % (J, Jr + 2 * Jc))
+    batched = ac.dim() == 2
+    _chk(ac, bc, dc, x, V, bt, bcv, ba, bU, bV)
+    _shape("x", x, (N,), (B, N))
+    for nm, v in (("ac", ac), ("bc", bc), ("dc", dc)):
+        _shape(nm, v, (Jc,) if not batched else (B, Jc))
+    _shape("bt", bt, (B, N)); _shape("bc", bcv, (B, J)); _shape("ba", ba, (B, N)); _shape("bU", bU, (B, N, J))
+    _shape("bV", bV, (B, N, J))
+    f64 = dict(dtype=torch.float64, device=V.device)
+    outs = [torch.empty((B, Jr), **f64), torch.empty((B, Jr), **f64)] + [torch.empty((B, Jc), **f64) for _ in range(4)] + \
+           [torch.empty((B, N), **f64) for _ in range(2)]
+    lib = _lib.load()
+    nbytes = lib.c2_get_celerite_matrices_rev_workspace_bytes(B, N, Jr, Jc)
+    if nbytes and (work is None or work.numel() * 8 < nbytes):
+        work = torch.empty(nbytes // 8, **f64)
+    optr = [_p(o if o.numel() else None) for o in outs[:6]] + [_p(o) for o in outs[6:]]
+    rc = lib.c2_get_celerite_matrices_rev(
+        _i64(B), _i64(N), _i64(Jr), _i64(Jc), _p(ac if Jc else None), _p(bc if Jc else None), _p(dc if Jc else None),
+        ctypes.c_int(1 if batched else 0), _p(x), _i64(_bs(x, N)), _p(V), _p(bt), _p(bcv), _p(ba), _p(bU), _p(bV), *optr,
+        _p(work), ctypes.c_size_t(0 if work is None else work.numel() * 8), _stream())
+    _lib.check(rc, "get_celerite_matrices_rev")
+    return tuple(outs)
 
 
 def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):

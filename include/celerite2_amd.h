@@ -439,6 +439,47 @@ int c2_inverse_diag(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_
                     const double *U, const double *W, const double *d, const double *z /* nullable */, double *q,
                     double *alpha /* nullable iff z is */, c2_stream_t stream);
 
+/* c2_inverse_diag that also stores what its reverse pass reads (the pattern of c2_factor's S): for every row n the state
+ * ENTERING it, before the row's decay is applied --
+ *   Mws (B,N,J,J): Mws[b,n,j,:] is column j of the symmetric M behind row n (zeros at n = N-1);
+ *   Fws (B,N,J), with z only: the upper solve's F behind row n, u_{n+1} alpha_{n+1} already added (zeros at n = N-1).
+ * 8 B N J (J + 1) bytes, written once: 2.4 MB per series at N = 4096, J = 8 -- callers with large batches chunk the batch.
+ * q and alpha have the bits c2_inverse_diag gives.  z, alpha, Fws are all given or all NULL.  No output may alias an
+ * input or another output (alpha == z is NOT allowed here: the reverse pass reads z).  J <= C2_FAST_WIDTH; wider models
+ * return C2_ERR_UNSUPPORTED.  No atomics, no allocation, no host read: capturable. */
+int c2_inverse_diag_fwd(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
+                        const double *U, const double *W, const double *d, const double *z /* nullable */, double *q,
+                        double *alpha /* nullable iff z is */, double *Mws, double *Fws /* nullable iff z is */,
+                        c2_stream_t stream);
+/* The reverse of c2_inverse_diag (csrc/c2_invdiag_rev.hip): cotangents bq (B,N) of q and balpha (B,N) of alpha
+ * (nullable iff z is) -> bt (B,N), bc (B,J), bU, bW (B,N,J), bd (B,N), bz (B,N; nullable iff z is), per series also when
+ * t or c is shared by the batch (the caller sums).  One upward sweep, n = 0 .. N-1, with a symmetric J x J adjoint state;
+ * q, alpha, Mws, Fws: what c2_inverse_diag_fwd returned for the same t, c, U, W, d, z.  No output may alias an input or
+ * another output.  J <= C2_FAST_WIDTH; wider models return C2_ERR_UNSUPPORTED.  Every output element has one writer: no
+ * atomics (two calls give identical bits), no allocation, no host read: capturable.  Rows of a series whose factorisation
+ * failed hold garbage (never another series'). */
+int c2_inverse_diag_rev(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
+                        const double *U, const double *W, const double *d, const double *z /* nullable */, const double *q,
+                        const double *alpha /* nullable iff z is */, const double *Mws,
+                        const double *Fws /* nullable iff z is */, const double *bq,
+                        const double *balpha /* nullable iff z is */, double *bt, double *bc, double *bU, double *bW,
+                        double *bd, double *bz /* nullable iff z is */, c2_stream_t stream);
+
+/* The reverse of c2_get_celerite_matrices (csrc/c2_terms.hip, the kernel inside c2_loglik_terms_grad): cotangents
+ * bt (B,N), bcv (B,J), ba (B,N), bU, bV (B,N,J) of (t, c, a, U, V), with J = Jr + 2 Jc and V the matrix the forward call
+ * returned (it holds the cos / sin of the phases) -> bar, bcr (B,Jr), bac, bbc, bcc, bdc (B,Jc), per series also when the
+ * coefficients are shared, bx (B,N) = bt + the phases' part, bdiag (B,N) = ba.  Sums in a fixed order: two calls give
+ * identical bits.  A handful of long series (B < 64, N >= 8192) is split over slices of the rows and needs `work` of
+ * c2_get_celerite_matrices_rev_workspace_bytes (0 otherwise; work may then be NULL).  No output may alias an input or
+ * another output.  J <= C2_FAST_WIDTH. */
+size_t c2_get_celerite_matrices_rev_workspace_bytes(int64_t B, int64_t N, int64_t Jr, int64_t Jc);
+int c2_get_celerite_matrices_rev(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ac, const double *bc,
+                                 const double *dc, int coef_batched, const double *x, int64_t x_bs, const double *V,
+                                 const double *bt, const double *bcv, const double *ba, const double *bU,
+                                 const double *bV, double *bar, double *bcr, double *bac, double *bbc, double *bcc,
+                                 double *bdc, double *bx, double *bdiag, void *work, size_t work_bytes,
+                                 c2_stream_t stream);
+
 /* Explained variance at NEW times, r[b, m] = k*_m^T (K + D)^-1 k*_m for M sorted query times ts against the matrix
  * c2_factor factored on the N sorted data times t (csrc/c2_predvar.hip): the predictive variance of the process at ts is
  * k(0) - r.  Two stream-ordered sweeps over the merge of the two grids -- the forward state of c2_factor rebuilt from d, W,

@@ -40,7 +40,7 @@ def register_table():
         name = re.sub(r"\(.*", "", name).replace("void ", "").replace("c2::invdiag::", "")
         lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (name, vg, ag, sg, lds, scratch, spill))
     lines += ["", "Largest scratch %d bytes, most spilled registers %d (to accumulation registers where scratch is 0) over %d kernels "
-              "(`group<lanes per series, with z>`)."
+              "(`group<lanes per series, with z, workspace of the reverse pass: tools/bench_loo.py>`)."
               % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows))]
     return "\n".join(lines)
 
