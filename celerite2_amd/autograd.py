@@ -9,6 +9,9 @@ the incoming cotangent.  Shared `t` (N,) / `c` (J,) receive the batch-summed gra
 `loo_log_predictive[_kernel]` is the leave-one-out log predictive density (Rasmussen & Williams 5.4.2) as a training
 objective, through `inverse_diag` and its reverse sweep (csrc/c2_invdiag_rev.hip).
 
+`predict_mean[_kernel]` is the conditional mean at new times as a differentiable function of everything it depends on,
+through `general_matmul_lower` / `general_matmul_upper` and their reverse sweep (csrc/c2_general_rev.hip).
+
 `factor`, `solve_lower`, `solve_upper`, `matmul_lower`, `matmul_upper` are the reference's five differentiable ops
 (python/celerite2/pymc/ops.py:61-141, jax/ops.py:33-172: forward = `backprop.<op>_fwd` with its workspace, gradient =
 `backprop.<op>_rev`), batched, on the device kernels -- for models that compose the ops themselves."""
@@ -18,7 +21,7 @@ import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -389,3 +392,104 @@ def loo_log_predictive_kernel(kernel, x, y, *, yerr=None, diag=None, jitter=None
     P = kernel.parameter_matrix(B)
     return _LooKernel.apply(kernel.program, yerr is not None, P, x, yerr if diag is None else diag,
                             _per_series(jitter, B, y), _per_series(mean, B, y), y)
+
+
+def _general(name):
+    fwd, rev = getattr(ops, name), getattr(ops, name + "_rev")
+
+    class _Op(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, t1, t2, c, U, V, Y):
+            args = [x.detach().contiguous() for x in (t1, t2, c, U, V, Y)]
+            Z, F = fwd(*args, workspace=True, zero_z=True)
+            ctx.save_for_backward(*args, F)
+            return Z
+
+        @staticmethod
+        def backward(ctx, bZ):
+            t1, t2, c, U, V, Y, F = ctx.saved_tensors
+            bt1, bt2, bc, bU, bV, bY = rev(t1, t2, c, U, V, Y, F, bZ.contiguous())
+            return _reduce(bt1, t1), _reduce(bt2, t2), _reduce(bc, c), bU, bV, bY
+
+    _Op.__name__ = "_" + name
+
+    def op(t1, t2, c, U, V, Y):
+        return _Op.apply(t1, t2, c, U, V, Y)
+
+    op.__name__ = name
+    op.__doc__ = ("Batched %s (B, N, nrhs): the product that carries Y (B, M, nrhs) from the grid t2 ((M,) | (B, M)) to the grid t1\n"
+                  "((N,) | (B, N)) (forward.hpp:285-392), differentiable w.r.t. (t1, t2, c, U, V, Y) -- forward with its workspace\n"
+                  "F (B, M, J, nrhs), backward c2_%s_rev (csrc/c2_general_rev.hip).  Shared t1 / t2 / c receive the batch sum.\n"
+                  "The result starts from zero (the ops layer accumulates into a caller's Z).  J <= 32." % (name, name))
+    return op
+
+
+general_matmul_lower = _general("general_matmul_lower")
+general_matmul_upper = _general("general_matmul_upper")
+
+
+class _CeleriteMatrices(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ar, ac, bc, dc, x, diag):
+        args = [v.detach().contiguous() for v in (ar, ac, bc, dc, x, diag)]
+        a, U, V = ops.get_celerite_matrices(*args)
+        ctx.save_for_backward(*args[:5], V)
+        return a, U, V
+
+    @staticmethod
+    def backward(ctx, ba, bU, bV):
+        ar, ac, bc, dc, x, V = ctx.saved_tensors
+        B, N, J = V.shape
+        zt, zc = torch.zeros((B, N), dtype=V.dtype, device=V.device), torch.zeros((B, J), dtype=V.dtype, device=V.device)
+        bar, _, bac, bbc, _, bdc, bx, bdiag = ops.get_celerite_matrices_rev(
+            ac, bc, dc, x, V, zt, zc, ba.contiguous(), bU.contiguous(), bV.contiguous(), ar.shape[-1])
+        return _reduce(bar, ar), _reduce(bac, ac), _reduce(bbc, bc), _reduce(bdc, dc), _reduce(bx, x), bdiag
+
+
+def get_celerite_matrices(ar, ac, bc, dc, x, diag):
+    """(a (B, N), U, V (B, N, J)) from the celerite coefficients ar (Jr,) | (B, Jr), ac, bc, dc (Jc,) | (B, Jc), the times
+    x (N,) | (B, N) and the diagonal diag (B, N) (ops.get_celerite_matrices), differentiable in all six
+    (c2_get_celerite_matrices_rev; shared arguments receive the batch sum).  The decay rates c = (cr, cc, cc) do not pass
+    through it: build them in torch.  The glue between `term_coefficients` and `factor` / `general_matmul_*`."""
+    return _CeleriteMatrices.apply(ar, ac, bc, dc, x, diag)
+
+
+def predict_mean(t, c, a, U, V, y, ts, Us, Vs):
+    """The conditional mean (B, M) at the sorted times ts ((M,) | (B, M)) of the process with the semiseparable matrix
+    (t, c, a, U, V) given y (B, N): K(ts, t) (K + D)^-1 y, as the chain factor -> solve_lower -> / d -> solve_upper ->
+    general_matmul_lower + general_matmul_upper of this module, differentiable in all nine arguments.  Us, Vs (B, M, J):
+    the kernel's rows at ts.  O((N + M) J^2) per series each way, no N x M array.  Raises LinAlgError when a factorisation
+    fails (as `factor`).  J <= 32."""
+    d, W = factor(t, c, a, U, V)
+    z = solve_lower(t, c, U, W, y[..., None])
+    alpha = solve_upper(t, c, U, W, z / d[..., None])
+    return (general_matmul_lower(ts, t, c, Us, V, alpha) + general_matmul_upper(ts, t, c, Vs, U, alpha))[..., 0]
+
+
+def predict_mean_kernel(kernel, x, y, t, *, yerr=None, diag=None, jitter=None, mean=None):
+    """The conditional mean (B, M) at the sorted times t ((M,) | (B, M)) given y (B, N) at x, as a differentiable function of
+    the HYPER-PARAMETERS: the arguments and conventions of `log_likelihood_kernel` (tensor parameters of `kernel`, TermExpr
+    kernels with their diagonal shift, `jitter` in quadrature, `mean` added back), differentiable in the parameters, jitter,
+    mean, y, x and t (and yerr | diag).  The composed chain term_coefficients -> get_celerite_matrices (at x and at t) ->
+    `predict_mean`; every step with a recurrence is a device kernel with its reverse.  A failed factorisation raises
+    LinAlgError.  J <= 32."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, N) is required")
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != y.shape[0]):
+        raise ValueError("Invalid shape: t (must be (M,) or (B, M))")
+    B = y.shape[0]
+    if not kernel._has_tensors():
+        raise TypeError("predict_mean_kernel: the kernel has no tensor parameter (give its parameters as device tensors)")
+    ar, cr, ac, bc, cc, dc, shift = term_coefficients(kernel.program, kernel.parameter_matrix(B), B, with_shift=True)
+    D = (yerr * yerr if diag is None else diag) + shift[:, None]
+    jitter, mean = _per_series(jitter, B, y), _per_series(mean, B, y)
+    if jitter is not None:
+        D = D + (jitter * jitter)[:, None]
+    r = y if mean is None else y - mean[:, None]
+    c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
+    a, U, V = get_celerite_matrices(ar, ac, bc, dc, x, D)
+    _, Us, Vs = get_celerite_matrices(ar, ac, bc, dc, t, torch.zeros((B, t.shape[-1]), dtype=y.dtype, device=y.device))
+    mu = predict_mean(x, c, a, U, V, r, t, Us, Vs)
+    return mu if mean is None else mu + mean[:, None]

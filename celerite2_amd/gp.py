@@ -221,6 +221,17 @@ class GaussianProcess:
         r = ops.explained_variance(self._t, ts, self._c, self._U, self._W, self._d, Us, Vs)
         return self._nan_failed(cond.mean, cond._k0() - r)
 
+    def predict_kernel(self, y, t, *, jitter=None):
+        """The conditional mean (B, M) at the sorted times `t` ((M,) shared or (B, M)), mean included, as a differentiable
+        function of the kernel's tensor hyper-parameters, of `jitter`, of a tensor `mean`, of `y` and of the times:
+        autograd.predict_mean_kernel on this GP's t, diag and mean -- to `predict(y, t)` what `log_likelihood_kernel` is to
+        `log_likelihood` (the coefficient-level chain, not the matrices `compute` factored).  J <= 32."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.predict_mean_kernel(self.kernel, self._t, y, t, diag=self._diag, jitter=jitter, mean=self.mean)
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

@@ -19,6 +19,7 @@ __all__ = [
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
     "inverse_diag", "inverse_diag_rev", "get_celerite_matrices_rev", "explained_variance", "prior_draw",
+    "general_matmul_lower_rev", "general_matmul_upper_rev",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
     "noise_mean_shift_apply", "noise_mean_shift_rev",
@@ -528,6 +529,45 @@ def get_celerite_matrices_rev(ac, bc, dc, x, V, bt, bcv, ba, bU, bV, Jr, *, work
         _p(work), ctypes.c_size_t(0 if work is None else work.numel() * 8), _stream())
     _lib.check(rc, "get_celerite_matrices_rev")
     return tuple(outs)
+
+
+def _general_rev(name):
+    def op(t1, t2, c, U, V, Y, F, bZ, *, out=None):
+        B, N, J = _dims(U)
+        if V.dim() != 3 or Y.dim() != 3:
+            raise ValueError("Invalid shape: V must be (B, M, J) and Y (B, M, nrhs)")
+        M, nrhs = V.shape[1], Y.shape[-1]
+        f64 = dict(dtype=torch.float64, device=U.device)
+        if out is None:
+            out = (torch.empty((B, N), **f64), torch.empty((B, M), **f64), torch.empty((B, J), **f64),
+                   torch.empty((B, N, J), **f64), torch.empty((B, M, J), **f64), torch.empty((B, M, nrhs), **f64))
+        bt1, bt2, bc, bU, bV, bY = out
+        _chk(t1, t2, c, U, V, Y, F, bZ, bt1, bt2, bc, bU, bV, bY)
+        _shape("t1", t1, (N,), (B, N)); _shape("t2", t2, (M,), (B, M)); _shape("c", c, (J,), (B, J))
+        _shape("V", V, (B, M, J)); _shape("Y", Y, (B, M, nrhs)); _shape("F", F, (B, M, J, nrhs))
+        _shape("bZ", bZ, (B, N, nrhs)); _shape("bt1", bt1, (B, N)); _shape("bt2", bt2, (B, M)); _shape("bc", bc, (B, J))
+        _shape("bU", bU, (B, N, J)); _shape("bV", bV, (B, M, J)); _shape("bY", bY, (B, M, nrhs))
+        _no_alias([("bt1", bt1), ("bt2", bt2), ("bc", bc), ("bU", bU), ("bV", bV), ("bY", bY)],
+                  [("t1", t1), ("t2", t2), ("c", c), ("U", U), ("V", V), ("Y", Y), ("F", F), ("bZ", bZ)])
+        rc = getattr(_lib.load(), "c2_" + name)(
+            _i64(B), _i64(N), _i64(M), _i64(J), _i64(nrhs), _p(t1), _i64(_bs(t1, N)), _p(t2), _i64(_bs(t2, M)), _p(c),
+            _i64(_bs(c, J)), _p(U), _p(V), _p(Y), _p(F), _p(bZ), _p(bt1), _p(bt2), _p(bc), _p(bU), _p(bV), _p(bY), _stream())
+        _lib.check(rc, name)
+        return bt1, bt2, bc, bU, bV, bY
+    op.__name__ = name
+    op.__doc__ = (
+        "The reverse of %s (c2_%s, csrc/c2_general_rev.hip): the cotangent bZ (B, N, nrhs) of the product ->\n"
+        "(bt1 (B, N), bt2 (B, M), bc (B, J), bU (B, N, J), bV (B, M, J), bY (B, M, nrhs)), per series also when t1, t2 or c is\n"
+        "shared (the caller sums); every element is overwritten.  F (B, M, J, nrhs): the workspace the forward call wrote for\n"
+        "the same arguments (`workspace=True`); it is read, never re-derived, and only at rows the forward absorbed.  `out`:\n"
+        "the six tensors of a previous call to write into (nothing is allocated then: capturable).  One sweep over the merge\n"
+        "of the two grids per right-hand side, O((N + M) J) each.  J <= 32; no output may alias an input or another output.\n"
+        "No atomics: two calls give identical bits." % (name[:-4], name))
+    return op
+
+
+general_matmul_lower_rev = _general_rev("general_matmul_lower_rev")
+general_matmul_upper_rev = _general_rev("general_matmul_upper_rev")
 
 
 def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):

@@ -511,6 +511,38 @@ int c2_prior_draw(int64_t B, int64_t N, int64_t M, int64_t J, int64_t K, const d
                   int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *V, const double *Us,
                   const double *Vs, const double *nt, const double *ns, double *ft, double *fs, c2_stream_t stream);
 
+/* The reverse of c2_general_matmul_lower / _upper (csrc/c2_general_rev.hip): the cotangent bZ (B,N,nrhs) of Z ->
+ * bt1 (B,N), bt2 (B,M), bc (B,J), bU (B,N,J), bV (B,M,J), bY (B,M,nrhs), per series also when t1, t2 or c is shared by the
+ * batch (the caller sums); every element is overwritten.  No counterpart in the reference, whose backprop.cpp exports the
+ * forward with its workspace and no reverse; parity is pinned by dense algebra.
+ * Walk coordinates: position s = 0 .. M-1 along t2 and q = 0 .. N-1 along t1, with walk time tau = t and array row =
+ * position (lower), tau = -t and array row = M-1-s / N-1-q (upper).  THE TIE RULE is the forward's: row s feeds output q
+ * iff tau2[s] <= tau1[q] (lower) / tau2[s] < tau1[q] (upper); s(q) is the last position that feeds q.  Forward:
+ *   F_0 = V_0^T Y_0,  F_s = p_s o F_{s-1} + V_s^T Y_s,  p_s = exp(-c (tau2[s] - tau2[s-1]));
+ *   Z_q += (U_q o e_q) F_{s(q)},  e_q = exp(-c (tau1[q] - tau2[s(q)]))     (nothing if no row feeds q).
+ * Reverse, with G = 0 (J x nrhs), walking the events backwards from the last position the forward absorbed:
+ *   output q (s(q) = s):  bU_q = e_q o (F_s bZ_q),  bc -= (tau1[q] - tau2[s]) U_q o bU_q,  G += (U_q o e_q)^T bZ_q;
+ *   row s:  bV_s = G Y_s,  bY_s = V_s G,  and for s >= 1  bc -= (tau2[s] - tau2[s-1]) rowsum(G o (F_s - V_s^T Y_s)),  G <- p_s o G;
+ *   bt1_q = -+ c . (U_q o bU_q),  bt2_s = +- c . (V_s o bV_s)             (upper sign: lower variant).
+ * bc is summed event by event from these non-negative lags (it does not cancel for times with a large offset).  Outputs
+ * that no row feeds, and t2 rows behind the last output (never absorbed), get exact zeros.
+ * THE WORKSPACE CONTRACT: F (B,M,J,nrhs) is what the forward call wrote for the same arguments (F != NULL there), by any of
+ * its kernels.  It is read, never re-derived, and only at the rows the forward absorbed behind its start row: the start
+ * row (array row 0, lower; M-1, upper, which the forward never writes) is formed from V and Y, and rows never absorbed may
+ * hold anything.  No output may alias an input or another output.  J <= C2_FAST_WIDTH; wider models return
+ * C2_ERR_UNSUPPORTED.  One launch per right-hand side on `stream`, each adding to what the one before wrote: a fixed
+ * order, no atomics (two calls give identical bits), no allocation, no host read: capturable. */
+int c2_general_matmul_lower_rev(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1,
+                                int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c, int64_t c_bs,
+                                const double *U, const double *V, const double *Y, const double *F, const double *bZ,
+                                double *bt1, double *bt2, double *bc, double *bU, double *bV, double *bY,
+                                c2_stream_t stream);
+int c2_general_matmul_upper_rev(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nrhs, const double *t1,
+                                int64_t t1_bs, const double *t2, int64_t t2_bs, const double *c, int64_t c_bs,
+                                const double *U, const double *V, const double *Y, const double *F, const double *bZ,
+                                double *bt1, double *bt2, double *bc, double *bU, double *bV, double *bY,
+                                c2_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * HOST entry points (B == 1, synchronous) -- what celerite2.driver /
  * celerite2.backprop bind.  Same argument meaning as the pybind11 functions of
