@@ -18,6 +18,10 @@
  *     device's default pool, which the process shares with everybody else, is
  *     never reconfigured.  The c2h_* host entry points keep one staging arena,
  *     pinned bounce buffer and stream PER CALLING THREAD (re-entrant).
+ *   - Alignment: every double* argument -- input, output or workspace -- is
+ *     8-byte aligned, and that is all an entry point asks for: 16-byte
+ *     alignment selects faster kernels and never changes results beyond
+ *     rounding (a view that starts at an odd element is a valid argument).
  *   - Exact-pointer aliasing the reference allows is allowed here too:
  *     d == a and W == V for factor (forward.hpp:55-58), Z == Y for
  *     solve_* / matmul_* (numpy.py:95-108).
