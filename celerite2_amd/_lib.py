@@ -28,6 +28,7 @@ SYMBOLS = [
     "c2_prior_draw", "c2_inverse_diag_fwd", "c2_inverse_diag_rev",
     "c2_get_celerite_matrices_rev_workspace_bytes", "c2_get_celerite_matrices_rev",
     "c2_general_matmul_lower_rev", "c2_general_matmul_upper_rev",
+    "c2_explained_variance_fwd", "c2_explained_variance_rev",
     "c2h_factor", "c2h_solve_lower", "c2h_solve_upper", "c2h_matmul_lower", "c2h_matmul_upper",
     "c2h_general_matmul_lower", "c2h_general_matmul_upper", "c2h_factor_rev",
     "c2h_solve_lower_rev", "c2h_solve_upper_rev", "c2h_matmul_lower_rev", "c2h_matmul_upper_rev",

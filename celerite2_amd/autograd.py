@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -493,3 +493,118 @@ def predict_mean_kernel(kernel, x, y, t, *, yerr=None, diag=None, jitter=None, m
     _, Us, Vs = get_celerite_matrices(ar, ac, bc, dc, t, torch.zeros((B, t.shape[-1]), dtype=y.dtype, device=y.device))
     mu = predict_mean(x, c, a, U, V, r, t, Us, Vs)
     return mu if mean is None else mu + mean[:, None]
+
+
+class _ExplainedVariance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, ts, c, U, W, d, Us, Vs):
+        args = [x.detach().contiguous() for x in (t, ts, c, U, W, d, Us, Vs)]
+        work = torch.empty_like(args[6])
+        r, (Sws, Rws) = ops.explained_variance(*args, work=work, workspace=True)
+        ctx.save_for_backward(*args, work, Sws, Rws)
+        return r
+
+    @staticmethod
+    def backward(ctx, br):
+        t, ts, c, U, W, d, Us, Vs, work, Sws, Rws = ctx.saved_tensors
+        bt, bts, bc, bU, bW, bd, bUs, bVs = ops.explained_variance_rev(t, ts, c, U, W, d, Us, Vs, work, (Sws, Rws), br.contiguous())
+        return _reduce(bt, t), _reduce(bts, ts), _reduce(bc, c), bU, bW, bd, bUs, bVs
+
+
+def explained_variance(t, ts, c, U, W, d, Us, Vs):
+    """r (B, M) = diag(K*^T (K + D)^-1 K*) at the sorted times ts ((M,) | (B, M)) from the factors (d, W) on t, differentiable
+    in all eight arguments (c2_explained_variance_fwd forward, c2_explained_variance_rev backward, csrc/c2_predvar_rev.hip;
+    shared t / ts / c receive the batch sum).  Composes with `factor`.  The forward call keeps 16 B N J^2 bytes for the
+    backward pass: 4.2 MB per series at N = 4096, J = 8 -- chunk large batches.  J <= 32."""
+    return _ExplainedVariance.apply(t, ts, c, U, W, d, Us, Vs)
+
+
+def predict_variance(t, c, a, U, V, ts, Us, Vs, k0):
+    """The conditional variance (B, M) at the sorted times ts ((M,) | (B, M)) of the process with the semiseparable matrix
+    (t, c, a, U, V): k0 - K(ts, t) (K + D)^-1 K(t, ts) on the diagonal, as the chain factor -> explained_variance of this
+    module, differentiable in all nine arguments.  k0 (B,) | float: the kernel at lag 0.  Us, Vs (B, M, J): the kernel's rows at
+    ts.  O((N + M) J^2) per series each way, no N x M array.  Raises LinAlgError when a factorisation fails (as `factor`).
+    Workspace: see `explained_variance`.  J <= 32."""
+    d, W = factor(t, c, a, U, V)
+    r = explained_variance(t, ts, c, U, W, d, Us, Vs)
+    return (k0[:, None] if torch.is_tensor(k0) and k0.dim() == 1 else k0) - r
+
+
+def _log_density(ys, mu, var):
+    return -0.5 * ((ys - mu) ** 2 / var + torch.log(var)).sum(dim=1) - 0.5 * ys.shape[1] * math.log(2.0 * math.pi)
+
+
+def predictive_log_density(t, c, a, U, V, y, ts, Us, Vs, k0, ys, vars=None):
+    """The held-out log predictive density (B,): sum_m log N(ys_m | mu_m, k0 - r_m + vars_m) with mu = `predict_mean` and
+    k0 - r = `predict_variance` at the sorted times ts, ys (B, M) the held-out values and vars (B, M) | None their noise
+    variances -- differentiable in every tensor argument.  The objective itself is plain torch on (B, M) arrays.  Raises
+    LinAlgError when a factorisation fails.  J <= 32."""
+    mu = predict_mean(t, c, a, U, V, y, ts, Us, Vs)
+    var = predict_variance(t, c, a, U, V, ts, Us, Vs, k0)
+    return _log_density(ys, mu, var if vars is None else var + vars)
+
+
+def _has_convolution(kernel):
+    """Is there a TermConvolution anywhere in the kernel's tree?"""
+    from .terms import TermConvolution
+    if isinstance(kernel, TermConvolution):
+        return True
+    kids = list(getattr(kernel, "terms", None) or []) + [getattr(kernel, nm, None) for nm in ("term", "term1", "term2")]
+    return any(_has_convolution(k) for k in kids if k is not None)
+
+
+def _predict_chain(name, kernel, x, y, t, yerr, diag, jitter, mean):
+    """predict_mean_kernel's conventions: (c, a, U, V, r, Us, Vs, k0, jitter, mean) of the coefficient-level chain."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, N) is required")
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != y.shape[0]):
+        raise ValueError("Invalid shape: t (must be (M,) or (B, M))")
+    if _has_convolution(kernel):
+        raise ValueError("%s does not take a kernel with a TermConvolution in it (not semiseparable inside the exposure "
+                         "window): use predict(y, t, return_var=True)" % name)
+    B = y.shape[0]
+    if not kernel._has_tensors():
+        raise TypeError("%s: the kernel has no tensor parameter (give its parameters as device tensors)" % name)
+    ar, cr, ac, bc, cc, dc, shift = term_coefficients(kernel.program, kernel.parameter_matrix(B), B, with_shift=True)
+    D = (yerr * yerr if diag is None else diag) + shift[:, None]
+    jitter, mean = _per_series(jitter, B, y), _per_series(mean, B, y)
+    if jitter is not None:
+        D = D + (jitter * jitter)[:, None]
+    r = y if mean is None else y - mean[:, None]
+    c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
+    a, U, V = get_celerite_matrices(ar, ac, bc, dc, x, D)
+    _, Us, Vs = get_celerite_matrices(ar, ac, bc, dc, t, torch.zeros((B, t.shape[-1]), dtype=y.dtype, device=y.device))
+    k0 = ar.sum(dim=-1) + ac.sum(dim=-1)
+    return c, a, U, V, r, Us, Vs, k0, jitter, mean
+
+
+def predict_variance_kernel(kernel, x, y, t, *, yerr=None, diag=None, jitter=None, mean=None):
+    """The conditional variance (B, M) of the process at the sorted times t ((M,) | (B, M)) as a differentiable function of
+    the HYPER-PARAMETERS, `predict_mean_kernel`'s arguments and chain with `predict_variance` at its end (y and mean only
+    give the batch size: the variance does not depend on them)."""
+    c, a, U, V, _, Us, Vs, k0, _, _ = _predict_chain("predict_variance_kernel", kernel, x, y, t, yerr, diag, jitter, mean)
+    return predict_variance(x, c, a, U, V, t, Us, Vs, k0)
+
+
+def predictive_log_density_kernel(kernel, x, y, t, ys, *, yerr=None, diag=None, jitter=None, mean=None, yerr_new=None):
+    """The held-out log predictive density (B,), sum_m log N(ys_m | mu_m, var_m + yerr_new_m^2 + jitter^2), of the values
+    ys (B, M) at the sorted times t ((M,) | (B, M)) given y (B, N) at x, as a differentiable function of the
+    HYPER-PARAMETERS: the arguments and conventions of `predict_mean_kernel` (tensor parameters of `kernel`, `jitter` in
+    quadrature, `mean`), the queries' own noise yerr_new (B, M) | None with the same jitter added in quadrature (or none).
+    Differentiable in the parameters, jitter, mean, y, ys, x and t (and yerr | diag, yerr_new).  The chain
+    term_coefficients -> get_celerite_matrices (at x and at t) -> `predict_mean` and `predict_variance` -> the objective in
+    torch; every step with a recurrence is a device kernel with its reverse, the reverse of the explained variance among
+    them (csrc/c2_predvar_rev.hip).  A failed factorisation raises LinAlgError.  A kernel with a TermConvolution anywhere in
+    it is refused: use predict(y, t, return_var=True).  Workspace: see `explained_variance`.  J <= 32."""
+    if ys.dim() != 2 or ys.shape[0] != y.shape[0] or ys.shape[1] != t.shape[-1]:
+        raise ValueError("Invalid shape: ys (must be (B, M))")
+    c, a, U, V, r, Us, Vs, k0, jitter, mean = _predict_chain("predictive_log_density_kernel", kernel, x, y, t, yerr, diag,
+                                                               jitter, mean)
+    noise = None if yerr_new is None else yerr_new * yerr_new
+    if jitter is not None:
+        j2 = (jitter * jitter)[:, None]
+        noise = j2 if noise is None else noise + j2
+    rs = ys if mean is None else ys - mean[:, None]
+    return predictive_log_density(x, c, a, U, V, r, t, Us, Vs, k0, rs, noise)

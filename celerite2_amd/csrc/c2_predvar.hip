@@ -44,13 +44,15 @@ namespace predvar {
 // DA, DB: the two rows of a data point (forward: W, W; backward: W, U).  QA, QB: those of a query (forward: Us, Vs;
 // backward: X, X).  Forward writes r and X; backward reads a query's r_m eight positions ahead with its row (the d slot of
 // the ring, which a query does not otherwise use) and stores r_m plus its own term: every r_m is read before it is written.
-template <int G, bool BACK>
+// WS (c2_explained_variance_fwd): a data event also stores the state AFTER its update -- column j of S'_n (forward) / of R_n
+// (backward) into ws[b, n, j, :], lane j its own J consecutive doubles: what c2_explained_variance_rev reads.
+template <int G, bool BACK, bool WS = false>
 __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int J, const double *__restrict__ t, int64_t t_bs,
                                                    const double *__restrict__ ts, int64_t ts_bs,
                                                    const double *__restrict__ c, int64_t c_bs,
                                                    const double *__restrict__ d, const double *__restrict__ DA,
                                                    const double *__restrict__ DB, const double *QA, const double *QB,
-                                                   double *r, double *X) {
+                                                   double *r, double *X, double *__restrict__ ws = nullptr) {
   constexpr int SPW = kWave / G, RD = kRing, PD = kPend, NS = kSlots;
   using Lay = RingLayout<G, 2, 0, 4>;   // scalars: time and d; the four vectors below
   constexpr int RS = Lay::kStride;
@@ -182,6 +184,14 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
         for (int i = 0; i < G; ++i) pin(St[i]);
         if (isq && L.valid && j == 0) rb[rowM(m)] = dslot + s;   // (its forward part came through the ring: no load to wait for)
       }
+      if constexpr (WS) {
+        if (isd && L.valid && act) {
+          double *sw = ws + ((L.b * N + rowN(n)) * J + j) * J;
+#pragma unroll
+          for (int i = 0; i < G; ++i)
+            if (i < J) sw[i] = St[i];
+        }
+      }
       lds_order();   // (the next event overwrites the vectors)
       tref = isd ? tn : tref;
       n += isd ? 1 : 0;
@@ -192,14 +202,25 @@ __global__ __launch_bounds__(kWave) void k_predvar(int64_t B, int N, int M, int 
 }
 
 template <int G>
+inline void launch_ws(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts, int64_t ts_bs,
+                      const double *c, int64_t c_bs, const double *U, const double *W, const double *d, const double *Us,
+                      const double *Vs, double *r, double *work, double *Sws, double *Rws, hipStream_t s) {
+  const dim3 grid((unsigned)((B * G + kWave - 1) / kWave));
+  hipLaunchKernelGGL((k_predvar<G, false, true>), grid, dim3(kWave), 0, s, B, (int)N, (int)M, (int)J, t, t_bs, ts, ts_bs, c, c_bs,
+                     d, W, W, Us, Vs, r, work, Sws);
+  hipLaunchKernelGGL((k_predvar<G, true, true>), grid, dim3(kWave), 0, s, B, (int)N, (int)M, (int)J, t, t_bs, ts, ts_bs, c, c_bs,
+                     d, W, U, (const double *)work, (const double *)work, r, (double *)nullptr, Rws);
+}
+
+template <int G>
 inline void launch(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts, int64_t ts_bs,
                    const double *c, int64_t c_bs, const double *U, const double *W, const double *d, const double *Us,
                    const double *Vs, double *r, double *work, hipStream_t s) {
   const dim3 grid((unsigned)((B * G + kWave - 1) / kWave));
   hipLaunchKernelGGL((k_predvar<G, false>), grid, dim3(kWave), 0, s, B, (int)N, (int)M, (int)J, t, t_bs, ts, ts_bs, c, c_bs, d,
-                     W, W, Us, Vs, r, work);
+                     W, W, Us, Vs, r, work, (double *)nullptr);
   hipLaunchKernelGGL((k_predvar<G, true>), grid, dim3(kWave), 0, s, B, (int)N, (int)M, (int)J, t, t_bs, ts, ts_bs, c, c_bs, d,
-                     W, U, (const double *)work, (const double *)work, r, (double *)nullptr);
+                     W, U, (const double *)work, (const double *)work, r, (double *)nullptr, (double *)nullptr);
 }
 
 }  // namespace predvar
@@ -218,5 +239,20 @@ extern "C" int c2_explained_variance(int64_t B, int64_t N, int64_t M, int64_t J,
   if (N + M > 0x7ffffff0LL || (B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   dispatch_group(J, [&](auto g) { launch<decltype(g)::value>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, s); });
+  return launch_ok();
+}
+
+extern "C" int c2_explained_variance_fwd(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs,
+                                         const double *ts, int64_t ts_bs, const double *c, int64_t c_bs, const double *U,
+                                         const double *W, const double *d, const double *Us, const double *Vs, double *r,
+                                         double *work, double *Sws, double *Rws, c2_stream_t stream) {
+  if (B < 1 || N < 1 || M < 1 || J < 1) return C2_ERR_INVALID;
+  if (J > C2_FAST_WIDTH) return C2_ERR_UNSUPPORTED;
+  if (!t || !ts || !c || !U || !W || !d || !Us || !Vs || !r || !work || !Sws || !Rws) return C2_ERR_INVALID;
+  if (N + M > 0x7ffffff0LL || (B * group_size(J) + kWave - 1) / kWave > 0x7fffffffLL) return C2_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  dispatch_group(J, [&](auto g) {
+    launch_ws<decltype(g)::value>(B, N, M, J, t, t_bs, ts, ts_bs, c, c_bs, U, W, d, Us, Vs, r, work, Sws, Rws, s);
+  });
   return launch_ok();
 }

@@ -232,6 +232,28 @@ class GaussianProcess:
         self._check_vector(y)
         return autograd.predict_mean_kernel(self.kernel, self._t, y, t, diag=self._diag, jitter=jitter, mean=self.mean)
 
+    def predict_variance_kernel(self, y, t, *, jitter=None):
+        """The conditional variance (B, M) at the sorted times `t` ((M,) shared or (B, M)) as a differentiable function of
+        the kernel's tensor hyper-parameters, of `jitter` and of the times: autograd.predict_variance_kernel on this GP's
+        t and diag -- to `predict_at(y, t, return_var=True)[1]` what `predict_kernel` is to its mean.  J <= 32."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.predict_variance_kernel(self.kernel, self._t, y, t, diag=self._diag, jitter=jitter, mean=self.mean)
+
+    def predictive_log_density_kernel(self, y, t, ys, *, jitter=None, yerr_new=None):
+        """The held-out log predictive density (B,) of the values `ys` (B, M) at the sorted times `t` given `y`, as a
+        differentiable function of the kernel's tensor hyper-parameters, of `jitter`, of a tensor `mean`, of `y`, `ys` and
+        the times: autograd.predictive_log_density_kernel on this GP's t, diag and mean.  `yerr_new` (B, M): the noise of
+        the held-out values (jitter is added to it in quadrature).  J <= 32."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.predictive_log_density_kernel(self.kernel, self._t, y, t, ys, diag=self._diag, jitter=jitter,
+                                                      mean=self.mean, yerr_new=yerr_new)
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

@@ -18,7 +18,7 @@ __all__ = [
     "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "general_matmul_lower",
     "general_matmul_upper", "factor_rev", "solve_lower_rev", "solve_upper_rev", "matmul_lower_rev",
     "matmul_upper_rev", "get_celerite_matrices", "kernel_values", "colsumsq_over_d", "loglik", "loglik_grad", "loglik_grad_workspace", "condition", "dot_tril",
-    "inverse_diag", "inverse_diag_rev", "get_celerite_matrices_rev", "explained_variance", "prior_draw",
+    "inverse_diag", "inverse_diag_rev", "get_celerite_matrices_rev", "explained_variance", "explained_variance_rev", "prior_draw",
     "general_matmul_lower_rev", "general_matmul_upper_rev",
     "kron_loglik", "kron_loglik_grad", "loglik_terms", "loglik_terms_grad",
     "TermProgram", "TermExpr", "term_coefficients", "term_coefficients_rev", "noise_mean_apply", "noise_mean_rev",
@@ -570,22 +570,44 @@ general_matmul_lower_rev = _general_rev("general_matmul_lower_rev")
 general_matmul_upper_rev = _general_rev("general_matmul_upper_rev")
 
 
-def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):
+def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None, workspace=False, ws=None):
     """r (B, M) = diag(K*^T (K + D)^-1 K*) at the M sorted query times `ts` ((M,) shared or (B, M)) against the factored
     matrix K + D = L diag(d) L^T on the data times `t`: the predictive variance at `ts` is k(0) - r.  Two sweeps over the
     merge of the two grids (c2_explained_variance), O((N + M) J^2) per series, no N x M array.  Us, Vs (B, M, J): the
     kernel's U and V rows at the queries.  Caller-owned `out` (B, M) and `work` (B, M, J) are accepted (nothing is
-    allocated then: capturable in a HIP graph); neither may alias an input or the other.  J <= 32."""
+    allocated then: capturable in a HIP graph); neither may alias an input or the other.  J <= 32.
+
+    `workspace=True` (c2_explained_variance_fwd): the same r and work, bit for bit, and the states explained_variance_rev
+    reads -- returns (r, ws) with ws = (Sws, Rws), both (B, N, J, J), the forward and the backward state after every data
+    row: 16 B N J^2 bytes, 4.2 MB per series at N = 4096, J = 8; callers with large batches chunk the batch.  A caller-owned
+    `ws` is accepted.  The reverse also reads `work`: pass it in to keep it."""
     B, N, J = _dims(U)
     if Us.dim() != 3:
         raise ValueError("Invalid shape: Us (must be (B, M, J))")
     M = Us.shape[1]
-    out = torch.empty((B, M), dtype=torch.float64, device=U.device) if out is None else out
-    work = torch.empty((B, M, J), dtype=torch.float64, device=U.device) if work is None else work
-    _chk(t, ts, c, U, W, d, Us, Vs, out, work)
+    f64 = dict(dtype=torch.float64, device=U.device)
+    out = torch.empty((B, M), **f64) if out is None else out
+    with_ws = workspace or ws is not None
+    if ws is not None:
+        Sws, Rws = ws
+    elif with_ws:
+        Sws, Rws = torch.empty((B, N, J, J), **f64), torch.empty((B, N, J, J), **f64)
+    else:
+        Sws = Rws = None
+    work = torch.empty((B, M, J), **f64) if work is None else work
+    _chk(t, ts, c, U, W, d, Us, Vs, out, work, Sws, Rws)
     _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J))
     _shape("W", W, (B, N, J)); _shape("d", d, (B, N)); _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J))
     _shape("out", out, (B, M)); _shape("work", work, (B, M, J))
+    if with_ws:
+        _shape("Sws", Sws, (B, N, J, J)); _shape("Rws", Rws, (B, N, J, J))
+        _no_alias([("out", out), ("work", work), ("Sws", Sws), ("Rws", Rws)],
+                  [("t", t), ("ts", ts), ("c", c), ("U", U), ("W", W), ("d", d), ("Us", Us), ("Vs", Vs)])
+        rc = _lib.load().c2_explained_variance_fwd(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts),
+                                                   _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(W), _p(d), _p(Us),
+                                                   _p(Vs), _p(out), _p(work), _p(Sws), _p(Rws), _stream())
+        _lib.check(rc, "explained_variance")
+        return out, (Sws, Rws)
     inputs = [x.data_ptr() for x in (t, ts, c, U, W, d, Us, Vs)]
     if out.data_ptr() in inputs or out.data_ptr() == work.data_ptr():
         raise ValueError("Invalid argument: out must not alias an input or work")
@@ -596,6 +618,43 @@ def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None):
                                            _p(out), _p(work), _stream())
     _lib.check(rc, "explained_variance")
     return out
+
+
+def explained_variance_rev(t, ts, c, U, W, d, Us, Vs, work, ws, br, *, out=None):
+    """The reverse of explained_variance (c2_explained_variance_rev, csrc/c2_predvar_rev.hip): the cotangent br (B, M) of r ->
+    (bt (B, N), bts (B, M), bc (B, J), bU, bW (B, N, J), bd (B, N), bUs, bVs (B, M, J)), per series also when t, ts or c is
+    shared (the caller sums); every element is overwritten.  work (B, M, J) and ws = (Sws, Rws) (B, N, J, J): what
+    explained_variance(..., work=work, workspace=True) wrote and returned for the same inputs --
+    16 B N J^2 bytes, 4.2 MB per series at N = 4096, J = 8; the states are read, never re-derived.  `out`: the eight tensors
+    of a previous call to write into (nothing is allocated then: capturable).  Two sweeps over the merge of the two grids,
+    O((N + M) J^2) per series.  J <= 32; no output may alias an input or another output.  No atomics: two calls give
+    identical bits."""
+    B, N, J = _dims(U)
+    if Us.dim() != 3:
+        raise ValueError("Invalid shape: Us (must be (B, M, J))")
+    M = Us.shape[1]
+    Sws, Rws = ws
+    f64 = dict(dtype=torch.float64, device=U.device)
+    if out is None:
+        out = (torch.empty((B, N), **f64), torch.empty((B, M), **f64), torch.empty((B, J), **f64), torch.empty((B, N, J), **f64),
+               torch.empty((B, N, J), **f64), torch.empty((B, N), **f64), torch.empty((B, M, J), **f64),
+               torch.empty((B, M, J), **f64))
+    bt, bts, bc, bU, bW, bd, bUs, bVs = out
+    _chk(t, ts, c, U, W, d, Us, Vs, work, Sws, Rws, br, *out)
+    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J))
+    _shape("W", W, (B, N, J)); _shape("d", d, (B, N)); _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J))
+    _shape("work", work, (B, M, J)); _shape("Sws", Sws, (B, N, J, J)); _shape("Rws", Rws, (B, N, J, J)); _shape("br", br, (B, M))
+    _shape("bt", bt, (B, N)); _shape("bts", bts, (B, M)); _shape("bc", bc, (B, J)); _shape("bU", bU, (B, N, J))
+    _shape("bW", bW, (B, N, J)); _shape("bd", bd, (B, N)); _shape("bUs", bUs, (B, M, J)); _shape("bVs", bVs, (B, M, J))
+    _no_alias([("bt", bt), ("bts", bts), ("bc", bc), ("bU", bU), ("bW", bW), ("bd", bd), ("bUs", bUs), ("bVs", bVs)],
+              [("t", t), ("ts", ts), ("c", c), ("U", U), ("W", W), ("d", d), ("Us", Us), ("Vs", Vs), ("work", work),
+               ("Sws", Sws), ("Rws", Rws), ("br", br)])
+    rc = _lib.load().c2_explained_variance_rev(
+        _i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts), _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U),
+        _p(W), _p(d), _p(Us), _p(Vs), _p(work), _p(Sws), _p(Rws), _p(br), _p(bt), _p(bts), _p(bc), _p(bU), _p(bW), _p(bd),
+        _p(bUs), _p(bVs), _stream())
+    _lib.check(rc, "explained_variance_rev")
+    return bt, bts, bc, bU, bW, bd, bUs, bVs
 
 
 def prior_draw(t, ts, c, U, V, Us, Vs, nt, ns, *, ft=None, fs=None):

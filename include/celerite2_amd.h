@@ -499,6 +499,45 @@ int c2_explained_variance(int64_t B, int64_t N, int64_t M, int64_t J, const doub
                           int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *W, const double *d,
                           const double *Us, const double *Vs, double *r, double *work, c2_stream_t stream);
 
+/* c2_explained_variance that also stores what its reverse pass reads: for every data row n the state AFTER its update --
+ *   Sws (B,N,J,J): Sws[b,n,j,:] is column j of the forward state S'_n (the S of c2_factor after row n);
+ *   Rws (B,N,J,J): Rws[b,n,j,:] is column j of the backward state R_n (the M of c2_inverse_diag after row n).
+ * 16 B N J^2 bytes, written once: 4.2 MB per series at N = 4096, J = 8 -- callers with large batches chunk the batch.
+ * r and work have the bits c2_explained_variance gives.  No output may alias an input or another output.
+ * J <= C2_FAST_WIDTH; wider models return C2_ERR_UNSUPPORTED.  No atomics, no allocation, no host read: capturable. */
+int c2_explained_variance_fwd(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts,
+                              int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *W,
+                              const double *d, const double *Us, const double *Vs, double *r, double *work, double *Sws,
+                              double *Rws, c2_stream_t stream);
+/* The reverse of c2_explained_variance (csrc/c2_predvar_rev.hip): the cotangent br (B,M) of r -> bt (B,N), bts (B,M),
+ * bc (B,J), bU, bW (B,N,J), bd (B,N), bUs, bVs (B,M,J), per series also when t, ts or c is shared by the batch (the caller
+ * sums); every element is overwritten.  work, Sws, Rws: what c2_explained_variance_fwd wrote for the same arguments; the
+ * states are read, never re-derived.  With n(m) the last data row with t_n <= s_m (-1 in front of the data), two
+ * stream-ordered launches over the merge of the two grids:
+ *   pass A walks upwards with the adjoint Rb = 0 of the backward state (a query before the data row above it):
+ *     query m, n(m) = n-1:  lag = t_n - s, eps = exp(-c lag), x = eps o X_m;  Rb += br_m x x^T;  bx = 2 br_m R_n x;
+ *                           bVs_m = eps o bx;  k = x o bx;  bc -= lag k;  bt_n -= c.k;  bts_m += c.k
+ *     data n:  p = exp(-c (t_{n+1} - t_n)), G = (p p^T) o R_{n+1} (n = N-1: G = 0, p = 1);  g = G w;  q = 1/d_n + w.g;
+ *              Mu = Rb u;  qb = u.Mu;  gb = -2 Mu + qb w;  bU_n = -2 Rb g + 2 q Mu;  bd_n = -qb / d_n^2;  bW_n = qb g + G gb;
+ *              Gb = Rb + (gb w^T + w gb^T) / 2;  n < N-1: pb = 2 (Gb o R_{n+1}) p, k = pb o p, bc -= (t_{n+1} - t_n) k,
+ *              bt_{n+1} -= c.k, bt_n += c.k;  Rb <- (p p^T) o Gb
+ *   pass B walks downwards with the adjoint Sb = 0 of the forward state (a query before the data row below it) and adds to
+ *   what pass A wrote:
+ *     query m, n(m) = n >= 0:  lag = s - t_n, e = exp(-c lag), uL = u* o e, h = S'_n uL, bX = bVs_m;
+ *                              bh = br_m uL - e o bX;  be = -h o bX;  buL = br_m h + S'_n bh;  Sb += (bh uL^T + uL bh^T) / 2;
+ *                              bUs_m = e o buL;  be += u* o buL;  k = e o be;  bc -= lag k;  bts_m -= c.k;  bt_n += c.k
+ *     data n:  bd_n += w^T Sb w;  bW_n += 2 d_n Sb w;  n > 0: p = exp(-c (t_n - t_{n-1})), pb = 2 (Sb o S'_{n-1}) p,
+ *              k = pb o p, bc -= (t_n - t_{n-1}) k, bt_n -= c.k, bt_{n-1} += c.k, Sb <- (p p^T) o Sb
+ * Queries with no data row above them get bVs = 0 exactly, queries in front of the data bUs = 0 exactly.  bc is summed
+ * event by event from these non-negative lags.  No output may alias an input or another output.  J <= C2_FAST_WIDTH; wider
+ * models return C2_ERR_UNSUPPORTED.  A fixed order, no atomics (two calls give identical bits), no allocation, no host
+ * read: capturable.  Rows of a series whose factorisation failed hold garbage (never another series'). */
+int c2_explained_variance_rev(int64_t B, int64_t N, int64_t M, int64_t J, const double *t, int64_t t_bs, const double *ts,
+                              int64_t ts_bs, const double *c, int64_t c_bs, const double *U, const double *W,
+                              const double *d, const double *Us, const double *Vs, const double *work, const double *Sws,
+                              const double *Rws, const double *br, double *bt, double *bts, double *bc, double *bU,
+                              double *bW, double *bd, double *bUs, double *bVs, c2_stream_t stream);
+
 /* Joint draw of the NOISE-FREE prior process on the merge of the N sorted data times t and the M sorted query times ts
  * (csrc/c2_priordraw.hip): ft (B,N,K) and fs (B,M,K) = the Cholesky factor of the zero-noise kernel matrix on the merged
  * grid (data first on a tie) applied to the standard normals nt (B,N,K), ns (B,M,K) -- K independent draws per series.
