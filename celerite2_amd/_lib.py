@@ -6,12 +6,65 @@ visible, the product path raises -- it never routes through oracle/.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.so"))  # override: A/B builds
+# override: A/B builds.  Whatever library is chosen, it is bound with THIS tree's header (the ABI of an A/B pair is one).
+LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.so"))
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # = build.INCLUDE: the build is in-tree
 
-C2_OK, C2_ERR_INVALID, C2_ERR_UNSUPPORTED, C2_ERR_HIP = 0, -1, -2, -3
-C2_MAX_WIDTH = 128
+
+class BackendError(RuntimeError):
+    pass
+
+
+class Pointer(ctypes.c_void_p):
+    """Every pointer parameter of the header except `const char *`: a tensor (anything with .data_ptr()), None, an int,
+    a c_void_p, byref(...) or ndarray.ctypes.data_as(c_void_p) -- but no str / bytes, which c_void_p would take."""
+
+    @classmethod
+    def from_param(cls, x, _void_p=ctypes.c_void_p):
+        if x is None or type(x) is _void_p:
+            return x
+        try:
+            return _void_p(x.data_ptr())
+        except AttributeError:
+            if isinstance(x, (str, bytes)):
+                raise TypeError("a pointer argument, not %s" % type(x).__name__)
+            return _void_p.from_param(x)
+
+
+# The C types of the header's prototypes (parameters and return values).  A prototype that uses another one fails at load.
+_CTYPES = {"void": None, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+_CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const int32_t *", "int *", "int64_t *", "void *",
+                              "c2_stream_t", "const char **", "const c2_term_program *", "const c2_term_expr *"), Pointer))
+
+
+def _header():
+    """include/celerite2_amd.h without its comments."""
+    if not os.path.exists(HEADER):
+        raise BackendError("celerite2_amd: %s not found -- the Python binding takes its prototypes from it" % HEADER)
+    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+
+
+def _ctype(text, name):
+    text = " ".join(text.replace("*", " * ").split()).replace("* *", "**")
+    if text not in _CTYPES:
+        raise BackendError("celerite2_amd: %s: no ctypes type for %r (celerite2_amd/_lib.py, _CTYPES)" % (name, text))
+    return _CTYPES[text]
+
+
+def _prototypes(header):
+    """name -> (restype, argtypes) of every `ret c2[h]_name(params);` the header declares."""
+    protos = {}
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+[\s*]+)(c2h?_\w+)\s*\(([^()]*)\)\s*;", header, flags=re.M):
+        params = [] if params.strip() == "void" else [re.sub(r"\w+$", "", p.strip()) for p in params.split(",")]
+        protos[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
+    return protos
+
+
+globals().update({k: int(v) for k, v in re.findall(r"^#define\s+(C2_(?:OK|ERR_\w+|MAX_WIDTH|FAST_WIDTH))\s+\(?(-?\d+)\)?\s*$",
+                                                     _header(), flags=re.M)})
 
 # Every symbol include/celerite2_amd.h declares (checked by tests/test_abi.py).
 SYMBOLS = [
@@ -39,10 +92,6 @@ SYMBOLS = [
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
-
-
-class BackendError(RuntimeError):
-    pass
 
 
 def _sync_env(lib):
@@ -102,26 +151,10 @@ def load():
     except Exception:  # pragma: no cover - torch is plumbing, not required for the C-ABI itself
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    lib.c2_version.restype = ctypes.c_char_p
-    lib.c2_last_error.restype = ctypes.c_char_p
-    lib.c2_device_count.restype = ctypes.c_int
-    lib.c2_loglik_grad_workspace_bytes.restype = ctypes.c_size_t
-    lib.c2_loglik_grad_workspace_bytes.argtypes = [ctypes.c_int64] * 3
-    lib.c2_loglik_terms_workspace_bytes.restype = ctypes.c_size_t
-    lib.c2_loglik_terms_workspace_bytes.argtypes = [ctypes.c_int64] * 4 + [ctypes.c_int]
-    lib.c2_kron_loglik_workspace_bytes.restype = ctypes.c_size_t
-    lib.c2_kron_loglik_workspace_bytes.argtypes = [ctypes.c_int64] * 4 + [ctypes.c_int] * 2
-    lib.c2_term_expr_workspace_bytes.restype = ctypes.c_size_t
-    lib.c2_term_expr_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    lib.c2_get_celerite_matrices_rev_workspace_bytes.restype = ctypes.c_size_t
-    lib.c2_get_celerite_matrices_rev_workspace_bytes.argtypes = [ctypes.c_int64] * 4
-    lib.c2_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-    lib.c2_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
-    lib.c2_option_count.restype = ctypes.c_int
-    lib.c2_option_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
-                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
-                                   ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)]
-    lib.c2_options_reload_env.restype = None
+    for name, (restype, argtypes) in _prototypes(_header()).items():
+        # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
+        # cdecl function take more)
+        setattr(lib, name, ctypes.CFUNCTYPE(restype, *argtypes)((name, lib), ((1,),) * len(argtypes)))
     _lib = lib
     names = []
     for i in range(lib.c2_option_count()):

@@ -26,8 +26,6 @@ __all__ = [
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
 
-_i64 = ctypes.c_int64
-
 
 def _p(x):
     return ctypes.c_void_p(0 if x is None else x.data_ptr())
@@ -60,6 +58,47 @@ def _shape(name, x, *allowed):
                          % (name, tuple(x.shape), " or ".join(str(a) for a in allowed)))
 
 
+def _forms(dims, spec):
+    """The shapes a spec allows: a letter names a dimension of `dims`, | separates the form shared by the batch from the
+    per-series one -- "N|BN" -> ((N,), (B, N))."""
+    return tuple(tuple(map(dims.__getitem__, form)) for form in spec.split("|"))
+
+
+def _shapes(dims, entries):
+    """_shape for every (name, tensor, spec) entry, in the listed order (a None tensor is skipped).  Reads shapes only."""
+    forms = {}   # (a spec becomes shapes once per call, not once per entry)
+    for name, x, spec in entries:
+        if x is not None:
+            if spec not in forms:
+                forms[spec] = _forms(dims, spec)
+            if x.shape not in forms[spec]:
+                _shape(name, x, *forms[spec])
+
+
+def _args(dims, ins, outs=()):
+    """The checks of one op on its (name, tensor, spec) entries: dtype, device and contiguity of all of them, then their
+    shapes in the listed order (`ins` before `outs`), then -- for an op that names its outputs -- _no_alias."""
+    entries = list(ins) + list(outs)
+    _chk(*(x for _, x, _ in entries))
+    _shapes(dims, entries)
+    if outs:
+        _no_alias(outs, ins)
+
+
+def _empty(dev, dims, *specs):
+    """Fresh float64 tensors of the given specs (outputs are always per series: the last form of a spec)."""
+    return tuple(torch.empty(_forms(dims, s)[-1], dtype=torch.float64, device=dev) for s in specs)
+
+
+def _named(spec, tensors):
+    """The (name, tensor, spec) entries of the tensors an output spec -- a dict name -> shape spec -- describes."""
+    return [(name, x, s) for (name, s), x in zip(spec.items(), tensors)]
+
+
+def _flag(B, dev):
+    return torch.empty(B, dtype=torch.int32, device=dev)
+
+
 def _bs(x, per):
     """(tensor, batch stride in elements): 0 when shared by the batch."""
     return 0 if x.dim() == 1 else per
@@ -71,19 +110,24 @@ def _dims(U):
     return U.shape
 
 
+_T, _C = "N|BN", "J|BJ"   # t and c: shared by the batch or per series
+_LOGLIK_IN = dict(t=_T, c=_C, a="BN", U="BNJ", V="BNJ", y="BN")
+_LOGLIK_GRADS = dict(bt="BN", bc="BJ", ba="BN", bU="BNJ", bV="BNJ", by="BN")
+_COEFS = ("BR", "BR", "BC", "BC", "BC", "BC")   # ar, cr (B, Jr); ac, bc, cc, dc (B, Jc)
+
+
 def factor(t, c, a, U, V, d=None, W=None, S=None, *, workspace=False):
     """Batched core::factor.  Returns (d, W, flag) or (d, W, S, flag); d may alias a, W may alias V."""
     B, N, J = _dims(U)
+    dims = dict(B=B, N=N, J=J)
     d = torch.empty_like(a) if d is None else d
     W = torch.empty_like(V) if W is None else W
     if workspace and S is None:
-        S = torch.empty((B, N, J, J), dtype=torch.float64, device=U.device)
-    flag = torch.empty(B, dtype=torch.int32, device=U.device)
-    _chk(t, c, a, U, V, d, W, S)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("a", a, (B, N)); _shape("V", V, (B, N, J))
-    _shape("d", d, (B, N)); _shape("W", W, (B, N, J)); _shape("S", S, (B, N, J, J))
-    rc = _lib.load().c2_factor(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                               _p(U), _p(V), _p(d), _p(W), _p(S), _p(flag), _stream())
+        S, = _empty(U.device, dims, "BNJJ")
+    flag = _flag(B, U.device)
+    _args(dims, [("t", t, _T), ("c", c, _C), ("a", a, "BN"), ("U", U, "BNJ"), ("V", V, "BNJ"), ("d", d, "BN"), ("W", W, "BNJ"),
+                 ("S", S, "BNJJ")])
+    rc = _lib.load().c2_factor(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, d, W, S, flag, _stream())
     _lib.check(rc, "factor")
     return (d, W, S, flag) if S is not None else (d, W, flag)
 
@@ -93,12 +137,11 @@ def condition(t, c, a, U, V):
     1e-10 agreement with the reference is attainable in float64 for these inputs (include/celerite2_amd.h, c2_condition:
     any evaluation order carries ~0.4 eps kappa^2 of the largest gradient entry).  Returns (kappa, flag)."""
     B, N, J = _dims(U)
-    kappa = torch.empty(B, dtype=torch.float64, device=U.device)
-    flag = torch.empty(B, dtype=torch.int32, device=U.device)
-    _chk(t, c, a, U, V)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("a", a, (B, N)); _shape("V", V, (B, N, J))
-    rc = _lib.load().c2_condition(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                                  _p(U), _p(V), _p(kappa), _p(flag), _stream())
+    dims = dict(B=B, N=N, J=J)
+    kappa, = _empty(U.device, dims, "B")
+    flag = _flag(B, U.device)
+    _args(dims, [("t", t, _T), ("c", c, _C), ("a", a, "BN"), ("U", U, "BNJ"), ("V", V, "BNJ")])
+    rc = _lib.load().c2_condition(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, kappa, flag, _stream())
     _lib.check(rc, "condition")
     return kappa, flag
 
@@ -109,18 +152,15 @@ def _sweep(name, matmul):
         if Y.dim() != 3:
             raise ValueError("Invalid shape: Y (must be (B, N, nrhs))")
         nrhs = Y.shape[-1]
+        dims = dict(B=B, N=N, J=J, K=nrhs)
         if Z is None:
             Z = torch.zeros_like(Y) if matmul else torch.empty_like(Y)
         if workspace and F is None:
-            F = torch.empty((B, N, J, nrhs), dtype=torch.float64, device=U.device)
-        _chk(t, c, U, W, Y, Z, F)
-        _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J))
-        _shape("Y", Y, (B, N, nrhs)); _shape("Z", Z, (B, N, nrhs)); _shape("F", F, (B, N, J, nrhs))
-        args = [_i64(B), _i64(N), _i64(J), _i64(nrhs), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U), _p(W),
-                _p(Y), _p(Z), _p(F)]
-        if matmul:
-            args.append(ctypes.c_int(1 if zero_z else 0))
-        rc = getattr(_lib.load(), "c2_" + name)(*args, _stream())
+            F, = _empty(U.device, dims, "BNJK")
+        _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("Y", Y, "BNK"), ("Z", Z, "BNK"),
+                     ("F", F, "BNJK")])
+        flags = (bool(zero_z),) if matmul else ()
+        rc = getattr(_lib.load(), "c2_" + name)(B, N, J, nrhs, t, _bs(t, N), c, _bs(c, J), U, W, Y, Z, F, *flags, _stream())
         _lib.check(rc, name)
         return (Z, F) if F is not None else Z
     op.__name__ = name
@@ -133,23 +173,25 @@ matmul_lower = _sweep("matmul_lower", True)
 matmul_upper = _sweep("matmul_upper", True)
 
 
+def _general_dims(U, V, Y):
+    B, N, J = _dims(U)
+    if V.dim() != 3 or Y.dim() != 3:
+        raise ValueError("Invalid shape: V must be (B, M, J) and Y (B, M, nrhs)")
+    return dict(B=B, N=N, M=V.shape[1], J=J, K=Y.shape[-1])
+
+
 def _general(name):
     def op(t1, t2, c, U, V, Y, Z=None, F=None, *, workspace=False, zero_z=False):
-        B, N, J = _dims(U)
-        if V.dim() != 3 or Y.dim() != 3:
-            raise ValueError("Invalid shape: V must be (B, M, J) and Y (B, M, nrhs)")
-        M, nrhs = V.shape[1], Y.shape[-1]
+        dims = _general_dims(U, V, Y)
+        B, N, M, J, nrhs = dims.values()
         if Z is None:
             Z = torch.zeros((B, N, nrhs), dtype=torch.float64, device=U.device)
         if workspace and F is None:
             F = torch.zeros((B, M, J, nrhs), dtype=torch.float64, device=U.device)
-        _chk(t1, t2, c, U, V, Y, Z, F)
-        _shape("t1", t1, (N,), (B, N)); _shape("t2", t2, (M,), (B, M)); _shape("c", c, (J,), (B, J))
-        _shape("V", V, (B, M, J)); _shape("Y", Y, (B, M, nrhs)); _shape("Z", Z, (B, N, nrhs))
-        _shape("F", F, (B, M, J, nrhs))
-        rc = getattr(_lib.load(), "c2_" + name)(
-            _i64(B), _i64(N), _i64(M), _i64(J), _i64(nrhs), _p(t1), _i64(_bs(t1, N)), _p(t2), _i64(_bs(t2, M)), _p(c),
-            _i64(_bs(c, J)), _p(U), _p(V), _p(Y), _p(Z), _p(F), ctypes.c_int(1 if zero_z else 0), _stream())
+        _args(dims, [("t1", t1, _T), ("t2", t2, "M|BM"), ("c", c, _C), ("U", U, "BNJ"), ("V", V, "BMJ"), ("Y", Y, "BMK"),
+                     ("Z", Z, "BNK"), ("F", F, "BMJK")])
+        rc = getattr(_lib.load(), "c2_" + name)(B, N, M, J, nrhs, t1, _bs(t1, N), t2, _bs(t2, M), c, _bs(c, J), U, V, Y, Z, F,
+                                                bool(zero_z), _stream())
         _lib.check(rc, name)
         return (Z, F) if F is not None else Z
     op.__name__ = name
@@ -167,19 +209,11 @@ def factor_rev(t, c, a, U, V, d, W, S, bd, bW):
     `S` is then only read if the device-side verification of that pass fails and the row-by-row kernel recomputes the
     batch behind it.  Either way the result is that of the reference on the same (t, c, U, d, W, bd, bW)."""
     B, N, J = _dims(U)
-    dev = U.device
-    bt = torch.empty((B, N), dtype=torch.float64, device=dev)
-    bc = torch.empty((B, J), dtype=torch.float64, device=dev)
-    ba = torch.empty((B, N), dtype=torch.float64, device=dev)
-    bU = torch.empty_like(U)
-    bV = torch.empty_like(U)
-    _chk(t, c, a, U, V, d, W, S, bd, bW)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("a", a, (B, N)); _shape("V", V, (B, N, J))
-    _shape("d", d, (B, N)); _shape("W", W, (B, N, J)); _shape("S", S, (B, N, J, J)); _shape("bd", bd, (B, N))
-    _shape("bW", bW, (B, N, J))
-    rc = _lib.load().c2_factor_rev(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                                   _p(U), _p(V), _p(d), _p(W), _p(S), _p(bd), _p(bW), _p(bt), _p(bc), _p(ba), _p(bU),
-                                   _p(bV), _stream())
+    dims = dict(B=B, N=N, J=J)
+    bt, bc, ba, bU, bV = _empty(U.device, dims, "BN", "BJ", "BN", "BNJ", "BNJ")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("a", a, "BN"), ("U", U, "BNJ"), ("V", V, "BNJ"), ("d", d, "BN"), ("W", W, "BNJ"),
+                 ("S", S, "BNJJ"), ("bd", bd, "BN"), ("bW", bW, "BNJ")])
+    rc = _lib.load().c2_factor_rev(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, d, W, S, bd, bW, bt, bc, ba, bU, bV, _stream())
     _lib.check(rc, "factor_rev")
     return bt, bc, ba, bU, bV
 
@@ -190,19 +224,12 @@ def _sweep_rev(name):
         if Y.dim() != 3:
             raise ValueError("Invalid shape: Y (must be (B, N, nrhs))")
         nrhs = Y.shape[-1]
-        dev = U.device
-        bt = torch.empty((B, N), dtype=torch.float64, device=dev)
-        bc = torch.empty((B, J), dtype=torch.float64, device=dev)
-        bU = torch.empty_like(U)
-        bW = torch.empty_like(U)
-        bY = torch.empty_like(Y)
-        _chk(t, c, U, W, Y, Z, F, bZ)
-        _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J))
-        _shape("Y", Y, (B, N, nrhs)); _shape("Z", Z, (B, N, nrhs)); _shape("F", F, (B, N, J, nrhs))
-        _shape("bZ", bZ, (B, N, nrhs))
-        rc = getattr(_lib.load(), "c2_" + name)(
-            _i64(B), _i64(N), _i64(J), _i64(nrhs), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U), _p(W), _p(Y),
-            _p(Z), _p(F), _p(bZ), _p(bt), _p(bc), _p(bU), _p(bW), _p(bY), _stream())
+        dims = dict(B=B, N=N, J=J, K=nrhs)
+        bt, bc, bU, bW, bY = _empty(U.device, dims, "BN", "BJ", "BNJ", "BNJ", "BNK")
+        _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("Y", Y, "BNK"), ("Z", Z, "BNK"),
+                     ("F", F, "BNJK"), ("bZ", bZ, "BNK")])
+        rc = getattr(_lib.load(), "c2_" + name)(B, N, J, nrhs, t, _bs(t, N), c, _bs(c, J), U, W, Y, Z, F, bZ, bt, bc, bU, bW,
+                                                bY, _stream())
         _lib.check(rc, name)
         return bt, bc, bU, bW, bY
     op.__name__ = name
@@ -234,10 +261,8 @@ def get_celerite_matrices(ar, ac, bc, dc, x, diag):
     _shape("ar", ar, (Jr,), (B, Jr))
     for nm, v in (("ac", ac), ("bc", bc), ("dc", dc)):
         _shape(nm, v, (Jc,), (B, Jc))
-    rc = _lib.load().c2_get_celerite_matrices(
-        _i64(B), _i64(N), _i64(Jr), _i64(Jc), _p(ar if Jr else None), _p(ac if Jc else None), _p(bc if Jc else None),
-        _p(dc if Jc else None), ctypes.c_int(1 if batched else 0), _p(x), _i64(_bs(x, N)), _p(diag), _p(a), _p(U),
-        _p(V), _stream())
+    rc = _lib.load().c2_get_celerite_matrices(B, N, Jr, Jc, ar if Jr else None, ac if Jc else None, bc if Jc else None,
+                                              dc if Jc else None, batched, x, _bs(x, N), diag, a, U, V, _stream())
     _lib.check(rc, "get_celerite_matrices")
     return a, U, V
 
@@ -260,10 +285,8 @@ def kernel_values(ar, cr, ac, bc, cc, dc, t1, t2, B=None):
     for nm, v, w in (("ar", ar, Jr), ("cr", cr, Jr), ("ac", ac, Jc), ("bc", bc, Jc), ("cc", cc, Jc), ("dc", dc, Jc)):
         _shape(nm, v, (w,), (B, w))
     K = torch.empty((B, N, M), dtype=torch.float64, device=t1.device)
-    rc = _lib.load().c2_kernel_values(
-        _i64(B), _i64(N), _i64(M), _i64(Jr), _i64(Jc), _p(ar if Jr else None), _p(cr if Jr else None), _p(ac if Jc else None),
-        _p(bc if Jc else None), _p(cc if Jc else None), _p(dc if Jc else None), ctypes.c_int(1 if batched else 0), _p(t1),
-        _i64(_bs(t1, N)), _p(t2), _i64(_bs(t2, M)), _p(K), _stream())
+    rc = _lib.load().c2_kernel_values(B, N, M, Jr, Jc, *_coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc), batched, t1, _bs(t1, N), t2,
+                                      _bs(t2, M), K, _stream())
     _lib.check(rc, "kernel_values")
     return K
 
@@ -277,25 +300,19 @@ def colsumsq_over_d(Z, d):
     _chk(Z, d)
     _shape("d", d, (B, N))
     out = torch.empty((B, M), dtype=torch.float64, device=Z.device)
-    rc = _lib.load().c2_colsumsq_over_d(_i64(B), _i64(N), _i64(M), _p(Z), _p(d), _p(out), _stream())
+    rc = _lib.load().c2_colsumsq_over_d(B, N, M, Z, d, out, _stream())
     _lib.check(rc, "colsumsq_over_d")
     return out
-
-
-def _loglik_shapes(B, N, J, t, c, a, V, y):
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("a", a, (B, N)); _shape("V", V, (B, N, J))
-    _shape("y", y, (B, N))
 
 
 def loglik(t, c, a, U, V, y):
     """Fused batched log-likelihood.  Returns (ll (B,), flag (B,) int32)."""
     B, N, J = _dims(U)
-    ll = torch.empty(B, dtype=torch.float64, device=U.device)
-    flag = torch.empty(B, dtype=torch.int32, device=U.device)
-    _chk(t, c, a, U, V, y)
-    _loglik_shapes(B, N, J, t, c, a, V, y)
-    rc = _lib.load().c2_loglik(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                               _p(U), _p(V), _p(y), _p(ll), _p(flag), _stream())
+    dims = dict(B=B, N=N, J=J)
+    ll, = _empty(U.device, dims, "B")
+    flag = _flag(B, U.device)
+    _args(dims, _named(_LOGLIK_IN, (t, c, a, U, V, y)))
+    rc = _lib.load().c2_loglik(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, y, ll, flag, _stream())
     _lib.check(rc, "loglik")
     return ll, flag
 
@@ -318,10 +335,7 @@ def loglik_grad_buffers(t, c, a, U, V, y, *, candidates=3):
     dev = U.device
 
     def fresh():
-        return (loglik_grad_workspace(B, N, J, dev),
-                (torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty((B, J), dtype=torch.float64, device=dev),
-                 torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty_like(U), torch.empty_like(U),
-                 torch.empty((B, N), dtype=torch.float64, device=dev)))
+        return loglik_grad_workspace(B, N, J, dev), _empty(dev, dict(B=B, N=N, J=J), *_LOGLIK_GRADS.values())
 
     def one_step_ms(w_, o_):
         for _ in range(2):
@@ -365,23 +379,18 @@ def loglik_grad_buffers(t, c, a, U, V, y, *, candidates=3):
 def loglik_grad(t, c, a, U, V, y, *, work=None, out=None):
     """Fused batched log-likelihood + gradient.  Returns (ll, (bt, bc, ba, bU, bV, by), flag)."""
     B, N, J = _dims(U)
+    dims = dict(B=B, N=N, J=J)
     dev = U.device
     if work is None:
         work = loglik_grad_workspace(B, N, J, dev)
     if out is None:
-        out = (torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty((B, J), dtype=torch.float64, device=dev),
-               torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty_like(U), torch.empty_like(U),
-               torch.empty((B, N), dtype=torch.float64, device=dev))
+        out = _empty(dev, dims, *_LOGLIK_GRADS.values())
     bt, bc, ba, bU, bV, by = out
-    ll = torch.empty(B, dtype=torch.float64, device=dev)
-    flag = torch.empty(B, dtype=torch.int32, device=dev)
-    _chk(t, c, a, U, V, y, bt, bc, ba, bU, bV, by)
-    _loglik_shapes(B, N, J, t, c, a, V, y)
-    _shape("bt", bt, (B, N)); _shape("bc", bc, (B, J)); _shape("ba", ba, (B, N)); _shape("bU", bU, (B, N, J))
-    _shape("bV", bV, (B, N, J)); _shape("by", by, (B, N))
-    rc = _lib.load().c2_loglik_grad(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                                    _p(U), _p(V), _p(y), _p(ll), _p(bt), _p(bc), _p(ba), _p(bU), _p(bV), _p(by),
-                                    _p(flag), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+    ll, = _empty(dev, dims, "B")
+    flag = _flag(B, dev)
+    _args(dims, _named(_LOGLIK_IN, (t, c, a, U, V, y)) + _named(_LOGLIK_GRADS, out))
+    rc = _lib.load().c2_loglik_grad(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work,
+                                    work.numel() * 8, _stream())
     _lib.check(rc, "loglik_grad")
     return ll, out, flag
 
@@ -393,11 +402,9 @@ def dot_tril(t, c, U, W, d, Y, Z=None):
         raise ValueError("Invalid shape: Y (must be (B, N, nrhs))")
     nrhs = Y.shape[-1]
     Z = torch.empty_like(Y) if Z is None else Z
-    _chk(t, c, U, W, d, Y, Z)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
-    _shape("Y", Y, (B, N, nrhs)); _shape("Z", Z, (B, N, nrhs))
-    rc = _lib.load().c2_dot_tril(_i64(B), _i64(N), _i64(J), _i64(nrhs), _p(t), _i64(_bs(t, N)), _p(c),
-                                 _i64(_bs(c, J)), _p(U), _p(W), _p(d), _p(Y), _p(Z), _stream())
+    _args(dict(B=B, N=N, J=J, K=nrhs), [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"),
+                                        ("Y", Y, "BNK"), ("Z", Z, "BNK")])
+    rc = _lib.load().c2_dot_tril(B, N, J, nrhs, t, _bs(t, N), c, _bs(c, J), U, W, d, Y, Z, _stream())
     _lib.check(rc, "dot_tril")
     return Z
 
@@ -406,9 +413,10 @@ _KRON_METHODS = {"collapsed": 0, "interleaved": 1}
 
 
 def _no_alias(outs, ins):
-    """No output may share its first byte with an input or another output ("<name> must not alias <name>")."""
-    seen = [(nm, x.data_ptr()) for nm, x in ins if x is not None and x.numel()]
-    for nm, x in outs:
+    """No output may share its first byte with an input or another output ("<name> must not alias <name>"); entries are
+    (name, tensor, ...)."""
+    seen = [(e[0], e[1].data_ptr()) for e in ins if e[1] is not None and e[1].numel()]
+    for nm, x, *_ in outs:
         if x is None or not x.numel():
             continue
         for other, ptr in seen:
@@ -428,28 +436,26 @@ def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None, *, workspace=False, 
     2.4 MB per series at N = 4096, J = 8; callers with large batches chunk the batch.  Caller-owned `ws` is accepted.
     J <= 32, and no output may alias an input or another output (alpha == z included)."""
     B, N, J = _dims(U)
+    dims = dict(B=B, N=N, J=J)
     q = torch.empty_like(d) if q is None else q
     if z is None:
         if alpha is not None:
             raise ValueError("Invalid shape: alpha (given without z)")
     elif alpha is None:
         alpha = torch.empty_like(z)
-    _chk(t, c, U, W, d, z, q, alpha)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
-    _shape("z", z, (B, N)); _shape("q", q, (B, N)); _shape("alpha", alpha, (B, N))
+    ins = [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("z", z, "BN")]
+    outs = [("q", q, "BN"), ("alpha", alpha, "BN")]
+    _args(dims, ins + outs)
     if workspace or ws is not None:
         if ws is None:
-            ws = (torch.empty((B, N, J, J), dtype=torch.float64, device=U.device),
-                  None if z is None else torch.empty((B, N, J), dtype=torch.float64, device=U.device))
+            ws = _empty(U.device, dims, "BNJJ") + (_empty(U.device, dims, "BNJ") if z is not None else (None,))
         Mws, Fws = ws
         if (Fws is None) != (z is None):
             raise ValueError("Invalid shape: Fws (given exactly when z is)")
-        _chk(Mws, Fws)
-        _shape("Mws", Mws, (B, N, J, J)); _shape("Fws", Fws, (B, N, J))
-        _no_alias([("q", q), ("alpha", alpha), ("Mws", Mws), ("Fws", Fws)],
-                  [("t", t), ("c", c), ("U", U), ("W", W), ("d", d), ("z", z)])
-        rc = _lib.load().c2_inverse_diag_fwd(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
-                                             _p(W), _p(d), _p(z), _p(q), _p(alpha), _p(Mws), _p(Fws), _stream())
+        states = [("Mws", Mws, "BNJJ"), ("Fws", Fws, "BNJ")]
+        _args(dims, states)
+        _no_alias(outs + states, ins)
+        rc = _lib.load().c2_inverse_diag_fwd(B, N, J, t, _bs(t, N), c, _bs(c, J), U, W, d, z, q, alpha, Mws, Fws, _stream())
         _lib.check(rc, "inverse_diag")
         return (q, (Mws, Fws)) if z is None else (q, alpha, (Mws, Fws))
     # the only aliasing the sweep allows is alpha == z (a row's z is read before its alpha is stored)
@@ -459,8 +465,7 @@ def inverse_diag(t, c, U, W, d, z=None, q=None, alpha=None, *, workspace=False, 
         raise ValueError("Invalid argument: q must not alias z or alpha")
     if alpha is not None and alpha.data_ptr() == d.data_ptr():
         raise ValueError("Invalid argument: alpha must not alias d")
-    rc = _lib.load().c2_inverse_diag(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
-                                     _p(W), _p(d), _p(z), _p(q), _p(alpha), _stream())
+    rc = _lib.load().c2_inverse_diag(B, N, J, t, _bs(t, N), c, _bs(c, J), U, W, d, z, q, alpha, _stream())
     _lib.check(rc, "inverse_diag")
     return q if z is None else (q, alpha)
 
@@ -473,28 +478,21 @@ def inverse_diag_rev(t, c, U, W, d, z, q, alpha, ws, bq, balpha, *, out=None):
     None).  `out`: the six tensors of a previous call to write into (nothing is allocated then: capturable).  J <= 32; no
     output may alias an input or another output.  No atomics: two calls give identical bits."""
     B, N, J = _dims(U)
+    dims = dict(B=B, N=N, J=J)
     Mws, Fws = ws
-    f64 = dict(dtype=torch.float64, device=U.device)
+    grads = dict(bt="BN", bc="BJ", bU="BNJ", bW="BNJ", bd="BN", **({} if z is None else dict(bz="BN")))
     if out is None:
-        out = (torch.empty((B, N), **f64), torch.empty((B, J), **f64), torch.empty((B, N, J), **f64),
-               torch.empty((B, N, J), **f64), torch.empty((B, N), **f64), None if z is None else torch.empty((B, N), **f64))
+        out = _empty(U.device, dims, *grads.values()) + ((None,) if z is None else ())
     bt, bc, bU, bW, bd, bz = out
     hz = z is not None
     for nm, v in (("alpha", alpha), ("Fws", Fws), ("balpha", balpha), ("bz", bz)):
         if (v is not None) != hz:
             raise ValueError("Invalid shape: %s (given exactly when z is)" % nm)
-    _chk(t, c, U, W, d, z, q, alpha, Mws, Fws, bq, balpha, bt, bc, bU, bW, bd, bz)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("W", W, (B, N, J)); _shape("d", d, (B, N))
-    _shape("z", z, (B, N)); _shape("q", q, (B, N)); _shape("alpha", alpha, (B, N)); _shape("Mws", Mws, (B, N, J, J))
-    _shape("Fws", Fws, (B, N, J)); _shape("bq", bq, (B, N)); _shape("balpha", balpha, (B, N))
-    _shape("bt", bt, (B, N)); _shape("bc", bc, (B, J)); _shape("bU", bU, (B, N, J)); _shape("bW", bW, (B, N, J))
-    _shape("bd", bd, (B, N)); _shape("bz", bz, (B, N))
-    _no_alias([("bt", bt), ("bc", bc), ("bU", bU), ("bW", bW), ("bd", bd), ("bz", bz)],
-              [("t", t), ("c", c), ("U", U), ("W", W), ("d", d), ("z", z), ("q", q), ("alpha", alpha), ("Mws", Mws),
-               ("Fws", Fws), ("bq", bq), ("balpha", balpha)])
-    rc = _lib.load().c2_inverse_diag_rev(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(U),
-                                         _p(W), _p(d), _p(z), _p(q), _p(alpha), _p(Mws), _p(Fws), _p(bq), _p(balpha), _p(bt),
-                                         _p(bc), _p(bU), _p(bW), _p(bd), _p(bz), _stream())
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("z", z, "BN"), ("q", q, "BN"),
+                 ("alpha", alpha, "BN"), ("Mws", Mws, "BNJJ"), ("Fws", Fws, "BNJ"), ("bq", bq, "BN"), ("balpha", balpha, "BN")],
+          _named(grads, out))
+    rc = _lib.load().c2_inverse_diag_rev(B, N, J, t, _bs(t, N), c, _bs(c, J), U, W, d, z, q, alpha, Mws, Fws, bq, balpha, bt, bc,
+                                         bU, bW, bd, bz, _stream())
     _lib.check(rc, "inverse_diag_rev")
     return bt, bc, bU, bW, bd, bz
 
@@ -508,50 +506,35 @@ def get_celerite_matrices_rev(ac, bc, dc, x, V, bt, bcv, ba, bU, bV, Jr, *, work
     Jc = ac.shape[-1]
     if Jr + 2 * Jc != J:
         raise ValueError("Invalid shape: V (got width %d, expected Jr + 2 Jc = %d)" % (J, Jr + 2 * Jc))
+    dims = dict(B=B, N=N, J=J, R=Jr, C=Jc)
     batched = ac.dim() == 2
-    _chk(ac, bc, dc, x, V, bt, bcv, ba, bU, bV)
-    _shape("x", x, (N,), (B, N))
-    for nm, v in (("ac", ac), ("bc", bc), ("dc", dc)):
-        _shape(nm, v, (Jc,) if not batched else (B, Jc))
-    _shape("bt", bt, (B, N)); _shape("bc", bcv, (B, J)); _shape("ba", ba, (B, N)); _shape("bU", bU, (B, N, J))
-    _shape("bV", bV, (B, N, J))
-    f64 = dict(dtype=torch.float64, device=V.device)
-    outs = [torch.empty((B, Jr), **f64), torch.empty((B, Jr), **f64)] + [torch.empty((B, Jc), **f64) for _ in range(4)] + \
-           [torch.empty((B, N), **f64) for _ in range(2)]
+    coef = "BC" if batched else "C"
+    _args(dims, [("x", x, _T), ("ac", ac, coef), ("bc", bc, coef), ("dc", dc, coef), ("V", V, "BNJ"), ("bt", bt, "BN"),
+                 ("bc", bcv, "BJ"), ("ba", ba, "BN"), ("bU", bU, "BNJ"), ("bV", bV, "BNJ")])
+    outs = _empty(V.device, dims, *_COEFS, "BN", "BN")
     lib = _lib.load()
     nbytes = lib.c2_get_celerite_matrices_rev_workspace_bytes(B, N, Jr, Jc)
     if nbytes and (work is None or work.numel() * 8 < nbytes):
-        work = torch.empty(nbytes // 8, **f64)
-    optr = [_p(o if o.numel() else None) for o in outs[:6]] + [_p(o) for o in outs[6:]]
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=V.device)
     rc = lib.c2_get_celerite_matrices_rev(
-        _i64(B), _i64(N), _i64(Jr), _i64(Jc), _p(ac if Jc else None), _p(bc if Jc else None), _p(dc if Jc else None),
-        ctypes.c_int(1 if batched else 0), _p(x), _i64(_bs(x, N)), _p(V), _p(bt), _p(bcv), _p(ba), _p(bU), _p(bV), *optr,
-        _p(work), ctypes.c_size_t(0 if work is None else work.numel() * 8), _stream())
+        B, N, Jr, Jc, ac if Jc else None, bc if Jc else None, dc if Jc else None, batched, x, _bs(x, N), V, bt, bcv, ba, bU, bV,
+        *_coef_ptrs(*outs[:6], Jr, Jc), *outs[6:], work, 0 if work is None else work.numel() * 8, _stream())
     _lib.check(rc, "get_celerite_matrices_rev")
-    return tuple(outs)
+    return outs
 
 
 def _general_rev(name):
     def op(t1, t2, c, U, V, Y, F, bZ, *, out=None):
-        B, N, J = _dims(U)
-        if V.dim() != 3 or Y.dim() != 3:
-            raise ValueError("Invalid shape: V must be (B, M, J) and Y (B, M, nrhs)")
-        M, nrhs = V.shape[1], Y.shape[-1]
-        f64 = dict(dtype=torch.float64, device=U.device)
+        dims = _general_dims(U, V, Y)
+        B, N, M, J, nrhs = dims.values()
+        grads = dict(bt1="BN", bt2="BM", bc="BJ", bU="BNJ", bV="BMJ", bY="BMK")
         if out is None:
-            out = (torch.empty((B, N), **f64), torch.empty((B, M), **f64), torch.empty((B, J), **f64),
-                   torch.empty((B, N, J), **f64), torch.empty((B, M, J), **f64), torch.empty((B, M, nrhs), **f64))
+            out = _empty(U.device, dims, *grads.values())
         bt1, bt2, bc, bU, bV, bY = out
-        _chk(t1, t2, c, U, V, Y, F, bZ, bt1, bt2, bc, bU, bV, bY)
-        _shape("t1", t1, (N,), (B, N)); _shape("t2", t2, (M,), (B, M)); _shape("c", c, (J,), (B, J))
-        _shape("V", V, (B, M, J)); _shape("Y", Y, (B, M, nrhs)); _shape("F", F, (B, M, J, nrhs))
-        _shape("bZ", bZ, (B, N, nrhs)); _shape("bt1", bt1, (B, N)); _shape("bt2", bt2, (B, M)); _shape("bc", bc, (B, J))
-        _shape("bU", bU, (B, N, J)); _shape("bV", bV, (B, M, J)); _shape("bY", bY, (B, M, nrhs))
-        _no_alias([("bt1", bt1), ("bt2", bt2), ("bc", bc), ("bU", bU), ("bV", bV), ("bY", bY)],
-                  [("t1", t1), ("t2", t2), ("c", c), ("U", U), ("V", V), ("Y", Y), ("F", F), ("bZ", bZ)])
-        rc = getattr(_lib.load(), "c2_" + name)(
-            _i64(B), _i64(N), _i64(M), _i64(J), _i64(nrhs), _p(t1), _i64(_bs(t1, N)), _p(t2), _i64(_bs(t2, M)), _p(c),
-            _i64(_bs(c, J)), _p(U), _p(V), _p(Y), _p(F), _p(bZ), _p(bt1), _p(bt2), _p(bc), _p(bU), _p(bV), _p(bY), _stream())
+        _args(dims, [("t1", t1, _T), ("t2", t2, "M|BM"), ("c", c, _C), ("U", U, "BNJ"), ("V", V, "BMJ"), ("Y", Y, "BMK"),
+                     ("F", F, "BMJK"), ("bZ", bZ, "BNK")], _named(grads, out))
+        rc = getattr(_lib.load(), "c2_" + name)(B, N, M, J, nrhs, t1, _bs(t1, N), t2, _bs(t2, M), c, _bs(c, J), U, V, Y, F, bZ,
+                                                bt1, bt2, bc, bU, bV, bY, _stream())
         _lib.check(rc, name)
         return bt1, bt2, bc, bU, bV, bY
     op.__name__ = name
@@ -570,6 +553,18 @@ general_matmul_lower_rev = _general_rev("general_matmul_lower_rev")
 general_matmul_upper_rev = _general_rev("general_matmul_upper_rev")
 
 
+def _merged_dims(U, Us):
+    B, N, J = _dims(U)
+    if Us.dim() != 3:
+        raise ValueError("Invalid shape: Us (must be (B, M, J))")
+    return dict(B=B, N=N, M=Us.shape[1], J=J)
+
+
+def _explained_variance_in(t, ts, c, U, W, d, Us, Vs):
+    return [("t", t, _T), ("ts", ts, "M|BM"), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Us", Us, "BMJ"),
+            ("Vs", Vs, "BMJ")]
+
+
 def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None, workspace=False, ws=None):
     """r (B, M) = diag(K*^T (K + D)^-1 K*) at the M sorted query times `ts` ((M,) shared or (B, M)) against the factored
     matrix K + D = L diag(d) L^T on the data times `t`: the predictive variance at `ts` is k(0) - r.  Two sweeps over the
@@ -581,31 +576,25 @@ def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None, worksp
     reads -- returns (r, ws) with ws = (Sws, Rws), both (B, N, J, J), the forward and the backward state after every data
     row: 16 B N J^2 bytes, 4.2 MB per series at N = 4096, J = 8; callers with large batches chunk the batch.  A caller-owned
     `ws` is accepted.  The reverse also reads `work`: pass it in to keep it."""
-    B, N, J = _dims(U)
-    if Us.dim() != 3:
-        raise ValueError("Invalid shape: Us (must be (B, M, J))")
-    M = Us.shape[1]
-    f64 = dict(dtype=torch.float64, device=U.device)
-    out = torch.empty((B, M), **f64) if out is None else out
+    dims = _merged_dims(U, Us)
+    B, N, M, J = dims.values()
+    dev = U.device
+    out = _empty(dev, dims, "BM")[0] if out is None else out
     with_ws = workspace or ws is not None
     if ws is not None:
         Sws, Rws = ws
     elif with_ws:
-        Sws, Rws = torch.empty((B, N, J, J), **f64), torch.empty((B, N, J, J), **f64)
+        Sws, Rws = _empty(dev, dims, "BNJJ", "BNJJ")
     else:
         Sws = Rws = None
-    work = torch.empty((B, M, J), **f64) if work is None else work
-    _chk(t, ts, c, U, W, d, Us, Vs, out, work, Sws, Rws)
-    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J))
-    _shape("W", W, (B, N, J)); _shape("d", d, (B, N)); _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J))
-    _shape("out", out, (B, M)); _shape("work", work, (B, M, J))
+    work = _empty(dev, dims, "BMJ")[0] if work is None else work
+    ins = _explained_variance_in(t, ts, c, U, W, d, Us, Vs)
+    outs = [("out", out, "BM"), ("work", work, "BMJ"), ("Sws", Sws, "BNJJ"), ("Rws", Rws, "BNJJ")]
+    _args(dims, ins + outs)
     if with_ws:
-        _shape("Sws", Sws, (B, N, J, J)); _shape("Rws", Rws, (B, N, J, J))
-        _no_alias([("out", out), ("work", work), ("Sws", Sws), ("Rws", Rws)],
-                  [("t", t), ("ts", ts), ("c", c), ("U", U), ("W", W), ("d", d), ("Us", Us), ("Vs", Vs)])
-        rc = _lib.load().c2_explained_variance_fwd(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts),
-                                                   _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(W), _p(d), _p(Us),
-                                                   _p(Vs), _p(out), _p(work), _p(Sws), _p(Rws), _stream())
+        _no_alias(outs, ins)
+        rc = _lib.load().c2_explained_variance_fwd(B, N, M, J, t, _bs(t, N), ts, _bs(ts, M), c, _bs(c, J), U, W, d, Us, Vs, out,
+                                                   work, Sws, Rws, _stream())
         _lib.check(rc, "explained_variance")
         return out, (Sws, Rws)
     inputs = [x.data_ptr() for x in (t, ts, c, U, W, d, Us, Vs)]
@@ -613,9 +602,8 @@ def explained_variance(t, ts, c, U, W, d, Us, Vs, *, out=None, work=None, worksp
         raise ValueError("Invalid argument: out must not alias an input or work")
     if work.data_ptr() in inputs:
         raise ValueError("Invalid argument: work must not alias an input")
-    rc = _lib.load().c2_explained_variance(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts),
-                                           _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(W), _p(d), _p(Us), _p(Vs),
-                                           _p(out), _p(work), _stream())
+    rc = _lib.load().c2_explained_variance(B, N, M, J, t, _bs(t, N), ts, _bs(ts, M), c, _bs(c, J), U, W, d, Us, Vs, out, work,
+                                           _stream())
     _lib.check(rc, "explained_variance")
     return out
 
@@ -629,30 +617,18 @@ def explained_variance_rev(t, ts, c, U, W, d, Us, Vs, work, ws, br, *, out=None)
     of a previous call to write into (nothing is allocated then: capturable).  Two sweeps over the merge of the two grids,
     O((N + M) J^2) per series.  J <= 32; no output may alias an input or another output.  No atomics: two calls give
     identical bits."""
-    B, N, J = _dims(U)
-    if Us.dim() != 3:
-        raise ValueError("Invalid shape: Us (must be (B, M, J))")
-    M = Us.shape[1]
+    dims = _merged_dims(U, Us)
+    B, N, M, J = dims.values()
     Sws, Rws = ws
-    f64 = dict(dtype=torch.float64, device=U.device)
+    grads = dict(bt="BN", bts="BM", bc="BJ", bU="BNJ", bW="BNJ", bd="BN", bUs="BMJ", bVs="BMJ")
     if out is None:
-        out = (torch.empty((B, N), **f64), torch.empty((B, M), **f64), torch.empty((B, J), **f64), torch.empty((B, N, J), **f64),
-               torch.empty((B, N, J), **f64), torch.empty((B, N), **f64), torch.empty((B, M, J), **f64),
-               torch.empty((B, M, J), **f64))
+        out = _empty(U.device, dims, *grads.values())
     bt, bts, bc, bU, bW, bd, bUs, bVs = out
-    _chk(t, ts, c, U, W, d, Us, Vs, work, Sws, Rws, br, *out)
-    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J))
-    _shape("W", W, (B, N, J)); _shape("d", d, (B, N)); _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J))
-    _shape("work", work, (B, M, J)); _shape("Sws", Sws, (B, N, J, J)); _shape("Rws", Rws, (B, N, J, J)); _shape("br", br, (B, M))
-    _shape("bt", bt, (B, N)); _shape("bts", bts, (B, M)); _shape("bc", bc, (B, J)); _shape("bU", bU, (B, N, J))
-    _shape("bW", bW, (B, N, J)); _shape("bd", bd, (B, N)); _shape("bUs", bUs, (B, M, J)); _shape("bVs", bVs, (B, M, J))
-    _no_alias([("bt", bt), ("bts", bts), ("bc", bc), ("bU", bU), ("bW", bW), ("bd", bd), ("bUs", bUs), ("bVs", bVs)],
-              [("t", t), ("ts", ts), ("c", c), ("U", U), ("W", W), ("d", d), ("Us", Us), ("Vs", Vs), ("work", work),
-               ("Sws", Sws), ("Rws", Rws), ("br", br)])
-    rc = _lib.load().c2_explained_variance_rev(
-        _i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(ts), _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U),
-        _p(W), _p(d), _p(Us), _p(Vs), _p(work), _p(Sws), _p(Rws), _p(br), _p(bt), _p(bts), _p(bc), _p(bU), _p(bW), _p(bd),
-        _p(bUs), _p(bVs), _stream())
+    _args(dims, _explained_variance_in(t, ts, c, U, W, d, Us, Vs) + [("work", work, "BMJ"), ("Sws", Sws, "BNJJ"),
+                                                                     ("Rws", Rws, "BNJJ"), ("br", br, "BM")],
+          _named(grads, out))
+    rc = _lib.load().c2_explained_variance_rev(B, N, M, J, t, _bs(t, N), ts, _bs(ts, M), c, _bs(c, J), U, W, d, Us, Vs, work, Sws,
+                                               Rws, br, bt, bts, bc, bU, bW, bd, bUs, bVs, _stream())
     _lib.check(rc, "explained_variance_rev")
     return bt, bts, bc, bU, bW, bd, bUs, bVs
 
@@ -665,18 +641,15 @@ def prior_draw(t, ts, c, U, V, Us, Vs, nt, ns, *, ft=None, fs=None):
     kernel's rows on the two grids.  A point that coincides with an earlier one takes that point's value and consumes no
     normal.  Caller-owned `ft`, `fs` are accepted (nothing is allocated then: capturable in a HIP graph); `ft` may be `nt`
     and `fs` may be `ns` (a row's normals are read before its draw is stored), any other aliasing is refused.  J <= 32."""
-    B, N, J = _dims(U)
-    if Us.dim() != 3:
-        raise ValueError("Invalid shape: Us (must be (B, M, J))")
+    dims = _merged_dims(U, Us)
     if nt.dim() != 3:
         raise ValueError("Invalid shape: nt (must be (B, N, K))")
-    M, K = Us.shape[1], nt.shape[2]
-    ft = torch.empty((B, N, K), dtype=torch.float64, device=U.device) if ft is None else ft
-    fs = torch.empty((B, M, K), dtype=torch.float64, device=U.device) if fs is None else fs
-    _chk(t, ts, c, U, V, Us, Vs, nt, ns, ft, fs)
-    _shape("t", t, (N,), (B, N)); _shape("ts", ts, (M,), (B, M)); _shape("c", c, (J,), (B, J)); _shape("V", V, (B, N, J))
-    _shape("Us", Us, (B, M, J)); _shape("Vs", Vs, (B, M, J)); _shape("nt", nt, (B, N, K)); _shape("ns", ns, (B, M, K))
-    _shape("ft", ft, (B, N, K)); _shape("fs", fs, (B, M, K))
+    dims["K"] = nt.shape[2]
+    B, N, M, J, K = dims.values()
+    ft = _empty(U.device, dims, "BNK")[0] if ft is None else ft
+    fs = _empty(U.device, dims, "BMK")[0] if fs is None else fs
+    _args(dims, [("t", t, _T), ("ts", ts, "M|BM"), ("c", c, _C), ("U", U, "BNJ"), ("V", V, "BNJ"), ("Us", Us, "BMJ"),
+                 ("Vs", Vs, "BMJ"), ("nt", nt, "BNK"), ("ns", ns, "BMK"), ("ft", ft, "BNK"), ("fs", fs, "BMK")])
     # the only aliasing the sweep allows is ft == nt and fs == ns
     inputs = {name: x.data_ptr() for name, x in (("t", t), ("ts", ts), ("c", c), ("U", U), ("V", V), ("Us", Us), ("Vs", Vs),
                                                    ("nt", nt), ("ns", ns))}
@@ -684,9 +657,8 @@ def prior_draw(t, ts, c, U, V, Us, Vs, nt, ns, *, ft=None, fs=None):
         raise ValueError("Invalid argument: ft must not alias an input other than nt, or fs")
     if fs.data_ptr() in [p for name, p in inputs.items() if name != "ns"]:
         raise ValueError("Invalid argument: fs must not alias an input other than ns")
-    rc = _lib.load().c2_prior_draw(_i64(B), _i64(N), _i64(M), _i64(J), _i64(K), _p(t), _i64(_bs(t, N)), _p(ts),
-                                   _i64(_bs(ts, M)), _p(c), _i64(_bs(c, J)), _p(U), _p(V), _p(Us), _p(Vs), _p(nt), _p(ns),
-                                   _p(ft), _p(fs), _stream())
+    rc = _lib.load().c2_prior_draw(B, N, M, J, K, t, _bs(t, N), ts, _bs(ts, M), c, _bs(c, J), U, V, Us, Vs, nt, ns, ft, fs,
+                                   _stream())
     _lib.check(rc, "prior_draw")
     return ft, fs
 
@@ -698,26 +670,26 @@ def _kron_args(t, c, a, U, V, alpha, diag, y, method):
     M = diag.shape[-1]
     if method not in _KRON_METHODS:
         raise ValueError("method must be 'collapsed' or 'interleaved'")
-    _chk(t, c, a, U, V, alpha, diag, y)
-    _shape("t", t, (N,), (B, N)); _shape("c", c, (J,), (B, J)); _shape("a", a, (B, N)); _shape("V", V, (B, N, J))
-    _shape("alpha", alpha, (M,), (B, M)); _shape("diag", diag, (B, N, M)); _shape("y", y, (B, N, M))
-    return B, N, M, J, _KRON_METHODS[method]
+    dims = dict(B=B, N=N, M=M, J=J)
+    _args(dims, [("t", t, _T), ("c", c, _C), ("a", a, "BN"), ("U", U, "BNJ"), ("V", V, "BNJ"), ("alpha", alpha, "M|BM"),
+                 ("diag", diag, "BNM"), ("y", y, "BNM")])
+    return dims, _KRON_METHODS[method]
 
 
 def kron_loglik(t, c, a, U, V, alpha, diag, y, *, method="collapsed", work=None):
     """2-D (multi-band) log-likelihood, rank-1 band covariance K = T (x) alpha alpha^T + diag (extension; the
     reference has no 2-D code).  (t, c, a, U, V): celerite matrices of the EPOCH grid built with zero white noise
     (a = k(0)); alpha (M,)|(B,M); diag, y (B,N,M).  Returns (ll (B,), flag (B,) int32)."""
-    B, N, M, J, meth = _kron_args(t, c, a, U, V, alpha, diag, y, method)
+    dims, meth = _kron_args(t, c, a, U, V, alpha, diag, y, method)
+    B, N, M, J = dims.values()
     lib = _lib.load()
     nbytes = lib.c2_kron_loglik_workspace_bytes(B, N, M, J, meth, 0)
     if work is None or work.numel() * 8 < nbytes:
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=U.device)
-    ll = torch.empty(B, dtype=torch.float64, device=U.device)
-    flag = torch.empty(B, dtype=torch.int32, device=U.device)
-    rc = lib.c2_kron_loglik(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                            _p(U), _p(V), _p(alpha), _i64(_bs(alpha, M)), _p(diag), _p(y), _p(ll), _p(flag),
-                            ctypes.c_int(meth), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+    ll, = _empty(U.device, dims, "B")
+    flag = _flag(B, U.device)
+    rc = lib.c2_kron_loglik(B, N, M, J, t, _bs(t, N), c, _bs(c, J), a, U, V, alpha, _bs(alpha, M), diag, y, ll, flag, meth, work,
+                            work.numel() * 8, _stream())
     _lib.check(rc, "kron_loglik")
     return ll, flag
 
@@ -727,22 +699,17 @@ def kron_loglik_grad(t, c, a, U, V, alpha, diag, y, *, method="collapsed", work=
     per series (B, M) also for a shared alpha.  (ba, bU, bV) are the partials of the method's own parametrisation
     ("collapsed": T_nn = a_n, the literal Kronecker definition; "interleaved": same-epoch cross-band terms through
     U_n.V_n); the total derivatives bU + ba V, bV + ba U along a = U.V agree."""
-    B, N, M, J, meth = _kron_args(t, c, a, U, V, alpha, diag, y, method)
+    dims, meth = _kron_args(t, c, a, U, V, alpha, diag, y, method)
+    B, N, M, J = dims.values()
     lib = _lib.load()
     dev = U.device
     nbytes = lib.c2_kron_loglik_workspace_bytes(B, N, M, J, meth, 1)
     if work is None or work.numel() * 8 < nbytes:
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    f64 = dict(dtype=torch.float64, device=dev)
-    bt, bc, ba = torch.empty((B, N), **f64), torch.empty((B, J), **f64), torch.empty((B, N), **f64)
-    bU, bV = torch.empty_like(U), torch.empty_like(U)
-    balpha, bdiag, by = torch.empty((B, M), **f64), torch.empty_like(diag), torch.empty_like(y)
-    ll = torch.empty(B, **f64)
-    flag = torch.empty(B, dtype=torch.int32, device=dev)
-    rc = lib.c2_kron_loglik_grad(_i64(B), _i64(N), _i64(M), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)),
-                                 _p(a), _p(U), _p(V), _p(alpha), _i64(_bs(alpha, M)), _p(diag), _p(y), _p(ll), _p(bt),
-                                 _p(bc), _p(ba), _p(bU), _p(bV), _p(balpha), _p(bdiag), _p(by), _p(flag),
-                                 ctypes.c_int(meth), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+    ll, bt, bc, ba, bU, bV, balpha, bdiag, by = _empty(dev, dims, "B", "BN", "BJ", "BN", "BNJ", "BNJ", "BM", "BNM", "BNM")
+    flag = _flag(B, dev)
+    rc = lib.c2_kron_loglik_grad(B, N, M, J, t, _bs(t, N), c, _bs(c, J), a, U, V, alpha, _bs(alpha, M), diag, y, ll, bt, bc, ba,
+                                 bU, bV, balpha, bdiag, by, flag, meth, work, work.numel() * 8, _stream())
     _lib.check(rc, "kron_loglik_grad")
     return ll, (bt, bc, ba, bU, bV, balpha, bdiag, by), flag
 
@@ -763,8 +730,9 @@ def _terms_args(ar, cr, ac, bc, cc, dc, x, diag, y):
 
 
 def _coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc):
-    return [_p(ar if Jr else None), _p(cr if Jr else None), _p(ac if Jc else None), _p(bc if Jc else None),
-            _p(cc if Jc else None), _p(dc if Jc else None)]
+    """The six coefficient arrays as arguments: a zero-width one is passed as NULL."""
+    return [ar if Jr else None, cr if Jr else None, ac if Jc else None, bc if Jc else None, cc if Jc else None,
+            dc if Jc else None]
 
 
 def loglik_terms(ar, cr, ac, bc, cc, dc, x, diag, y, *, work=None):
@@ -776,10 +744,9 @@ def loglik_terms(ar, cr, ac, bc, cc, dc, x, diag, y, *, work=None):
     if work is None or work.numel() * 8 < nbytes:
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=diag.device)
     ll = torch.empty(B, dtype=torch.float64, device=diag.device)
-    flag = torch.empty(B, dtype=torch.int32, device=diag.device)
-    rc = lib.c2_loglik_terms(_i64(B), _i64(N), _i64(Jr), _i64(Jc), *_coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc),
-                             ctypes.c_int(1 if batched else 0), _p(x), _i64(_bs(x, N)), _p(diag), _p(y), _p(ll),
-                             _p(flag), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+    flag = _flag(B, diag.device)
+    rc = lib.c2_loglik_terms(B, N, Jr, Jc, *_coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc), batched, x, _bs(x, N), diag, y, ll, flag,
+                             work, work.numel() * 8, _stream())
     _lib.check(rc, "loglik_terms")
     return ll, flag
 
@@ -798,25 +765,22 @@ def loglik_terms_grad(ar, cr, ac, bc, cc, dc, x, diag, y, *, work=None, out=None
     B, N, Jr, Jc, batched = _terms_args(ar, cr, ac, bc, cc, dc, x, diag, y)
     lib = _lib.load()
     dev = diag.device
+    dims = dict(B=B, N=N, R=Jr, C=Jc)
     nbytes = lib.c2_loglik_terms_workspace_bytes(B, N, Jr, Jc, 1)
     if work is None or work.numel() * 8 < nbytes:
         work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    f64 = dict(dtype=torch.float64, device=dev)
+    spec = _COEFS + ("BN", "BN", "BN")
     if out is not None:
         outs = list(out)
-        shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4 + [(B, N)] * 3
-        if len(outs) != 9 or any(tuple(o.shape) != sh or o.dtype != torch.float64 or o.device != dev or not o.is_contiguous()
-                                 for o, sh in zip(outs, shapes)):
+        if len(outs) != 9 or any(tuple(o.shape) != _forms(dims, s)[0] or o.dtype != torch.float64 or o.device != dev
+                                 or not o.is_contiguous() for o, s in zip(outs, spec)):
             raise ValueError("Invalid shape: out (nine contiguous float64 tensors as returned by loglik_terms_grad)")
     else:
-        outs = [torch.empty((B, Jr), **f64), torch.empty((B, Jr), **f64)] + [torch.empty((B, Jc), **f64) for _ in range(4)] + \
-               [torch.empty((B, N), **f64) for _ in range(3)]
-    ll = torch.empty(B, **f64)
-    flag = torch.empty(B, dtype=torch.int32, device=dev)
-    optr = [_p(o if o.numel() else None) for o in outs[:6]] + [_p(o) for o in outs[6:]]
-    rc = lib.c2_loglik_terms_grad(_i64(B), _i64(N), _i64(Jr), _i64(Jc), *_coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc),
-                                  ctypes.c_int(1 if batched else 0), _p(x), _i64(_bs(x, N)), _p(diag), _p(y), _p(ll),
-                                  *optr, _p(flag), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+        outs = list(_empty(dev, dims, *spec))
+    ll, = _empty(dev, dims, "B")
+    flag = _flag(B, dev)
+    rc = lib.c2_loglik_terms_grad(B, N, Jr, Jc, *_coef_ptrs(ar, cr, ac, bc, cc, dc, Jr, Jc), batched, x, _bs(x, N), diag, y, ll,
+                                  *_coef_ptrs(*outs[:6], Jr, Jc), *outs[6:], flag, work, work.numel() * 8, _stream())
     _lib.check(rc, "loglik_terms_grad")
     return ll, tuple(outs), flag
 
@@ -825,20 +789,20 @@ def _loglik_grad_composite(t, c, a, U, V, y):
     """Internal cross-check: the literal op chain (factor_fwd -> solve_lower_fwd -> seeds -> solve_lower_rev ->
     factor_rev) with S/F workspaces materialised in HBM, as the reference's autodiff frontends run it."""
     B, N, J = _dims(U)
+    dims = dict(B=B, N=N, J=J)
     dev = U.device
     lib = _lib.load()
+    # (not in the public header: declared here, next to their only user)
     lib.c2_loglik_grad_composite_workspace_bytes.restype = ctypes.c_size_t
     lib.c2_loglik_grad_composite_workspace_bytes.argtypes = [ctypes.c_int64] * 3
+    lib.c2_loglik_grad_composite.argtypes = lib.c2_loglik_grad.argtypes
     work = torch.empty(lib.c2_loglik_grad_composite_workspace_bytes(B, N, J) // 8, dtype=torch.float64, device=dev)
-    out = (torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty((B, J), dtype=torch.float64, device=dev),
-           torch.empty((B, N), dtype=torch.float64, device=dev), torch.empty_like(U), torch.empty_like(U),
-           torch.empty((B, N), dtype=torch.float64, device=dev))
+    out = _empty(dev, dims, *_LOGLIK_GRADS.values())
     bt, bc, ba, bU, bV, by = out
-    ll = torch.empty(B, dtype=torch.float64, device=dev)
-    flag = torch.empty(B, dtype=torch.int32, device=dev)
-    rc = lib.c2_loglik_grad_composite(_i64(B), _i64(N), _i64(J), _p(t), _i64(_bs(t, N)), _p(c), _i64(_bs(c, J)), _p(a),
-                                      _p(U), _p(V), _p(y), _p(ll), _p(bt), _p(bc), _p(ba), _p(bU), _p(bV), _p(by),
-                                      _p(flag), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+    ll, = _empty(dev, dims, "B")
+    flag = _flag(B, dev)
+    rc = lib.c2_loglik_grad_composite(B, N, J, t, _bs(t, N), c, _bs(c, J), a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work,
+                                      work.numel() * 8, _stream())
     _lib.check(rc, "loglik_grad_composite")
     return ll, out, flag
 
@@ -1025,26 +989,23 @@ def term_coefficients(program, P, B=None, *, out=None, flag=None, shift=None, wo
     _shape("P", P, (program.NP,), (B, program.NP))
     dev = P.device
     Jr, Jc = program.Jr, program.Jc
-    shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4
+    dims = dict(B=B, R=Jr, C=Jc)
     if out is None:
-        out = [torch.empty(sh, dtype=torch.float64, device=dev) for sh in shapes]
+        out = list(_empty(dev, dims, *_COEFS))
     else:
-        _chk(*out)
-        for nm, o, sh in zip(("ar", "cr", "ac", "bc", "cc", "dc"), out, shapes):
-            _shape(nm, o, sh)
-    flag = torch.empty(B, dtype=torch.int32, device=dev) if flag is None else flag
+        _args(dims, zip(("ar", "cr", "ac", "bc", "cc", "dc"), out, _COEFS))
+    flag = _flag(B, dev) if flag is None else flag
     if isinstance(program, TermExpr):
-        shift = torch.empty(B, dtype=torch.float64, device=dev) if shift is None else shift
+        shift = _empty(dev, dims, "B")[0] if shift is None else shift
         work = program.workspace(B, dev) if work is None else work
         _chk(shift, work)
         _shape("shift", shift, (B,))
-        rc = _lib.load().c2_term_expr_coefficients(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
-                                                   *_coef_ptrs(*out, Jr, Jc), _p(shift), _p(flag), _p(work),
-                                                   ctypes.c_size_t(work.numel() * 8), _stream())
+        rc = _lib.load().c2_term_expr_coefficients(ctypes.byref(program._c), B, P, _bs(P, program.NP), *_coef_ptrs(*out, Jr, Jc),
+                                                   shift, flag, work, work.numel() * 8, _stream())
         _lib.check(rc, "term_expr_coefficients")
         return tuple(out), flag, shift
-    rc = _lib.load().c2_term_coefficients(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
-                                          *_coef_ptrs(*out, Jr, Jc), _p(flag), _stream())
+    rc = _lib.load().c2_term_coefficients(ctypes.byref(program._c), B, P, _bs(P, program.NP), *_coef_ptrs(*out, Jr, Jc), flag,
+                                          _stream())
     _lib.check(rc, "term_coefficients")
     return tuple(out), flag
 
@@ -1061,10 +1022,9 @@ def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=N
         raise ValueError("Invalid shape: cotangents (six tensors)")
     B = cot[0].shape[0] if Jr else cot[2].shape[0]
     _shape("P", P, (program.NP,), (B, program.NP))
-    _chk(*cot)
-    for nm, o, w in zip(("bar", "bcr", "bac", "bbc", "bcc", "bdc"), cot, (Jr, Jr, Jc, Jc, Jc, Jc)):
-        _shape(nm, o, (B, w))
-    bP = torch.empty((B, program.NP), dtype=torch.float64, device=P.device) if out is None else out
+    dims = dict(B=B, R=Jr, C=Jc, P=program.NP)
+    _args(dims, zip(("bar", "bcr", "bac", "bbc", "bcc", "bdc"), cot, _COEFS))
+    bP = _empty(P.device, dims, "BP")[0] if out is None else out
     _chk(bP)
     _shape("bP", bP, (B, program.NP))
     for nm, f in (("tflag", tflag), ("lflag", lflag)):
@@ -1075,13 +1035,13 @@ def term_coefficients_rev(program, P, cotangents, *, B=None, tflag=None, lflag=N
         work = program.workspace(B, P.device) if work is None else work
         _chk(bshift, work)
         _shape("bshift", bshift, (B,))
-        rc = _lib.load().c2_term_expr_coefficients_rev(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
-                                                       *_coef_ptrs(*cot, Jr, Jc), _p(bshift), _p(tflag), _p(lflag), _p(ll),
-                                                       _p(bP), _p(work), ctypes.c_size_t(work.numel() * 8), _stream())
+        rc = _lib.load().c2_term_expr_coefficients_rev(ctypes.byref(program._c), B, P, _bs(P, program.NP),
+                                                       *_coef_ptrs(*cot, Jr, Jc), bshift, tflag, lflag, ll, bP, work,
+                                                       work.numel() * 8, _stream())
         _lib.check(rc, "term_expr_coefficients_rev")
         return bP
-    rc = _lib.load().c2_term_coefficients_rev(ctypes.byref(program._c), _i64(B), _p(P), _i64(_bs(P, program.NP)),
-                                              *_coef_ptrs(*cot, Jr, Jc), _p(tflag), _p(lflag), _p(ll), _p(bP), _stream())
+    rc = _lib.load().c2_term_coefficients_rev(ctypes.byref(program._c), B, P, _bs(P, program.NP),
+                                              *_coef_ptrs(*cot, Jr, Jc), tflag, lflag, ll, bP, _stream())
     _lib.check(rc, "term_coefficients_rev")
     return bP
 
@@ -1093,11 +1053,9 @@ def noise_mean_apply(yerr, jitter, mean, y, *, yerr_is_sigma=True, out=None):
         raise ValueError("Invalid shape: y (must be (B, N))")
     B, N = y.shape
     diag, r = (torch.empty_like(y), torch.empty_like(y)) if out is None else out
-    _chk(yerr, jitter, mean, y, diag, r)
-    _shape("yerr", yerr, (B, N)); _shape("jitter", jitter, (B,)); _shape("mean", mean, (B,))
-    _shape("diag", diag, (B, N)); _shape("r", r, (B, N))
-    rc = _lib.load().c2_noise_mean_apply(_i64(B), _i64(N), _p(yerr), ctypes.c_int(1 if yerr_is_sigma else 0), _p(jitter),
-                                         _p(mean), _p(y), _p(diag), _p(r), _stream())
+    _args(dict(B=B, N=N), [("yerr", yerr, "BN"), ("jitter", jitter, "B"), ("mean", mean, "B"), ("y", y, "BN"), ("diag", diag, "BN"),
+                           ("r", r, "BN")])
+    rc = _lib.load().c2_noise_mean_apply(B, N, yerr, bool(yerr_is_sigma), jitter, mean, y, diag, r, _stream())
     _lib.check(rc, "noise_mean_apply")
     return diag, r
 
@@ -1108,12 +1066,12 @@ def noise_mean_rev(jitter, bdiag, by, *, flag=None, out=None):
     if by.dim() != 2:
         raise ValueError("Invalid shape: by (must be (B, N))")
     B, N = by.shape
-    bj, bm = (torch.empty(B, dtype=torch.float64, device=by.device) for _ in range(2)) if out is None else out
-    _chk(jitter, bdiag, by, bj, bm)
-    _shape("jitter", jitter, (B,)); _shape("bdiag", bdiag, (B, N)); _shape("bjitter", bj, (B,)); _shape("bmean", bm, (B,))
+    dims = dict(B=B, N=N)
+    bj, bm = _empty(by.device, dims, "B", "B") if out is None else out
+    _args(dims, [("jitter", jitter, "B"), ("bdiag", bdiag, "BN"), ("by", by, "BN"), ("bjitter", bj, "B"), ("bmean", bm, "B")])
     if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (B,)):
         raise ValueError("Invalid shape: flag (must be (B,) int32)")
-    rc = _lib.load().c2_noise_mean_rev(_i64(B), _i64(N), _p(jitter), _p(bdiag), _p(by), _p(flag), _p(bj), _p(bm), _stream())
+    rc = _lib.load().c2_noise_mean_rev(B, N, jitter, bdiag, by, flag, bj, bm, _stream())
     _lib.check(rc, "noise_mean_rev")
     return bj, bm
 
@@ -1125,11 +1083,9 @@ def noise_mean_shift_apply(yerr, jitter, mean, shift, y, *, yerr_is_sigma=True, 
         raise ValueError("Invalid shape: y (must be (B, N))")
     B, N = y.shape
     diag, r = (torch.empty_like(y), torch.empty_like(y)) if out is None else out
-    _chk(yerr, jitter, mean, shift, y, diag, r)
-    _shape("yerr", yerr, (B, N)); _shape("jitter", jitter, (B,)); _shape("mean", mean, (B,)); _shape("shift", shift, (B,))
-    _shape("diag", diag, (B, N)); _shape("r", r, (B, N))
-    rc = _lib.load().c2_noise_mean_shift_apply(_i64(B), _i64(N), _p(yerr), ctypes.c_int(1 if yerr_is_sigma else 0), _p(jitter),
-                                               _p(mean), _p(shift), _p(y), _p(diag), _p(r), _stream())
+    _args(dict(B=B, N=N), [("yerr", yerr, "BN"), ("jitter", jitter, "B"), ("mean", mean, "B"), ("shift", shift, "B"), ("y", y, "BN"),
+                           ("diag", diag, "BN"), ("r", r, "BN")])
+    rc = _lib.load().c2_noise_mean_shift_apply(B, N, yerr, bool(yerr_is_sigma), jitter, mean, shift, y, diag, r, _stream())
     _lib.check(rc, "noise_mean_shift_apply")
     return diag, r
 
@@ -1140,15 +1096,14 @@ def noise_mean_shift_rev(jitter, bdiag, by, *, flag=None, tflag=None, out=None):
     if by.dim() != 2:
         raise ValueError("Invalid shape: by (must be (B, N))")
     B, N = by.shape
-    bj, bm, bs = (torch.empty(B, dtype=torch.float64, device=by.device) for _ in range(3)) if out is None else out
-    _chk(jitter, bdiag, by, bj, bm, bs)
-    _shape("jitter", jitter, (B,)); _shape("bdiag", bdiag, (B, N))
-    _shape("bjitter", bj, (B,)); _shape("bmean", bm, (B,)); _shape("bshift", bs, (B,))
+    dims = dict(B=B, N=N)
+    bj, bm, bs = _empty(by.device, dims, "B", "B", "B") if out is None else out
+    _args(dims, [("jitter", jitter, "B"), ("bdiag", bdiag, "BN"), ("by", by, "BN"), ("bjitter", bj, "B"), ("bmean", bm, "B"),
+                 ("bshift", bs, "B")])
     for f in (flag, tflag):
         if f is not None and (f.dtype != torch.int32 or tuple(f.shape) != (B,)):
             raise ValueError("Invalid shape: flag (must be (B,) int32)")
-    rc = _lib.load().c2_noise_mean_shift_rev(_i64(B), _i64(N), _p(jitter), _p(bdiag), _p(by), _p(flag), _p(tflag), _p(bj),
-                                             _p(bm), _p(bs), _stream())
+    rc = _lib.load().c2_noise_mean_shift_rev(B, N, jitter, bdiag, by, flag, tflag, bj, bm, bs, _stream())
     _lib.check(rc, "noise_mean_shift_rev")
     return bj, bm, bs
 
@@ -1157,14 +1112,14 @@ def loglik_kernel_workspace(program, B, N, device):
     """Caller-owned buffers of loglik_kernel_grad, reusable across calls of the same shape (and required for graph capture):
     a dict with the scratch of loglik_terms_grad, the six coefficient arrays and their cotangents, diag, r and the term flag;
     for a TermExpr also the diagonal shift, its cotangent and the register buffer of the coefficient kernels."""
-    f64 = dict(dtype=torch.float64, device=device)
     Jr, Jc = program.Jr, program.Jc
-    shapes = [(B, Jr)] * 2 + [(B, Jc)] * 4
-    work = {"terms": loglik_terms_workspace(B, N, Jr, Jc, device), "coefs": [torch.empty(sh, **f64) for sh in shapes],
-            "cots": [torch.empty(sh, **f64) for sh in shapes], "diag": torch.empty((B, N), **f64),
-            "r": torch.empty((B, N), **f64), "tflag": torch.empty(B, dtype=torch.int32, device=device)}
+    dims = dict(B=B, N=N, R=Jr, C=Jc)
+    diag, r = _empty(device, dims, "BN", "BN")
+    work = {"terms": loglik_terms_workspace(B, N, Jr, Jc, device), "coefs": list(_empty(device, dims, *_COEFS)),
+            "cots": list(_empty(device, dims, *_COEFS)), "diag": diag, "r": r, "tflag": _flag(B, device)}
     if isinstance(program, TermExpr):
-        work.update(shift=torch.empty(B, **f64), bshift=torch.empty(B, **f64), expr=program.workspace(B, device))
+        shift, bshift = _empty(device, dims, "B", "B")
+        work.update(shift=shift, bshift=bshift, expr=program.workspace(B, device))
     return work
 
 
@@ -1185,10 +1140,8 @@ def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=Tr
     dev = y.device
     if work is None:
         work = loglik_kernel_workspace(program, B, N, dev)
-    f64 = dict(dtype=torch.float64, device=dev)
     if out is None:
-        out = (torch.empty((B, program.NP), **f64), torch.empty(B, **f64), torch.empty(B, **f64), torch.empty((B, N), **f64),
-               torch.empty((B, N), **f64), torch.empty((B, N), **f64))
+        out = _empty(dev, dict(B=B, N=N, P=program.NP), "BP", "B", "B", "BN", "BN", "BN")
     bP, bj, bm, bx, bdiag, by = out
     if isinstance(program, TermExpr):
         coefs, tflag, shift = term_coefficients(program, P, B, out=work["coefs"], flag=work["tflag"], shift=work["shift"],
