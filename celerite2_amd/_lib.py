@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""ctypes binding of the C-ABI (include/celerite2_amd.h).
+"""ctypes binding of the C-ABI (include/celerite2_amd.h and include/celerite2_amd_linear.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # override: A/B builds.  Whatever library is chosen, it is bound with THIS tree's header (the ABI of an A/B pair is one).
 LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.so"))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # = build.INCLUDE: the build is in-tree
+LINEAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_linear.h")   # linear mean models
 
 
 class BackendError(RuntimeError):
@@ -40,11 +41,12 @@ _CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const 
                               "c2_stream_t", "const char **", "const c2_term_program *", "const c2_term_expr *"), Pointer))
 
 
-def _header():
-    """include/celerite2_amd.h without its comments."""
-    if not os.path.exists(HEADER):
-        raise BackendError("celerite2_amd: %s not found -- the Python binding takes its prototypes from it" % HEADER)
-    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+def _header(path=None):
+    """A public header (default: include/celerite2_amd.h) without its comments."""
+    path = HEADER if path is None else path
+    if not os.path.exists(path):
+        raise BackendError("celerite2_amd: %s not found -- the Python binding takes its prototypes from it" % path)
+    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
 
 
 def _ctype(text, name):
@@ -88,6 +90,9 @@ SYMBOLS = [
     "c2h_get_celerite_matrices", "c2h_release_thread_cache",
     "c2_set_option", "c2_get_option", "c2_option_count", "c2_option_info", "c2_options_reload_env",
 ]
+
+# Every symbol include/celerite2_amd_linear.h declares (checked by tests/test_linear_model.py).
+LINEAR_SYMBOLS = ["c2_whitened_gram"]
 
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
@@ -151,7 +156,9 @@ def load():
     except Exception:  # pragma: no cover - torch is plumbing, not required for the C-ABI itself
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _prototypes(_header()).items():
+    protos = _prototypes(_header())
+    protos.update(_prototypes(_header(LINEAR_HEADER)))
+    for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)
         setattr(lib, name, ctypes.CFUNCTYPE(restype, *argtypes)((name, lib), ((1,),) * len(argtypes)))

@@ -12,16 +12,21 @@ objective, through `inverse_diag` and its reverse sweep (csrc/c2_invdiag_rev.hip
 `predict_mean[_kernel]` is the conditional mean at new times as a differentiable function of everything it depends on,
 through `general_matmul_lower` / `general_matmul_upper` and their reverse sweep (csrc/c2_general_rev.hip).
 
+`whitened_gram`, `gls` and `marginal_log_likelihood_kernel` are linear mean models under the GP noise model: the Q x Q
+Gram matrix [A | y]^T (K + D)^-1 [A | y] in one forward sweep (csrc/c2_gram.hip), generalized least squares on it, and the
+likelihood with the linear coefficients profiled or marginalised out.
+
 `factor`, `solve_lower`, `solve_upper`, `matmul_lower`, `matmul_upper` are the reference's five differentiable ops
 (python/celerite2/pymc/ops.py:61-141, jax/ops.py:33-172: forward = `backprop.<op>_fwd` with its workspace, gradient =
 `backprop.<op>_rev`), batched, on the device kernels -- for models that compose the ops themselves."""
+import collections
 import math
 
 import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "whitened_gram", "gls", "marginal_log_likelihood_kernel", "LinearFit", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -608,3 +613,154 @@ def predictive_log_density_kernel(kernel, x, y, t, ys, *, yerr=None, diag=None, 
         noise = j2 if noise is None else noise + j2
     rs = ys if mean is None else ys - mean[:, None]
     return predictive_log_density(x, c, a, U, V, r, t, Us, Vs, k0, rs, noise)
+
+
+class _WhitenedGram(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, c, U, W, d, A, y):
+        args = [None if x is None else x.detach().contiguous() for x in (t, c, U, W, d, A, y)]
+        S = ops.whitened_gram(*args)
+        ctx.hy = y is not None
+        ctx.save_for_backward(*[x for x in args if x is not None])
+        return S
+
+    @staticmethod
+    def backward(ctx, bS):
+        t, c, U, W, d, A, *rest = ctx.saved_tensors
+        B, N, P = U.shape[0], U.shape[1], A.shape[-1]
+        Y = torch.cat([A.expand(B, N, P)] + [y[..., None] for y in rest], dim=-1).contiguous()
+        Z, F = ops.solve_lower(t, c, U, W, Y, workspace=True)
+        bZ = torch.matmul(Z, bS + bS.transpose(1, 2)) / d[..., None]
+        bd = -(torch.matmul(Z, bS) * Z).sum(dim=-1) / (d * d)
+        bt, bc, bU, bW, bY = ops.solve_lower_rev(t, c, U, W, Y, Z, F, bZ.contiguous())
+        return (_reduce(bt, t), _reduce(bc, c), bU, bW, bd, _reduce(bY[..., :P], A), bY[..., P] if ctx.hy else None)
+
+
+def whitened_gram(t, c, U, W, d, A, y=None):
+    """S (B, Q, Q) = [A | y]^T (K + D)^-1 [A | y] from the factors (d, W) of `factor`, differentiable in every argument.
+    A (N, P) shared by the batch | (B, N, P); y (B, N) | None (Q = P + 1 with y, its column last).  The forward call is the
+    fused sweep (c2_whitened_gram: S accumulates in registers, L^-1 [A | y] is never written) and keeps only its inputs.
+    The backward pass is composed from reverses that exist: it recomputes Z = solve_lower([A | y]) with its workspace, then
+    bZ = Z (bS + bS^T) / d, bd_n = -(z_n^T bS z_n) / d_n^2 and solve_lower_rev; a shared t / c / A receives the batch sum.
+    J <= 32 and Q <= 32."""
+    return _WhitenedGram.apply(t, c, U, W, d, A, y)
+
+
+LinearFit = collections.namedtuple("LinearFit", "beta cov log_likelihood marginal_log_likelihood")
+
+# A Cholesky pivot of H below this fraction of H's own diagonal entry: the column is a combination of those before it to
+# twelve digits, the coefficients keep fewer than four -- H counts as rank-deficient.
+_RANK_TOL = 1e-12
+
+
+def _linear_fit(S, log_det, N, prior_mean=None, prior_precision=None, ok=None):
+    """`gls` on the Gram matrix S (B, P + 1, P + 1) of [A | y - A mu0], log_det (B,) = sum log d and the series length N:
+    (LinearFit, bad) with bad (B,) marking the series whose H = S_AA + Lambda is not positive definite or is
+    rank-deficient (_RANK_TOL).  `ok` (B,) | None: series to take at all (the others count as bad; their S is not read).
+    Plain torch on (B, Q, Q) arrays, differentiable; bad series hold NaN / -inf."""
+    B, Q = S.shape[0], S.shape[-1]
+    P = Q - 1
+    eye = torch.eye(P, dtype=S.dtype, device=S.device)
+    if ok is not None:
+        S = torch.where(ok[:, None, None], S, torch.eye(Q, dtype=S.dtype, device=S.device))
+    S_AA, s_Ay, s_yy = S[:, :P, :P], S[:, :P, P], S[:, P, P]
+    H = S_AA if prior_precision is None else S_AA + prior_precision
+    Lc, info = torch.linalg.cholesky_ex(H)
+    bad = info != 0
+    bad = bad | ~((torch.diagonal(Lc, dim1=-2, dim2=-1) ** 2 > _RANK_TOL * torch.diagonal(H, dim1=-2, dim2=-1)).all(dim=-1))
+    if ok is not None:
+        bad = bad | ~ok
+    if bool(bad.any()):   # (the solves below stay finite: a bad series is solved against the identity, then overwritten)
+        Lc = torch.where(bad[:, None, None], eye, Lc)
+    delta = torch.cholesky_solve(s_Ay[..., None], Lc)[..., 0]
+    cov = torch.cholesky_solve(eye.expand(B, P, P), Lc)
+    beta = delta if prior_mean is None else prior_mean + delta
+    ll = -0.5 * (s_yy - (s_Ay * delta).sum(dim=-1)) - 0.5 * log_det - 0.5 * N * math.log(2.0 * math.pi)
+    log_det_H = 2.0 * torch.log(torch.diagonal(Lc, dim1=-2, dim2=-1)).sum(dim=-1)
+    if prior_precision is None:
+        mll = ll - 0.5 * log_det_H + 0.5 * P * math.log(2.0 * math.pi)
+    else:
+        mll = ll - 0.5 * log_det_H + 0.5 * torch.linalg.slogdet(prior_precision)[1]
+    if bool(bad.any()):
+        nan = torch.full((), math.nan, dtype=S.dtype, device=S.device)
+        ninf = torch.full((), -math.inf, dtype=S.dtype, device=S.device)
+        beta, cov = torch.where(bad[:, None], nan, beta), torch.where(bad[:, None, None], nan, cov)
+        ll, mll = torch.where(bad, ninf, ll), torch.where(bad, ninf, mll)
+    return LinearFit(beta, cov, ll, mll), bad
+
+
+def _check_design(A, B, N, prior_mean, prior_precision):
+    """"Invalid shape: A" and the prior's shapes; returns P."""
+    if A.dim() not in (2, 3) or tuple(A.shape[-2:-1]) != (N,) or (A.dim() == 3 and A.shape[0] != B) or A.shape[-1] < 1:
+        raise ValueError("Invalid shape: A %s (must be (N, P) or (B, N, P) with (B, N) = %s, P >= 1)" % (tuple(A.shape), (B, N)))
+    P = A.shape[-1]
+    if prior_mean is not None and tuple(prior_mean.shape) not in ((P,), (B, P)):
+        raise ValueError("Invalid shape: prior_mean %s (must be (P,) or (B, P))" % (tuple(prior_mean.shape),))
+    if prior_precision is not None and tuple(prior_precision.shape) not in ((P, P), (B, P, P)):
+        raise ValueError("Invalid shape: prior_precision %s (must be (P, P) or (B, P, P))" % (tuple(prior_precision.shape),))
+    return P
+
+
+def _prior_residual(y, A, prior_mean):
+    """r = y - A mu0 (one matmul), y itself without a prior mean."""
+    return y if prior_mean is None else y - torch.matmul(A, prior_mean[..., None])[..., 0]
+
+
+def gls(t, c, a, U, V, A, y, *, prior_mean=None, prior_precision=None):
+    """Generalized least squares of y (B, N) on the design matrix A ((N, P) shared | (B, N, P)) under the covariance
+    (t, c, a, U, V): LinearFit(beta (B, P), cov (B, P, P), log_likelihood (B,), marginal_log_likelihood (B,)),
+    differentiable in every tensor argument.  The chain `factor` -> `whitened_gram` -> torch on (B, Q, Q): a batched P x P
+    Cholesky, outside the hot path.  With S_AA, s_Ay, s_yy the blocks of the Gram matrix of [A | r], r = y - A mu0,
+    mu0 = prior_mean ((P,) | (B, P)), Lambda = prior_precision ((P, P) | (B, P, P)) and H = S_AA + Lambda (a flat prior:
+    mu0 = 0, Lambda = 0):
+
+        beta = mu0 + H^-1 s_Ay,      cov = H^-1
+        log_likelihood          = -(s_yy - s_Ay^T H^-1 s_Ay) / 2 - sum log d / 2 - N log(2 pi) / 2
+        marginal_log_likelihood = log_likelihood - logdet H / 2 + logdet Lambda / 2          (Gaussian prior)
+                                = log_likelihood - logdet S_AA / 2 + P log(2 pi) / 2         (flat prior)
+
+    `log_likelihood` is the profiled one: log N(y | A beta, K + D) at beta under a flat prior; with a Gaussian prior the
+    same expression carries the prior's quadratic term -(beta - mu0)^T Lambda (beta - mu0) / 2 at beta.  The Gaussian-prior
+    marginal is log N(y | A mu0, K + D + A Lambda^-1 A^T).  Raises LinAlgError when a factorisation fails (as `factor`) or
+    an H is not positive definite to twelve digits (rank-deficient A); `.flag` marks the series.  J <= 32 and P <= 31."""
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B, N = y.shape
+    _check_design(A, B, N, prior_mean, prior_precision)
+    d, W = factor(t, c, a, U, V)
+    S = whitened_gram(t, c, U, W, d, A, _prior_residual(y, A, prior_mean))
+    fit, bad = _linear_fit(S, torch.log(d).sum(dim=1), N, prior_mean, prior_precision)
+    if bool(bad.any()):
+        err = LinAlgError("failed to factorize or solve matrix (rank-deficient design matrix)")
+        err.flag = bad.to(torch.int32)
+        raise err
+    return fit
+
+
+def marginal_log_likelihood_kernel(kernel, x, y, A, *, yerr=None, diag=None, jitter=None, mean=None, prior_mean=None,
+                                   prior_precision=None, profiled=False):
+    """The log-likelihood (B,) of y (B, N) at x under `kernel` plus a LINEAR mean model mean + A beta, with the coefficients
+    beta marginalised out (`profiled=False`: `gls`'s marginal_log_likelihood, under the Gaussian prior (prior_mean,
+    prior_precision) or a flat one) or set to their generalized-least-squares value (`profiled=True`: its log_likelihood) --
+    a differentiable function of the HYPER-PARAMETERS alone, with `predict_mean_kernel`'s conventions (tensor parameters of
+    `kernel`, TermExpr kernels with their diagonal shift, `jitter` in quadrature, `mean` subtracted).  Differentiable in the
+    parameters, jitter, mean, y, A, x (and yerr | diag, the prior).  The chain term_coefficients -> get_celerite_matrices ->
+    `gls`.  A TermConvolution is allowed: only the factored matrix is used.  Raises LinAlgError as `gls`.  J <= 32, P <= 31."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, N) is required")
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B, N = y.shape
+    _check_design(A, B, N, prior_mean, prior_precision)
+    if not kernel._has_tensors():
+        raise TypeError("marginal_log_likelihood_kernel: the kernel has no tensor parameter (give its parameters as device tensors)")
+    ar, cr, ac, bc, cc, dc, shift = term_coefficients(kernel.program, kernel.parameter_matrix(B), B, with_shift=True)
+    D = (yerr * yerr if diag is None else diag) + shift[:, None]
+    jitter, mean = _per_series(jitter, B, y), _per_series(mean, B, y)
+    if jitter is not None:
+        D = D + (jitter * jitter)[:, None]
+    r = y if mean is None else y - mean[:, None]
+    c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
+    a, U, V = get_celerite_matrices(ar, ac, bc, dc, x, D)
+    fit = gls(x, c, a, U, V, A, r, prior_mean=prior_mean, prior_precision=prior_precision)
+    return fit.log_likelihood if profiled else fit.marginal_log_likelihood

@@ -8,13 +8,16 @@ reductions; apply_inverse -> solve_lower, /d, solve_upper; dot_tril; sample; the
 via apply_inverse on the N x M cross-covariance (solves with M right-hand sides).  Everything stays on the GPU.
 `log_likelihood_and_grad` exposes the fused kernels' gradients w.r.t. (t, c, a, U, V, y).
 """
+import collections
 import math
 
 import torch
 
 from . import ops
 
-__all__ = ["GaussianProcess", "ConditionalDistribution", "LinAlgError"]
+__all__ = ["GaussianProcess", "ConditionalDistribution", "LinearModelFit", "LinAlgError"]
+
+LinearModelFit = collections.namedtuple("LinearModelFit", "beta cov log_likelihood marginal_log_likelihood residual")
 
 
 class LinAlgError(Exception):
@@ -253,6 +256,55 @@ class GaussianProcess:
         self._check_vector(y)
         return autograd.predictive_log_density_kernel(self.kernel, self._t, y, t, ys, diag=self._diag, jitter=jitter,
                                                       mean=self.mean, yerr_new=yerr_new)
+
+    # -- linear mean models in linear time (ops.whitened_gram; no counterpart in the reference) --------------------
+    def _linear(self, y, A, prior_mean, prior_precision):
+        """(LinearFit, r, A) on the stored factors: r = y - mean - A mu0, S from one forward sweep, the rest on (B, Q, Q)."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        B, N = self._diag.shape
+        autograd._check_design(A, B, N, prior_mean, prior_precision)
+        r = autograd._prior_residual(y - self.mean, A, prior_mean)
+        S = ops.whitened_gram(self._t, self._c, self._U, self._W, self._d, A.contiguous(), r.contiguous())
+        fit, _ = autograd._linear_fit(S, self._log_det, N, prior_mean, prior_precision, ok=self._flag == 0)
+        return fit, r
+
+    def fit_linear(self, y, A, *, prior_mean=None, prior_precision=None):
+        """Generalized least squares of `y` on the design matrix `A` ((N, P) shared | (B, N, P)) under the factored
+        covariance: the model y = mean + A beta + GP.  Returns LinearModelFit(beta (B, P), cov (B, P, P), log_likelihood (B,),
+        marginal_log_likelihood (B,), residual (B, N)) -- autograd.gls's LinearFit (its docstring has the formulas and the
+        Gaussian prior `prior_mean` (P,) | (B, P), `prior_precision` (P, P) | (B, P, P); flat without) plus
+        residual = y - mean - A beta.  One forward sweep over the stored factors that never writes L^-1 [A | y]
+        (ops.whitened_gram), then a P x P Cholesky per series.  The stochastic part of the data is then
+
+            gp.predict(fit.residual + gp.mean, t)
+
+        Not differentiable (`marginal_log_likelihood_kernel` is) and never raising under compute(..., quiet=True): a series
+        whose factorisation failed or whose A is rank-deficient holds NaN beta / cov / residual and -inf likelihoods.
+        J <= 32, P <= 31."""
+        fit, r = self._linear(y, A, prior_mean, prior_precision)
+        delta = fit.beta if prior_mean is None else fit.beta - prior_mean
+        return LinearModelFit(*fit, r - torch.matmul(A, delta[..., None])[..., 0])
+
+    def marginal_log_likelihood(self, y, A, *, prior_mean=None, prior_precision=None, profiled=False):
+        """(B,): the log-likelihood of `y` under mean + A beta + GP with beta marginalised out under the Gaussian prior
+        (prior_mean, prior_precision), or a flat one -- `fit_linear`'s marginal_log_likelihood (`profiled=True`: its
+        log_likelihood, at the fitted beta).  -inf for a failed or rank-deficient series."""
+        fit, _ = self._linear(y, A, prior_mean, prior_precision)
+        return fit.log_likelihood if profiled else fit.marginal_log_likelihood
+
+    def marginal_log_likelihood_kernel(self, y, A, *, jitter=None, prior_mean=None, prior_precision=None, profiled=False):
+        """`marginal_log_likelihood` as a differentiable function of the kernel's tensor hyper-parameters, of `jitter`, of a
+        tensor `mean`, of `y` and of `A`: autograd.marginal_log_likelihood_kernel on this GP's t, diag and mean (the
+        coefficient-level chain, not the matrices `compute` factored; it raises LinAlgError where this class gives -inf)."""
+        from . import autograd
+
+        self._need()
+        self._check_vector(y)
+        return autograd.marginal_log_likelihood_kernel(self.kernel, self._t, y, A, diag=self._diag, jitter=jitter, mean=self.mean,
+                                                       prior_mean=prior_mean, prior_precision=prior_precision, profiled=profiled)
 
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):

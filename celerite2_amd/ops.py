@@ -25,6 +25,8 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
+# (`whitened_gram`, the op of include/celerite2_amd_linear.h, is public as well; it is listed with its header's symbols,
+# _lib.LINEAR_SYMBOLS, and this list stays the ops of include/celerite2_amd.h)
 
 
 def _p(x):
@@ -407,6 +409,27 @@ def dot_tril(t, c, U, W, d, Y, Z=None):
     rc = _lib.load().c2_dot_tril(B, N, J, nrhs, t, _bs(t, N), c, _bs(c, J), U, W, d, Y, Z, _stream())
     _lib.check(rc, "dot_tril")
     return Z
+
+
+def whitened_gram(t, c, U, W, d, A, y=None, S=None):
+    """S (B, Q, Q) = [A | y]^T (K + D)^-1 [A | y] from the factors (d, W) of `factor`, in one forward sweep that keeps S in
+    registers and never writes L^-1 [A | y] (c2_whitened_gram, csrc/c2_gram.hip).  A (N, P) shared by the batch or (B, N, P);
+    y (B, N) or None: Q = P + 1 with y (its column last), P without.  Both triangles are stored and equal to the bit.
+    Caller-owned `S` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.
+    J <= 32 and Q <= 32.  No atomics: two calls give identical bits."""
+    B, N, J = _dims(U)
+    if A.dim() not in (2, 3):
+        raise ValueError("Invalid shape: A (must be (N, P) or (B, N, P))")
+    P = A.shape[-1]
+    dims = dict(B=B, N=N, J=J, P=P, Q=P + (y is not None))
+    if S is None:
+        S, = _empty(U.device, dims, "BQQ")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("A", A, "NP|BNP"), ("y", y, "BN")],
+          [("S", S, "BQQ")])
+    rc = _lib.load().c2_whitened_gram(B, N, J, P, t, _bs(t, N), c, _bs(c, J), U, W, d, A, 0 if A.dim() == 2 else N * P, y, S,
+                                      _stream())
+    _lib.check(rc, "whitened_gram")
+    return S
 
 
 _KRON_METHODS = {"collapsed": 0, "interleaved": 1}
