@@ -13,7 +13,10 @@
 //
 // Aliasing is preserved end to end: two host arguments with the same address
 // share ONE device buffer, so d == a, W == V, Z == Y exercise the kernels'
-// in-place behaviour exactly as the reference's in-place calls do.  Outputs whose
+// in-place behaviour exactly as the reference's in-place calls do.  Inputs that
+// start at the same address and differ in length (views of one array: t1 = x[:k]
+// with t2 = x) share the longer extent, staged once, and read what copies would;
+// an OUTPUT on such a view is the one call that is refused (Staging::map, commit).  Outputs whose
 // unwritten elements must keep the caller's contents (rows after a failed
 // factorisation, workspace rows the merge never visits, accumulated Z) are
 // uploaded first; outputs the kernels overwrite completely (the S / F
@@ -83,7 +86,8 @@ constexpr size_t kBounceMax = 64u << 20;    // beyond this, arguments go up one 
 struct Staging {
   struct Entry {
     const void *host;
-    size_t bytes, off;
+    size_t bytes, off;   // bytes: the longest of the arguments that start at `host`
+    size_t shortest;     // ... and the shortest of them
     bool out;
     bool fresh;   // a pure output the kernels overwrite completely: laid out behind everything else, never uploaded
   };
@@ -100,16 +104,23 @@ struct Staging {
     return true;
   }
   // Register a host array; returns its handle (shared when the host pointer repeats).  -1: absent.
+  // Arguments that start at the same address share ONE staged extent, the longest of them, and each points at its start.
+  // Equal lengths are the reference's in-place calls (d == a, W == V, Z == Y).  Unequal lengths are views of one array
+  // that begin at its first element (t1 = x[:k] with t2 = x; ar, ac cut from one coefficient vector): as inputs they read
+  // exactly what a copy of the shorter one would, whichever is registered first.  An OUTPUT on such an extent is refused
+  // (commit): the reference would read, through the longer view, rows this call has already written through the shorter
+  // one (or the reverse) -- a result that depends on its row order and that no staged copy reproduces.
   int map(const void *host, size_t bytes, bool is_output, bool fresh = false) {
     if (host == nullptr) return -1;
     for (size_t i = 0; i < entries.size(); ++i)
       if (entries[i].host == host) {
         entries[i].out = entries[i].out || is_output;
         entries[i].fresh = entries[i].fresh && fresh;        // (aliased with an input or an in/out array: it is read)
-        if (bytes > entries[i].bytes) err = C2_ERR_INVALID;  // overlapping-but-different views are not supported
+        if (bytes > entries[i].bytes) entries[i].bytes = bytes;
+        if (bytes < entries[i].shortest) entries[i].shortest = bytes;
         return (int)i;
       }
-    entries.push_back({host, bytes, 0, is_output, is_output && fresh});
+    entries.push_back({host, bytes, 0, bytes, is_output, is_output && fresh});
     return (int)entries.size() - 1;
   }
   int in(const double *h, int64_t n) { return map(h, sizeof(double) * (size_t)n, false); }
@@ -124,6 +135,7 @@ struct Staging {
   // Sizes are known: lay the arrays out, grow the arena, ONE upload.
   bool commit() {
     committed = true;
+    for (auto &e : entries) if (e.out && e.shortest != e.bytes) err = C2_ERR_INVALID;   // an output on a view of another length
     if (err) return false;
     for (auto &e : entries) if (!e.out) { e.off = in_bytes; in_bytes += up(e.bytes ? e.bytes : 8); }
     for (auto &e : entries) if (e.out && !e.fresh) { e.off = in_bytes + io_bytes; io_bytes += up(e.bytes ? e.bytes : 8); }

@@ -62,7 +62,8 @@ inline double *mptr(const py::buffer_info &b) { return (double *)b.ptr; }
 // Translate a C-ABI status into the exception a caller of the reference would see.
 inline void check(int rc) {
   if (rc == C2_OK) return;
-  if (rc == C2_ERR_INVALID) throw std::invalid_argument("Invalid shape: empty or inconsistent dimensions");
+  if (rc == C2_ERR_INVALID) throw std::invalid_argument(
+        "Invalid shape: empty or inconsistent dimensions, or an output that starts at the address of an argument of another length");
   if (rc == C2_ERR_UNSUPPORTED)
     throw std::invalid_argument("celerite2_amd: J exceeds the supported width (C2_MAX_WIDTH = 128)");
   throw std::runtime_error(std::string("celerite2_amd: HIP error (is an MI355X visible?): ") + c2_last_error());

@@ -22,9 +22,18 @@
  *     8-byte aligned, and that is all an entry point asks for: 16-byte
  *     alignment selects faster kernels and never changes results beyond
  *     rounding (a view that starts at an odd element is a valid argument).
- *   - Exact-pointer aliasing the reference allows is allowed here too:
- *     d == a and W == V for factor (forward.hpp:55-58), Z == Y for
- *     solve_* / matmul_* (numpy.py:95-108).
+ *   - Aliasing.  Exact-pointer aliasing the reference allows is allowed here
+ *     too: d == a and W == V for factor (forward.hpp:55-58), Z == Y for
+ *     solve_* / matmul_* (numpy.py:95-108).  The c2h_* host entry points also
+ *     take INPUTS that are views of one array: two inputs that start at the
+ *     same address and differ in length (t1 = x[:k] with t2 = x; ar and ac cut
+ *     from the front of one coefficient vector) behave exactly as if the
+ *     shorter one were a copy, in either argument order; views that start at
+ *     different addresses are staged separately, as copies would be.  The one
+ *     call they refuse (C2_ERR_INVALID) is an OUTPUT that starts at the
+ *     address of an argument of another length: the reference would read
+ *     rows the same call has already overwritten, a result that follows its
+ *     row order and that no staged copy reproduces.
  *   - Return value: C2_OK (0) or a negative C2_ERR_* code.  A non positive
  *     definite matrix is NOT an error code: `flag[b]` receives the first row
  *     index n >= 1 with d[n] <= 0, or 0 on success (forward.hpp:128,134), and

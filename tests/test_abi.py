@@ -109,6 +109,55 @@ def test_fails_loudly_without_gpu(built):
         driver.factor(t, np.ones(J), np.ones(N), np.zeros((N, J)), np.zeros((N, J)), np.ones(N), np.zeros((N, J)))
 
 
+def test_views_of_one_array_pass_argument_bookkeeping(built):
+    """Arguments that are views of ONE array and start at its first element share a host address and differ in length
+    (conditioning on x, predicting at x[:k]; coefficient arrays cut from one vector).  The reference takes such calls, so
+    the staging layer must: without a device each of them gets as far as the device (RuntimeError naming the HIP error),
+    not ValueError -- whichever of the two comes first, and for a tail view, which has an address of its own."""
+    from celerite2_amd import _lib, backprop, driver
+
+    if _lib.load().c2_device_count() > 0:
+        pytest.skip("a GPU is visible here")
+    hip = dict(match=r"HIP error[^:]*: \S")
+    n, k, J, nrhs = 10, 4, 2, 1
+    x = np.linspace(0, 1, n)
+    c = np.ones(J)
+    for t1, t2 in ((x[:k], x), (x, x[:k]), (x[n - k:], x), (x, x[n - k:]), (x[::1], x)):
+        assert t1.flags.c_contiguous and t2.flags.c_contiguous
+        N, M = len(t1), len(t2)
+        U, V, Y = np.ones((N, J)), np.ones((M, J)), np.ones((M, nrhs))
+        for lower in ("general_matmul_lower", "general_matmul_upper"):
+            with pytest.raises(RuntimeError, **hip):
+                getattr(driver, lower)(t1, t2, c, U, V, Y, np.zeros((N, nrhs)))
+            with pytest.raises(RuntimeError, **hip):
+                getattr(backprop, lower + "_fwd")(t1, t2, c, U, V, Y, np.zeros((N, nrhs)), np.zeros((M, J, nrhs)))
+    co = np.linspace(0.1, 1.0, 8)
+    N = 5
+    for Jr, Jc in ((1, 3), (3, 1), (2, 2)):
+        Jw = Jr + 2 * Jc
+        for ar, ac, bc, dc in ((co[:Jr], co[:Jc], co[:Jc], co[:Jc]),                    # all four from the front
+                               (co[:Jr], co[Jr:Jr + Jc], co[:Jc], co[Jr:Jr + Jc]),      # front and middle, mixed
+                               (co[8 - Jr:], co[:Jc], co[8 - Jc:], co[:Jc])):           # tails among them
+            with pytest.raises(RuntimeError, **hip):
+                driver.get_celerite_matrices(ar, ac, bc, dc, x[:N], np.ones(N), np.empty(N), np.empty((N, Jw)), np.empty((N, Jw)))
+
+
+def test_output_on_a_view_of_another_length_is_refused(built):
+    """The one refusal the staging layer keeps (include/celerite2_amd.h, "Aliasing"): an OUTPUT that starts at the address
+    of an argument of another length.  The reference would read rows this very call has already overwritten, which no
+    staged copy reproduces; the call is refused before anything touches the device, in either argument order."""
+    from celerite2_amd import driver
+
+    n, k, J = 10, 4, 2
+    x = np.linspace(0, 1, n)
+    buf = np.ones((n, 1))
+    U, V, c = np.ones((k, J)), np.ones((n, J)), np.ones(J)
+    with pytest.raises(ValueError, match="Invalid shape"):
+        driver.general_matmul_lower(x[:k], x, c, U, V, buf, buf[:k])       # Z on the first rows of Y
+    with pytest.raises(ValueError, match="Invalid shape"):
+        driver.general_matmul_lower(x, x[:k], c, V, U, buf[:k], buf)       # Y on the first rows of Z
+
+
 def test_every_entry_point_names_its_hip_error(built):
     """C2_ERR_HIP never comes without text: without a device every device entry point, handed valid small host arrays
     (B = 1, N = 4, J = 2, one right-hand side and eight; nothing is launched, so they are never dereferenced), returns

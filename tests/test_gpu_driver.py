@@ -7,6 +7,7 @@ through the host C-ABI (c2h_*) and additionally compare against the CPU oracle a
 import numpy as np
 import pytest
 
+import host_layout
 from oracle import dense
 
 pytestmark = pytest.mark.gpu
@@ -205,8 +206,14 @@ def test_wide_model_through_the_drop_in(mods, oracle):
     Z2 = driver.matmul_lower(x, c, U, V, Y, np.zeros_like(Y))
     _close(Z2, np.tril(K, -1) @ Y, 1e-9)
     for op, ref in (("matmul_lower", np.tril(K - np.diag(diag), -1) @ Y), ("matmul_upper", np.triu(K - np.diag(diag), 1) @ Y)):
-        # *_fwd zeroes Z itself (backprop.cpp: Z.setZero()): a NaN-filled output buffer must come back clean, first row included
-        Zf, Ff = getattr(backprop, op + "_fwd")(x, c, U, V, Y, np.full_like(Y, np.nan), np.full((N, J, 3), np.nan))
+        # *_fwd zeroes Z itself (backprop.cpp: Z.setZero()): a NaN-filled Z -- which is uploaded -- must come back clean, first row
+        # included.  F is never uploaded, so NaN in the caller's F would prove nothing: the NaN go where F will lie in the
+        # staging arena (host_layout.poison), and every element of F must come back written
+        args = [x, c, U, V, Y, np.full_like(Y, np.nan), np.empty((N, J, 3))]
+        lay = host_layout.layout(host_layout.entries("sweep", *args))
+        host_layout.poison(lay["upload"], lay["total"])
+        Zf, Ff = getattr(backprop, op + "_fwd")(*args)
+        assert np.isfinite(Zf).all() and np.isfinite(Ff).all()
         _close(Zf, ref, 1e-9)
         Zo = np.empty_like(Y); Fo = np.empty((N, J, 3))
         getattr(oracle, op + "_fwd")(x, c, U, V, Y, Zo, Fo)
