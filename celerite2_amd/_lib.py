@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""ctypes binding of the C-ABI (include/celerite2_amd.h and include/celerite2_amd_linear.h).
+"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h and celerite2_amd_periodogram.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.so"))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # = build.INCLUDE: the build is in-tree
 LINEAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_linear.h")   # linear mean models
+PERIODOGRAM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_periodogram.h")   # the periodogram
 
 
 class BackendError(RuntimeError):
@@ -36,7 +37,7 @@ class Pointer(ctypes.c_void_p):
 
 
 # The C types of the header's prototypes (parameters and return values).  A prototype that uses another one fails at load.
-_CTYPES = {"void": None, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+_CTYPES = {"void": None, "int": ctypes.c_int, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
 _CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const int32_t *", "int *", "int64_t *", "void *",
                               "c2_stream_t", "const char **", "const c2_term_program *", "const c2_term_expr *"), Pointer))
 
@@ -93,6 +94,9 @@ SYMBOLS = [
 
 # Every symbol include/celerite2_amd_linear.h declares (checked by tests/test_linear_model.py).
 LINEAR_SYMBOLS = ["c2_whitened_gram"]
+
+# Every symbol include/celerite2_amd_periodogram.h declares (checked by tests/test_periodogram.py).
+PERIODOGRAM_SYMBOLS = ["c2_whitened_sinusoids"]
 
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
@@ -158,6 +162,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     protos = _prototypes(_header())
     protos.update(_prototypes(_header(LINEAR_HEADER)))
+    protos.update(_prototypes(_header(PERIODOGRAM_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

@@ -306,6 +306,51 @@ class GaussianProcess:
         return autograd.marginal_log_likelihood_kernel(self.kernel, self._t, y, A, diag=self._diag, jitter=jitter, mean=self.mean,
                                                        prior_mean=prior_mean, prior_precision=prior_precision, profiled=profiled)
 
+    # -- the periodogram under the factored covariance (ops.whitened_sinusoids; no counterpart in the reference) -------
+    def periodogram(self, y, freq, *, A="mean", normalization="standard", t_ref=0.0, return_fit=False):
+        """The generalized Lomb-Scargle periodogram of `y` (B, N) under the factored covariance, (B, F): for each ANGULAR trial
+        frequency of `freq` ((F,) shared | (B, F)) the model y = mean + A beta0 + alpha cos w(t - t_ref) + beta sin w(t - t_ref)
+        + GP is fitted by generalized least squares and compared with the fit without the sinusoid (chi2_null - chi2 = dchi2).
+        `A`: the nuisance columns -- "mean" (a column of ones: the floating-mean periodogram), None (none), or a design
+        matrix (N, P0) | (B, N, P0) with P0 <= 7.  `normalization`: "standard" (dchi2 / chi2_null, in [0, 1]), "chi2" (dchi2)
+        or "log_likelihood" (dchi2 / 2, the log-likelihood ratio at fixed hyper-parameters).  `return_fit=True`:
+        periodogram.Periodogram(power (B, F), amplitude (B, F, 2) = (alpha, beta), chi2_null (B,)).
+        One solve_lower with P0 + 1 columns, one sweep with a lane per frequency (ops.whitened_sinusoids), then torch on
+        (B, F, .) arrays (celerite2_amd/periodogram.py has the formulas).  Not differentiable and never raising under
+        compute(..., quiet=True): a frequency at which the sinusoid is not identifiable (w = 0 beside a constant column),
+        a series whose factorisation failed or whose A is rank-deficient, and every frequency when N < P0 + 3 hold NaN.
+        Times with a large offset keep their phase accuracy with `t_ref` at the offset.  J <= 32."""
+        from . import periodogram as pg
+
+        self._need()
+        self._check_vector(y)
+        B, N = self._diag.shape
+        if normalization not in pg.NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
+        if not torch.is_tensor(freq) or freq.dim() not in (1, 2) or (freq.dim() == 2 and freq.shape[0] != B) or freq.shape[-1] < 1:
+            raise ValueError("Invalid shape: freq (must be (F,) or (B, F) with B = %d, F >= 1)" % B)
+        r = (y - self.mean)[..., None]
+        if A is None:
+            Y0 = r
+        else:
+            if isinstance(A, str):
+                if A != "mean":
+                    raise ValueError("A must be \"mean\", None or a design matrix")
+                A = torch.ones((N, 1), dtype=torch.float64, device=self._diag.device)
+            if A.dim() not in (2, 3) or tuple(A.shape[-2:-1]) != (N,) or (A.dim() == 3 and A.shape[0] != B) \
+                    or not 1 <= A.shape[-1] <= 7:
+                raise ValueError("Invalid shape: A %s (must be (N, P0) or (B, N, P0) with (B, N) = %s, 1 <= P0 <= 7)"
+                                 % (tuple(A.shape), (B, N)))
+            Y0 = torch.cat([A.expand(B, N, A.shape[-1]), r], dim=-1)
+        Z0 = ops.solve_lower(self._t, self._c, self._U, self._W, Y0.contiguous())
+        T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq.contiguous(), t_ref=t_ref)
+        fit = pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0)
+        F = T.shape[1]
+        power, amplitude, chi2_null = self._nan_failed(fit.power, fit.amplitude.reshape(B, 2 * F), fit.chi2_null[:, None])
+        if not return_fit:
+            return power
+        return pg.Periodogram(power, amplitude.reshape(B, F, 2), chi2_null[:, 0])
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

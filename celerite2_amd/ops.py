@@ -25,8 +25,9 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
-# (`whitened_gram`, the op of include/celerite2_amd_linear.h, is public as well; it is listed with its header's symbols,
-# _lib.LINEAR_SYMBOLS, and this list stays the ops of include/celerite2_amd.h)
+# (`whitened_gram` and `whitened_sinusoids`, the ops of include/celerite2_amd_linear.h and celerite2_amd_periodogram.h, are
+# public as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS and _lib.PERIODOGRAM_SYMBOLS, and this
+# list stays the ops of include/celerite2_amd.h)
 
 
 def _p(x):
@@ -430,6 +431,34 @@ def whitened_gram(t, c, U, W, d, A, y=None, S=None):
                                       _stream())
     _lib.check(rc, "whitened_gram")
     return S
+
+
+def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
+    """T (B, F, 3 + 2 Q0): for every series and every ANGULAR trial frequency freq ((F,) shared by the batch or (B, F)), with
+    z_c = L^-1 cos(w (t - t_ref)), z_s = L^-1 sin(w (t - t_ref)) and <a, b> = sum_n a_n b_n / d_n,
+
+        T[b, f] = [<z_c, z_c>, <z_c, z_s>, <z_s, z_s>, <z_c, Z0[:, k]> for k < Q0, <z_s, Z0[:, k]> for k < Q0]
+
+    from the factors (d, W) of `factor` and Z0 (B, N, Q0) = solve_lower of [A0 | y - mean], in one forward sweep that forms the
+    two columns in registers, one lane per frequency (c2_whitened_sinusoids, csrc/c2_periodogram.hip; the header has the rule
+    for the phase).  What the periodogram under correlated noise reads (celerite2_amd/periodogram.py).  Caller-owned `out` is
+    accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.
+    No atomics: two calls give identical bits."""
+    B, N, J = _dims(U)
+    if Z0.dim() != 3:
+        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
+    if freq.dim() not in (1, 2):
+        raise ValueError("Invalid shape: freq (must be (F,) or (B, F))")
+    Q0, F = Z0.shape[-1], freq.shape[-1]
+    dims = dict(B=B, N=N, J=J, Q=Q0, F=F, K=3 + 2 * Q0)
+    if out is None:
+        out, = _empty(U.device, dims, "BFK")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
+                 ("freq", freq, "F|BF")], [("out", out, "BFK")])
+    rc = _lib.load().c2_whitened_sinusoids(B, N, J, Q0, F, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, freq, _bs(freq, F),
+                                           float(t_ref), out, _stream())
+    _lib.check(rc, "whitened_sinusoids")
+    return out
 
 
 _KRON_METHODS = {"collapsed": 0, "interleaved": 1}
