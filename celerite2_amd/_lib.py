@@ -1,5 +1,6 @@
 # -*- coding: utf-8 -*-
-"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h and celerite2_amd_periodogram.h).
+"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h and
+celerite2_amd_transit.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -14,6 +15,7 @@ LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.s
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # = build.INCLUDE: the build is in-tree
 LINEAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_linear.h")   # linear mean models
 PERIODOGRAM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_periodogram.h")   # the periodogram
+TRANSIT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_transit.h")   # the transit search
 
 
 class BackendError(RuntimeError):
@@ -98,6 +100,9 @@ LINEAR_SYMBOLS = ["c2_whitened_gram"]
 # Every symbol include/celerite2_amd_periodogram.h declares (checked by tests/test_periodogram.py).
 PERIODOGRAM_SYMBOLS = ["c2_whitened_sinusoids"]
 
+# Every symbol include/celerite2_amd_transit.h declares (checked by tests/test_transit.py).
+TRANSIT_SYMBOLS = ["c2_whitened_transits"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -163,6 +168,7 @@ def load():
     protos = _prototypes(_header())
     protos.update(_prototypes(_header(LINEAR_HEADER)))
     protos.update(_prototypes(_header(PERIODOGRAM_HEADER)))
+    protos.update(_prototypes(_header(TRANSIT_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

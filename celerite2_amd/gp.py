@@ -306,6 +306,25 @@ class GaussianProcess:
         return autograd.marginal_log_likelihood_kernel(self.kernel, self._t, y, A, diag=self._diag, jitter=jitter, mean=self.mean,
                                                        prior_mean=prior_mean, prior_precision=prior_precision, profiled=profiled)
 
+    def _whitened_columns(self, y, A):
+        """Z0 (B, N, P0 + 1) = L^-1 [A0 | y - mean] for the nuisance columns `A` of periodogram and transit_search: "mean" (a
+        column of ones), None (none) or a design matrix (N, P0) | (B, N, P0) with P0 <= 7."""
+        B, N = self._diag.shape
+        r = (y - self.mean)[..., None]
+        if A is None:
+            Y0 = r
+        else:
+            if isinstance(A, str):
+                if A != "mean":
+                    raise ValueError("A must be \"mean\", None or a design matrix")
+                A = torch.ones((N, 1), dtype=torch.float64, device=self._diag.device)
+            if A.dim() not in (2, 3) or tuple(A.shape[-2:-1]) != (N,) or (A.dim() == 3 and A.shape[0] != B) \
+                    or not 1 <= A.shape[-1] <= 7:
+                raise ValueError("Invalid shape: A %s (must be (N, P0) or (B, N, P0) with (B, N) = %s, 1 <= P0 <= 7)"
+                                 % (tuple(A.shape), (B, N)))
+            Y0 = torch.cat([A.expand(B, N, A.shape[-1]), r], dim=-1)
+        return ops.solve_lower(self._t, self._c, self._U, self._W, Y0.contiguous())
+
     # -- the periodogram under the factored covariance (ops.whitened_sinusoids; no counterpart in the reference) -------
     def periodogram(self, y, freq, *, A="mean", normalization="standard", t_ref=0.0, return_fit=False):
         """The generalized Lomb-Scargle periodogram of `y` (B, N) under the factored covariance, (B, F): for each ANGULAR trial
@@ -329,20 +348,7 @@ class GaussianProcess:
             raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
         if not torch.is_tensor(freq) or freq.dim() not in (1, 2) or (freq.dim() == 2 and freq.shape[0] != B) or freq.shape[-1] < 1:
             raise ValueError("Invalid shape: freq (must be (F,) or (B, F) with B = %d, F >= 1)" % B)
-        r = (y - self.mean)[..., None]
-        if A is None:
-            Y0 = r
-        else:
-            if isinstance(A, str):
-                if A != "mean":
-                    raise ValueError("A must be \"mean\", None or a design matrix")
-                A = torch.ones((N, 1), dtype=torch.float64, device=self._diag.device)
-            if A.dim() not in (2, 3) or tuple(A.shape[-2:-1]) != (N,) or (A.dim() == 3 and A.shape[0] != B) \
-                    or not 1 <= A.shape[-1] <= 7:
-                raise ValueError("Invalid shape: A %s (must be (N, P0) or (B, N, P0) with (B, N) = %s, 1 <= P0 <= 7)"
-                                 % (tuple(A.shape), (B, N)))
-            Y0 = torch.cat([A.expand(B, N, A.shape[-1]), r], dim=-1)
-        Z0 = ops.solve_lower(self._t, self._c, self._U, self._W, Y0.contiguous())
+        Z0 = self._whitened_columns(y, A)
         T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq.contiguous(), t_ref=t_ref)
         fit = pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0)
         F = T.shape[1]
@@ -350,6 +356,38 @@ class GaussianProcess:
         if not return_fit:
             return power
         return pg.Periodogram(power, amplitude.reshape(B, F, 2), chi2_null[:, 0])
+
+    # -- the transit search under the factored covariance (ops.whitened_transits; no counterpart in the reference) -----
+    def transit_search(self, y, trials, *, A="mean", return_fit=False):
+        """Box least squares of `y` (B, N) under the factored covariance, (B, K): for each trial (period P, epoch t0,
+        duration w, ingress tau) of `trials` ((K, 4) shared | (B, K, 4); transit.trial_grid makes a folded grid) the model
+        y = mean + A beta0 + delta b_k(t) + GP is fitted by generalized least squares and compared with the fit without the
+        template (chi2_null - chi2 = delta_chi2).  b_k is a box (tau = 0) or a trapezoid of full width w with ramps of length
+        tau, +1 in transit, folded at P or a single event at t0 when P = 0 (include/celerite2_amd_transit.h has the rule): a
+        dip has a negative depth.  `A`: the nuisance columns, as for `periodogram`.  `return_fit=True`:
+        transit.TransitSearch(delta_chi2, depth, depth_err, snr (each (B, K)), chi2_null (B,)).
+        One solve_lower with P0 + 1 columns, one sweep with a lane per trial (ops.whitened_transits), then torch on (B, K, .)
+        arrays (celerite2_amd/transit.py has the formulas).  Not differentiable and never raising under
+        compute(..., quiet=True): a trial with no sample in transit, one whose template lies in the span of A, one outside
+        w > 0, 0 <= tau <= w / 2, P >= 0, w <= P (P > 0), a series whose factorisation failed or whose A is rank-deficient, and
+        every trial when N < P0 + 2 hold NaN.  A TermConvolution kernel is accepted: only the factored matrix is used.
+        J <= 32."""
+        from . import periodogram as pg, transit as tr
+
+        self._need()
+        self._check_vector(y)
+        B, N = self._diag.shape
+        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
+                or trials.shape[-1] != 4 or trials.shape[-2] < 1:
+            raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4) with B = %d, K >= 1)" % B)
+        trials = trials.contiguous()
+        Z0 = self._whitened_columns(y, A)
+        T = ops.whitened_transits(self._t, self._c, self._U, self._W, self._d, Z0, trials)
+        fit = tr.finish(pg.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials)
+        *per_trial, chi2_null = self._nan_failed(*fit[:4], fit.chi2_null[:, None])
+        if not return_fit:
+            return per_trial[0]
+        return tr.TransitSearch(*per_trial, chi2_null[:, 0])
 
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):

@@ -25,9 +25,10 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
-# (`whitened_gram` and `whitened_sinusoids`, the ops of include/celerite2_amd_linear.h and celerite2_amd_periodogram.h, are
-# public as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS and _lib.PERIODOGRAM_SYMBOLS, and this
-# list stays the ops of include/celerite2_amd.h)
+# (`whitened_gram`, `whitened_sinusoids` and `whitened_transits`, the ops of include/celerite2_amd_linear.h,
+# celerite2_amd_periodogram.h and celerite2_amd_transit.h, are public as well; they are listed with their headers' symbols,
+# _lib.LINEAR_SYMBOLS, _lib.PERIODOGRAM_SYMBOLS and _lib.TRANSIT_SYMBOLS, and this list stays the ops of
+# include/celerite2_amd.h)
 
 
 def _p(x):
@@ -458,6 +459,34 @@ def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
     rc = _lib.load().c2_whitened_sinusoids(B, N, J, Q0, F, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, freq, _bs(freq, F),
                                            float(t_ref), out, _stream())
     _lib.check(rc, "whitened_sinusoids")
+    return out
+
+
+def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
+    """T (B, K, 1 + Q0): for every series and every trial (period P, epoch t0, duration w, ingress tau) of `trials` ((K, 4)
+    shared by the batch or (B, K, 4)), with z = L^-1 b_k(t) and <a, b> = sum_n a_n b_n / d_n,
+
+        T[b, k] = [<z, z>, <z, Z0[:, j]> for j < Q0]
+
+    from the factors (d, W) of `factor` and Z0 (B, N, Q0) = solve_lower of [A0 | y - mean], in one forward sweep that forms
+    the box (tau = 0) or trapezoid template b_k in registers, one lane per trial (c2_whitened_transits, csrc/c2_transit.hip;
+    the header has the rule for the template; P = 0 is a single event, P > 0 folds).  What the transit search under
+    correlated noise reads (celerite2_amd/transit.py).  Caller-owned `out` is accepted (nothing is allocated then: capturable
+    in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two calls give identical bits."""
+    B, N, J = _dims(U)
+    if Z0.dim() != 3:
+        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
+    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
+        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
+    Q0, K = Z0.shape[-1], trials.shape[-2]
+    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=4, R=1 + Q0)
+    if out is None:
+        out, = _empty(U.device, dims, "BKR")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
+                 ("trials", trials, "KF|BKF")], [("out", out, "BKR")])
+    rc = _lib.load().c2_whitened_transits(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
+                                          0 if trials.dim() == 2 else 4 * K, out, _stream())
+    _lib.check(rc, "whitened_transits")
     return out
 
 

@@ -1,0 +1,291 @@
+# -*- coding: utf-8 -*-
+"""What the transit search under correlated noise costs (csrc/c2_transit.hip) beside the only route there was before it, on
+one device, in ONE fresh process:
+
+    python tools/bench_transit.py [--steps 10] [--out profiles/transit_search.md] [--quick]
+    python tools/bench_transit.py --static-only --out profiles/transit_search.md   # no GPU: registers and instruction mix
+
+  fused     ops.solve_lower ([1 | y]) + ops.whitened_transits + transit.finish (torch)
+  kernel    ops.whitened_transits alone (the figure the share of the fp64 rate is taken from)
+  composed  ops.whitened_gram on [1 | b_k ... | y] in chunks of at most 30 trials (Q <= 32), the templates built with torch
+            inside the timed region, then the same finish on the blocks of S
+
+alternating step by step at B x N x J x K = 64 x 4096 x 8 x 4096, 1 x 4096 x 8 x 4096, 1024 x 1024 x 4 x 1024 and
+64 x 4096 x 32 x 512 on folded box trials, every step timed by its own pair of HIP events after a warm-up, plus one run of
+single events sorted by epoch at the first shape (fused and kernel only).  The composed route takes hundreds of launches a
+step and is given fewer steps (--composed-steps).  The two routes' delta_chi2 are compared before timing.
+
+The kernel has no memory floor to quote (O(N K J) arithmetic on O(N J) bytes); its yardstick is the vector fp64 rate, as for
+the periodogram: the static part counts the fp64 VALU instructions of one row of one lane from the compiler's
+own assembly (the ramp's division, which a wavefront skips when no lane is on an ingress or egress, left out), and the timed
+part turns lane-rows per second into a share of 39.3e12 fp64 instructions per lane and second -- the public 78.6 TFLOP/s
+vector fp64 figure of the part counted as fused multiply-adds."""
+import argparse
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+FP64_PEAK = 78.6e12 / 2.0   # fp64 VALU instructions per lane and second
+SHAPES = [(64, 4096, 8, 4096), (1, 4096, 8, 4096), (1024, 1024, 4, 1024), (64, 4096, 32, 512)]
+CHUNK = 30
+TOOL = "tools/bench_transit.py --static-only"
+
+
+def marks(key):
+    return "<!-- %s:begin (%s) -->" % (key, TOOL), "<!-- %s:end -->" % key
+
+
+def register_table():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_regs import kernel_rows
+
+    rows = kernel_rows("c2_transit.o")
+    if not rows:
+        return None
+    lines = ["| kernel | registers (of them accumulation) | SGPRs | LDS bytes | scratch bytes | spilled registers |", "|---|---|---|---|---|---|"]
+    for _, name, vg, ag, scratch, lds, spill, sg in sorted(rows, key=lambda r: [int(v) for v in re.findall(r"\d+", re.sub(r"\(.*", "", r[1]))[-2:]]):
+        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("c2::transit::", "")
+        lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (name, vg, ag, sg, lds, scratch, spill))
+    lines += ["", "Largest scratch %d bytes, %d spilled registers over %d kernels (`k_transits<JR, QR>`: J rounded up to 4, 8, 16 "
+              "or 32, Q0 to 1, 2, 4 or 8)." % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows))]
+    return "\n".join(lines)
+
+
+def row_loop_mix(asm, jr, qr):
+    """(Counter of the instructions one row of one lane issues in k_transits<jr, qr>, Counter of the ramp's block): the
+    innermost loop of the kernel in the compiler's assembly; the forward-skipped region that holds the ramp's division
+    (v_div_fmas_f64) is counted apart."""
+    name = "_ZN2c27transit10k_transitsILi%dELi%dEE" % (jr, qr)
+    i = asm.index("\n" + name) + 1
+    lines = asm[i:asm.index(".Lfunc_end", i)].split("\n")
+    labels = {m.group(1): k for k, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l.strip())] if m}
+    loops = []
+    for k, l in enumerate(lines):
+        m = re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
+        if m and labels.get(m.group(1), k) < k:
+            loops.append((labels[m.group(1)], k))
+    a = max(lp[0] for lp in loops if any("ds_read" in l for l in lines[lp[0]:lp[1]]))   # the innermost header ...
+    b = max(lp[1] for lp in loops if lp[0] == a)                                        # ... and its last back edge
+    skip = set()
+    for k in range(a, b + 1):
+        m = re.search(r"s_cbranch_(?:execz|scc[01]|vccn?z)\s+(\.LBB\d+_\d+)", lines[k])
+        if m and k < labels[m.group(1)] <= b and any("v_div_fmas_f64" in l for l in lines[k:labels[m.group(1)]]):
+            skip.update(range(k + 1, labels[m.group(1)]))
+    # (the compiler may rotate the loop instead: the row's body first, then the template, a conditional branch back to the
+    # body when no lane is on a ramp, and the division falling through to an unconditional branch back)
+    for k in range(a, b + 1):
+        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", lines[k])
+        if m and labels[m.group(1)] == a and k < b and any("v_div_fmas_f64" in l for l in lines[k:b + 1]):
+            skip.update(range(k + 1, b + 1))
+    is_ins = lambda l: l.strip() and not l.strip().startswith((";", ".")) and not l.strip().endswith(":")
+    row = collections.Counter(lines[k].split()[0] for k in range(a, b + 1) if k not in skip and is_ins(lines[k]))
+    ramp = collections.Counter(lines[k].split()[0] for k in sorted(skip) if is_ins(lines[k]))
+    return row, ramp
+
+
+def fp64_valu(c):
+    return {k: v for k, v in c.items() if k.startswith("v_") and "_f64" in k}
+
+
+def instruction_table():
+    """The row loop's instruction mix per width, from a device-only compile of the kernel with the build's own flags."""
+    from celerite2_amd import build
+
+    if not os.path.exists(build.HIPCC):
+        return None
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "c2_transit.s")
+        flags = [f for f in build.HIPFLAGS if f not in ("-shared", "-fPIC")]
+        subprocess.run([build.HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "c2_transit.hip"), "-o", out], check=True)
+        asm = open(out).read()
+    lines = ["| kernel | instructions a row | fp64 VALU | of them fma / mul / add / other | other VALU | LDS reads (b128 / b64 / other) | scalar | the ramp's block (fp64 VALU / all) |",
+             "|---|---|---|---|---|---|---|---|"]
+    per_row = {}
+    for jr, qr in ((4, 2), (8, 2), (16, 2), (32, 2), (8, 1), (8, 8)):
+        c, ramp = row_loop_mix(asm, jr, qr)
+        f64 = fp64_valu(c)
+        fma = sum(v for k, v in f64.items() if "fma" in k)
+        mul, add = sum(v for k, v in f64.items() if k.startswith("v_mul")), sum(v for k, v in f64.items() if k.startswith("v_add"))
+        valu = sum(v for k, v in c.items() if k.startswith("v_"))
+        lds = sum(v for k, v in c.items() if k.startswith("ds_"))
+        if qr == 2:
+            per_row[jr] = sum(f64.values())
+        lines.append("| `k_transits<%d, %d>` | %d | %d | %d / %d / %d / %d | %d | %d / %d / %d | %d | %d / %d |"
+                     % (jr, qr, sum(c.values()), sum(f64.values()), fma, mul, add, sum(f64.values()) - fma - mul - add,
+                        valu - sum(f64.values()), c.get("ds_read_b128", 0), c.get("ds_read_b64", 0),
+                        lds - c.get("ds_read_b128", 0) - c.get("ds_read_b64", 0), sum(v for k, v in c.items() if k.startswith("s_")),
+                        sum(fp64_valu(ramp).values()), sum(ramp.values())))
+    lines += ["", "One row of one lane (one trial), the path a wavefront takes when no lane is on an ingress or egress (box trials "
+              "always); the last column is the block with the ramp's division, entered by a wavefront with at least one such lane.  "
+              "fp64 VALU per lane-row, machine-readable: " + " ".join("JR%d=%d" % kv for kv in sorted(per_row.items()))]
+    return "\n".join(lines)
+
+
+def with_block(text, key, table, title):
+    begin, end = marks(key)
+    table = table or "(neither the built objects nor the compiler are on this machine: run `python %s --out <this file>` where the library was built)" % TOOL
+    block = begin + "\n" + table + "\n" + end
+    if begin in text and end in text:
+        head, rest = text.split(begin, 1)
+        return head + block + rest.split(end, 1)[1]
+    return text + "\n## %s\n\n" % title + block + "\n"
+
+
+def kept_block(text, key):
+    begin, end = marks(key)
+    return text.split(begin, 1)[1].split(end, 1)[0].strip("\n") if begin in text and end in text else None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--composed-steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal of the script, not a measurement)")
+    ap.add_argument("--static-only", action="store_true")
+    a = ap.parse_args()
+    old = open(a.out).read() if a.out and os.path.exists(a.out) else ""
+    if a.static_only:
+        text = with_block(old, "registers", register_table(), "Registers (gfx950, from the built objects)")
+        text = with_block(text, "instructions", instruction_table(), "The row loop (gfx950, from the compiler's assembly)")
+        if a.out:
+            open(a.out, "w").write(text)
+        print(text)
+        return
+
+    import torch
+    from celerite2_amd import ops, periodogram as pg, synth, transit as tr
+
+    assert torch.cuda.is_available(), "this measures the GPU: there is nothing to fall back to"
+    dev = torch.device("cuda:0")
+    per_row = dict((int(k), int(v)) for k, v in re.findall(r"JR(\d+)=(\d+)", kept_block(old, "instructions") or ""))
+
+    def stats(ms):
+        ms = sorted(ms)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def alternate(runs, steps):
+        """runs: name -> (fn, steps or None)."""
+        for k, (fn, n) in runs.items():
+            for _ in range(a.warmup if n is None else 1):
+                fn()
+        # events made beforehand and ONE synchronise at the end: the device never idles between steps
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n or steps)]
+              for k, (fn, n) in runs.items()}
+        torch.cuda.synchronize()
+        for i in range(steps):
+            for k, (fn, n) in runs.items():
+                if i < len(ev[k]):
+                    ev[k][i][0].record()
+                    fn()
+                    ev[k][i][1].record()
+        torch.cuda.synchronize()
+        return {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
+
+    lines = ["# gp.transit_search's route beside ops.whitened_gram in chunks of %d trials" % CHUNK, "",
+             "One process, steps alternating between the routes, %d timed steps each (composed: %d) after %d warm-up steps "
+             "(composed: 1); ms: median (min .. max).  Trials: folded boxes (periods from a fiftieth to a third of the baseline, "
+             "durations 2 %% of the period, epochs uniform over the baseline), shared by the batch; \"single\": single events of "
+             "1 %% of the baseline sorted by epoch over the baseline (no composed route timed).  The routes' delta_chi2 are compared before "
+             "timing (neither is a reference: the worst distance in units of the standing criterion is listed under the table).  "
+             "Share of the fp64 rate: lane-rows a second (B N K) times the fp64 VALU instructions of a lane-row (the table below) "
+             "over 39.3e12." % (a.steps, a.composed_steps, a.warmup), "",
+             "| B x N x J x K | trials | route | ms | lane-rows / s | share of the vector fp64 rate | fused / composed |", "|---|---|---|---|---|---|---|"]
+    agree = []
+    shapes = [s + ("folded",) for s in (SHAPES if not a.quick else [(8, 256, 8, 100), (4, 128, 32, 40)])]
+    shapes.insert(1, shapes[0][:4] + ("single",))
+    for B, N, J, K, kind in shapes:
+        t, c, av, U, V, y = synth.device_batch_fast(0, B, N, J, dev)
+        d, W, flag = ops.factor(t, c, av, U, V)
+        t_lo, span = float(t.min()), float(t.max() - t.min())
+        gen = torch.Generator(device="cpu").manual_seed(1)
+        if kind == "folded":
+            P = span / torch.linspace(3.0, 50.0, K, dtype=torch.float64)
+            trials = torch.stack([P, t_lo + span * torch.rand(K, dtype=torch.float64, generator=gen), 0.02 * P, torch.zeros_like(P)], dim=1)
+        else:
+            one = torch.ones(K, dtype=torch.float64)
+            trials = torch.stack([0.0 * one, t_lo + span * torch.linspace(0.0, 1.0, K, dtype=torch.float64), 0.01 * span * one, 0.0 * one], dim=1)
+        trials = trials.to(dev).contiguous()
+        Y0 = torch.stack([torch.ones_like(y), y], dim=-1).contiguous()
+        Z0, T = torch.empty_like(Y0), torch.empty((B, K, 3), dtype=torch.float64, device=dev)
+        ok = flag == 0
+        chunks = [(lo, min(lo + CHUNK, K)) for lo in range(0, K, CHUNK)]
+        T2 = torch.empty_like(T)
+        A = torch.empty((B, N, 1 + CHUNK), dtype=torch.float64, device=dev)
+        S = torch.empty((B, 2 + CHUNK, 2 + CHUNK), dtype=torch.float64, device=dev)
+        zero, one_ = torch.zeros((), dtype=torch.float64, device=dev), torch.ones((), dtype=torch.float64, device=dev)
+        res = {}
+
+        def fused():
+            ops.solve_lower(t, c, U, W, Y0, Z=Z0)
+            ops.whitened_transits(t, c, U, W, d, Z0, trials, out=T)
+            res["fused"] = tr.finish(pg.null_products(Z0, d), T, N, ok=ok, trials=trials).delta_chi2
+
+        def kernel():
+            ops.whitened_transits(t, c, U, W, d, Z0, trials, out=T)
+
+        def composed():
+            S0 = None
+            for lo, hi in chunks:
+                n = hi - lo
+                P, t0, w, tau = [trials[lo:hi, i] for i in range(4)]
+                x = t[:, :, None] - t0
+                phi = x - torch.round(x * torch.where(P != 0, 1.0 / P, zero)) * P
+                u = 0.5 * w - phi.abs()
+                Ac, Sc = (A, S) if n == CHUNK else (torch.empty((B, N, 1 + n), dtype=torch.float64, device=dev),
+                                                    torch.empty((B, 2 + n, 2 + n), dtype=torch.float64, device=dev))
+                Ac[..., 0] = 1.0
+                Ac[..., 1:] = torch.where(u >= tau, one_, torch.where(u >= 0, u / tau, zero))
+                ops.whitened_gram(t, c, U, W, d, Ac, y, S=Sc)
+                k, q = torch.arange(1, 1 + n, device=dev), 1 + n
+                T2[:, lo:hi, 0], T2[:, lo:hi, 1], T2[:, lo:hi, 2] = Sc[:, k, k], Sc[:, k, 0], Sc[:, k, q]
+                S0 = Sc[:, [0, q]][:, :, [0, q]]
+            res["composed"] = tr.finish(S0, T2, N, ok=ok, trials=trials).delta_chi2
+
+        fused()
+        runs = {"fused": (fused, None), "kernel": (kernel, None)}
+        if kind == "folded":
+            composed()
+            torch.cuda.synchronize()
+            p1, p2 = res["fused"], res["composed"]
+            fin = torch.isfinite(p2) & ok[:, None]
+            tol = 1e-10 * p2.abs() + 1e-12 * torch.nan_to_num(p2).abs().amax(dim=1, keepdim=True)
+            worst = float(((p1 - p2).abs() / tol)[fin].max())
+            assert bool(torch.equal(torch.isnan(p1), torch.isnan(p2))) and worst < 1e4, "the two routes disagree: %g" % worst
+            agree.append("%d x %d x %d x %d: %.3g (%d series not factored, %d trials NaN in each)"
+                         % (B, N, J, K, worst, int((~ok).sum()), int(torch.isnan(p1[ok]).sum())))
+            runs["composed"] = (composed, a.composed_steps)
+        out = alternate(runs, a.steps)
+        jr = 4 if J <= 4 else 8 if J <= 8 else 16 if J <= 16 else 32
+        lane_rows = B * N * K
+        for op, st in out.items():
+            rate = lane_rows / (st[0] * 1e-3)
+            share = "%.1f %%" % (100.0 * rate * per_row[jr] / FP64_PEAK) if op == "kernel" and jr in per_row else ""
+            lines.append("| %d x %d x %d x %d | %s | %s | %.3f (%.3f .. %.3f) | %s | %s | %s |"
+                         % (B, N, J, K, kind, op, st[0], st[1], st[2], "%.3g" % rate if op == "kernel" else "", share,
+                            "%.4f" % (out["fused"][0] / out["composed"][0]) if op == "fused" and "composed" in out else ""))
+            print(lines[-1], flush=True)
+        del t, c, av, U, V, y, d, W, trials, Y0, Z0, T, T2, A, S
+        torch.cuda.empty_cache()
+    lines += ["", "Worst |fused - composed| delta_chi2 in units of the standing criterion: " + "; ".join(agree) + "."]
+    text = "\n".join(lines) + "\n"
+    for key, title in (("registers", "Registers (gfx950, from the built objects)"),
+                       ("instructions", "The row loop (gfx950, from the compiler's assembly)")):
+        text = with_block(text, key, kept_block(old, key), title)
+    # whatever follows the generated part of an earlier file (hand-written notes) is kept
+    if "<!-- notes -->" in old:
+        text += "\n<!-- notes -->" + old.split("<!-- notes -->", 1)[1]
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text)
+
+
+if __name__ == "__main__":
+    main()
