@@ -148,19 +148,6 @@ __global__ __launch_bounds__(kWave) void k_gram(int64_t B, int64_t N, int J, int
   }
 }
 
-inline int padded(int64_t n) { return n <= 4 ? 4 : group_size(n); }   // 4, 8, 16 or 32
-
-// f(std::integral_constant<int, R>{}) for R = padded(n)
-template <class F>
-inline void dispatch_padded(int64_t n, F &&f) {
-  switch (padded(n)) {
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    default: f(std::integral_constant<int, 32>{}); break;
-  }
-}
-
 }  // namespace gram
 }  // namespace c2
 

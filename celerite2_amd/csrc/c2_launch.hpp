@@ -29,4 +29,27 @@ inline auto dispatch_group(int64_t J, F &&f) {
   }
 }
 
+// the kernels that keep a J- or Q-long vector in registers pad it to 4, 8, 16 or 32 (k_gram, k_sinusoids, k_transits)
+inline int padded(int64_t n) { return n <= 4 ? 4 : group_size(n); }
+
+// f(std::integral_constant<int, R>{}) for R = padded(n); f(... group_size(n)) for n <= 8 columns (1, 2, 4 or 8)
+template <class F>
+inline void dispatch_padded(int64_t n, F &&f) {
+  switch (padded(n)) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    default: f(std::integral_constant<int, 32>{}); break;
+  }
+}
+template <class F>
+inline void dispatch_columns(int64_t n, F &&f) {
+  switch (group_size(n)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
 }  // namespace c2

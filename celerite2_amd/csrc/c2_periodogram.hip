@@ -19,12 +19,10 @@
 // lanes, one column each (32 frequencies per wavefront), the cosine lane keeps <z_c, .>, the sine lane <z_s, .>, and the
 // one value a row exchanges is the partner's z for <z_c, z_s> (a DPP move inside the quad).  Both forms make the same
 // statements per value, so T does not depend on which one ran.
-// Everything else about a row -- t_n, 1 / d_n, the Z0 row, u_n, w_{n-1}, p_n -- is the same for all 64 lanes: the
-// wavefront stages R rows at a time in LDS, lane (r, j) loading u, w and forming ONE decay factor, and every lane reads the
-// block back by broadcast.  The next block's global loads are issued before a block's rows are swept and staged after them
-// (one wavefront per block, LDS in order: one buffer does).  Lanes with f >= F carry w = 0 and store nothing.  Every
-// element of T is written by exactly one lane: no atomics, two calls give identical bits.  Blocks:
-// B * ceil(F / frequencies per wavefront) in grid.x, the frequency blocks of a series next to each other.
+// Everything else about a row is the same for all 64 lanes and comes staged through LDS, R = 16 rows a block (8 in the
+// two-lane form), by trial::sweep_rows (c2_trial_sweep.hpp); the row body below is this kernel's own.  Lanes with f >= F
+// carry w = 0 and store nothing.  Every element of T is written by exactly one lane: no atomics, two calls give identical
+// bits.  Blocks: B * ceil(F / frequencies per wavefront) in grid.x, the frequency blocks of a series next to each other.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,11 +32,10 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd_periodogram.h"
 #include "c2_launch.hpp"
+#include "c2_trial_sweep.hpp"
 
 namespace c2 {
 namespace pgram {
-
-constexpr int kMaxQ0 = 8;
 
 // x = fl(w * fl(t - t_ref)): the two roundings of the header, kept apart from whatever uses x
 __device__ __forceinline__ double phase(double w, double t, double t_ref) {
@@ -60,18 +57,9 @@ __global__ __launch_bounds__(kWave) void k_sinusoids(int64_t N, int J, int Q0, i
   constexpr bool SPLIT = freqs_per_wave(JR) < kWave;        // a lane holds one column (cos: even lane, sin: odd), not both
   constexpr int NC = SPLIT ? 1 : 2;
   constexpr int R = SPLIT ? 8 : 16;                         // rows per staged block
-  constexpr int RPL = kWave / JR, NV = R / RPL;             // rows one pass of the wavefront covers; passes per block
-  constexpr int NZ = (R * QR + kWave - 1) / kWave;          // passes over the block's Z0 rows
-  __shared__ __attribute__((aligned(16))) double sp[R][JR], sw[R][JR], su[R][JR];
-  __shared__ __attribute__((aligned(16))) double sx[R][2], sz[R][QR];   // sx: (t_n, 1 / d_n)
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x / FB, f = (blockIdx.x % FB) * freqs_per_wave(JR) + (SPLIT ? lane >> 1 : lane);
   const bool sine = SPLIT && (lane & 1);
-  const int j = lane & (JR - 1), r0 = lane / JR;
-  const bool act = j < J;                                    // this lane stages column j of U, W and forms p_j
-  const double *tb = t + b * t_bs, *db = d + b * N, *Zb = Z0 + b * N * Q0;
-  const double *Ub = U + b * N * J + (act ? j : 0), *Wb = W + b * N * J + (act ? j : 0);
-  const double cj = act ? c[b * c_bs + j] : 0.0;
   const double om = f < F ? freq[b * f_bs + f] : 0.0;
 
   // column 0: the cosine's (SPLIT: this lane's own), column 1: the sine's
@@ -85,91 +73,42 @@ __global__ __launch_bounds__(kWave) void k_sinusoids(int64_t N, int J, int Q0, i
     Tsq[a] = z[a] = 0.0;
   }
 
-  // the staged block: what this lane loads for rows n0 + r0, n0 + r0 + RPL, ...
-  double vu[NV], vw[NV], vdt[NV], vt = 0.0, vd = 1.0, vz[NZ];
-  auto vload = [&](int64_t n0) {
+  // one row: sx = (t_n, 1 / d_n) and the staged LDS rows p_n, w_{n-1}, u_n, Z0[n]
+  auto row = [&](const double *sx, const double *sp, const double *sw, const double *su, const double *sz) {
+    const double x = phase(om, sx[0], t_ref), rd = sx[1];
+    double rhs[2];
+    sincos_cw(x, rhs[1], rhs[0]);
+    if (SPLIT) rhs[0] = sine ? rhs[1] : rhs[0];
+    double acc[NC][4];
 #pragma unroll
-    for (int m = 0; m < NV; ++m) {
-      int64_t n = n0 + r0 + m * RPL;
-      n = n < N - 1 ? n : N - 1;
-      const int64_t nm = n > 0 ? n - 1 : 0;                  // (row 0: p = 1 and w_{-1} = 0 leave F at zero)
-      const double u = Ub[n * J], w = Wb[nm * J];            // (an idle lane reads column 0 and drops it)
-      vu[m] = act ? u : 0.0;
-      vw[m] = act && n > 0 ? w : 0.0;
-      vdt[m] = tb[nm] - tb[n];
-    }
-    if (lane < R) {
-      int64_t n = n0 + lane;
-      n = n < N - 1 ? n : N - 1;
-      vt = tb[n]; vd = db[n];
-    }
+    for (int a = 0; a < NC; ++a) acc[a][0] = acc[a][1] = acc[a][2] = acc[a][3] = 0.0;
 #pragma unroll
-    for (int m = 0; m < NZ; ++m) {
-      const int e = lane + m * kWave, k = e % QR;
-      int64_t n = n0 + e / QR;
-      n = n < N - 1 ? n : N - 1;                             // (e >= R * QR: a valid row, not staged)
-      const double z0 = Zb[n * Q0 + (k < Q0 ? k : 0)];
-      vz[m] = k < Q0 ? z0 : 0.0;
-    }
-  };
-  auto vstage = [&]() {
-#pragma unroll
-    for (int m = 0; m < NV; ++m) {
-      const int r = r0 + m * RPL;
-      sp[r][j] = exp_decay(cj * vdt[m]);                     // internal.hpp:139
-      sw[r][j] = vw[m]; su[r][j] = vu[m];
-    }
-    if (lane < R) { sx[lane][0] = vt; sx[lane][1] = rcp_nr(vd); }
-#pragma unroll
-    for (int m = 0; m < NZ; ++m) {
-      const int e = lane + m * kWave;
-      if (R * QR >= (m + 1) * kWave || e < R * QR) sz[e / QR][e % QR] = vz[m];
-    }
-  };
-
-  vload(0);
-  for (int64_t n0 = 0; n0 < N; n0 += R) {
-    lds_order();   // (the rows of the last block are read)
-    vstage();
-    lds_order();
-    if (n0 + R < N) vload(n0 + R);
-    const int rows = N - n0 < R ? (int)(N - n0) : R;
-#pragma unroll 1
-    for (int r = 0; r < rows; ++r) {
-      const double x = phase(om, sx[r][0], t_ref), rd = sx[r][1];
-      double rhs[2];
-      sincos_cw(x, rhs[1], rhs[0]);
-      if (SPLIT) rhs[0] = sine ? rhs[1] : rhs[0];
-      double acc[NC][4];
-#pragma unroll
-      for (int a = 0; a < NC; ++a) acc[a][0] = acc[a][1] = acc[a][2] = acc[a][3] = 0.0;
-#pragma unroll
-      for (int i = 0; i < JR; ++i) {
-        const double p = sp[r][i], w = sw[r][i], u = su[r][i];
-#pragma unroll
-        for (int a = 0; a < NC; ++a) {
-          const double fa = p * fma(w, z[a], Fst[a][i]);   // :140, :143
-          Fst[a][i] = fa;
-          acc[a][i & 3] = fma(fa, u, acc[a][i & 3]);
-        }
-      }
-      double zd[NC];
+    for (int i = 0; i < JR; ++i) {
+      const double p = sp[i], w = sw[i], u = su[i];
 #pragma unroll
       for (int a = 0; a < NC; ++a) {
-        z[a] = rhs[a] - ((acc[a][0] + acc[a][1]) + (acc[a][2] + acc[a][3]));   // :144
-        zd[a] = z[a] * rd;
-        Tsq[a] = fma(z[a], zd[a], Tsq[a]);
-      }
-      // <z_c, z_s> as (z_c / d) z_s: the sine's z is the partner lane's when a lane holds one column (kept by the cosine lane)
-      Tcs = fma(zd[0], SPLIT ? dpp_mov<kDppXor1>(z[0]) : z[NC - 1], Tcs);
-#pragma unroll
-      for (int k = 0; k < QR; ++k) {
-        const double z0 = sz[r][k];
-#pragma unroll
-        for (int a = 0; a < NC; ++a) T0[a][k] = fma(zd[a], z0, T0[a][k]);
+        const double fa = p * fma(w, z[a], Fst[a][i]);   // :140, :143
+        Fst[a][i] = fa;
+        acc[a][i & 3] = fma(fa, u, acc[a][i & 3]);
       }
     }
-  }
+    double zd[NC];
+#pragma unroll
+    for (int a = 0; a < NC; ++a) {
+      z[a] = rhs[a] - ((acc[a][0] + acc[a][1]) + (acc[a][2] + acc[a][3]));   // :144
+      zd[a] = z[a] * rd;
+      Tsq[a] = fma(z[a], zd[a], Tsq[a]);
+    }
+    // <z_c, z_s> as (z_c / d) z_s: the sine's z is the partner lane's when a lane holds one column (kept by the cosine lane)
+    Tcs = fma(zd[0], SPLIT ? dpp_mov<kDppXor1>(z[0]) : z[NC - 1], Tcs);
+#pragma unroll
+    for (int k = 0; k < QR; ++k) {
+      const double z0 = sz[k];
+#pragma unroll
+      for (int a = 0; a < NC; ++a) T0[a][k] = fma(zd[a], z0, T0[a][k]);
+    }
+  };
+  trial::sweep_rows<JR, QR, R>(N, J, Q0, b, t, t_bs, c, c_bs, U, W, d, Z0, row);
 
   if (f < F) {
     double *Tb = T + (b * F + f) * (3 + 2 * Q0);
@@ -184,28 +123,6 @@ __global__ __launch_bounds__(kWave) void k_sinusoids(int64_t N, int J, int Q0, i
   }
 }
 
-inline int padded(int64_t n) { return n <= 4 ? 4 : group_size(n); }   // 4, 8, 16 or 32 (as c2_gram.hip's dispatch_padded)
-
-// f(std::integral_constant<int, R>{}) for R = padded(n); f(... group_size(n)) for the columns of Z0 (1, 2, 4 or 8)
-template <class Fn>
-inline void dispatch_padded(int64_t n, Fn &&f) {
-  switch (padded(n)) {
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    default: f(std::integral_constant<int, 32>{}); break;
-  }
-}
-template <class Fn>
-inline void dispatch_columns(int64_t n, Fn &&f) {
-  switch (group_size(n)) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;
-  }
-}
-
 }  // namespace pgram
 }  // namespace c2
 
@@ -217,7 +134,7 @@ extern "C" int c2_whitened_sinusoids(int64_t B, int64_t N, int64_t J, int64_t Q0
                                      const double *Z0, const double *freq, int64_t f_bs, double t_ref, double *T,
                                      c2_stream_t stream) {
   if (B < 1 || N < 1 || J < 1 || Q0 < 1 || F < 1) return C2_ERR_INVALID;
-  if (J > C2_FAST_WIDTH || Q0 > kMaxQ0) return C2_ERR_UNSUPPORTED;
+  if (J > C2_FAST_WIDTH || Q0 > trial::kMaxQ0) return C2_ERR_UNSUPPORTED;
   if (!t || !c || !U || !W || !d || !Z0 || !freq || !T) return C2_ERR_INVALID;
   if (t_bs < 0 || c_bs < 0 || f_bs < 0) return C2_ERR_INVALID;
   const int64_t fpw = freqs_per_wave(padded(J)), FB = (F + fpw - 1) / fpw;

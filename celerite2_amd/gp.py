@@ -325,6 +325,11 @@ class GaussianProcess:
             Y0 = torch.cat([A.expand(B, N, A.shape[-1]), r], dim=-1)
         return ops.solve_lower(self._t, self._c, self._U, self._W, Y0.contiguous())
 
+    def _nan_failed_fit(self, fit):
+        """`fit`, a named tuple of (B, ...) tensors, with NaN in the series whose factorisation failed."""
+        B = self._diag.shape[0]
+        return type(fit)(*[self._nan_failed(x.reshape(B, -1))[0].reshape(x.shape) for x in fit])
+
     # -- the periodogram under the factored covariance (ops.whitened_sinusoids; no counterpart in the reference) -------
     def periodogram(self, y, freq, *, A="mean", normalization="standard", t_ref=0.0, return_fit=False):
         """The generalized Lomb-Scargle periodogram of `y` (B, N) under the factored covariance, (B, F): for each ANGULAR trial
@@ -350,12 +355,8 @@ class GaussianProcess:
             raise ValueError("Invalid shape: freq (must be (F,) or (B, F) with B = %d, F >= 1)" % B)
         Z0 = self._whitened_columns(y, A)
         T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq.contiguous(), t_ref=t_ref)
-        fit = pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0)
-        F = T.shape[1]
-        power, amplitude, chi2_null = self._nan_failed(fit.power, fit.amplitude.reshape(B, 2 * F), fit.chi2_null[:, None])
-        if not return_fit:
-            return power
-        return pg.Periodogram(power, amplitude.reshape(B, F, 2), chi2_null[:, 0])
+        fit = self._nan_failed_fit(pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0))
+        return fit if return_fit else fit.power
 
     # -- the transit search under the factored covariance (ops.whitened_transits; no counterpart in the reference) -----
     def transit_search(self, y, trials, *, A="mean", return_fit=False):
@@ -372,7 +373,7 @@ class GaussianProcess:
         w > 0, 0 <= tau <= w / 2, P >= 0, w <= P (P > 0), a series whose factorisation failed or whose A is rank-deficient, and
         every trial when N < P0 + 2 hold NaN.  A TermConvolution kernel is accepted: only the factored matrix is used.
         J <= 32."""
-        from . import periodogram as pg, transit as tr
+        from . import _trial_fit, transit as tr
 
         self._need()
         self._check_vector(y)
@@ -383,11 +384,8 @@ class GaussianProcess:
         trials = trials.contiguous()
         Z0 = self._whitened_columns(y, A)
         T = ops.whitened_transits(self._t, self._c, self._U, self._W, self._d, Z0, trials)
-        fit = tr.finish(pg.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials)
-        *per_trial, chi2_null = self._nan_failed(*fit[:4], fit.chi2_null[:, None])
-        if not return_fit:
-            return per_trial[0]
-        return tr.TransitSearch(*per_trial, chi2_null[:, 0])
+        fit = self._nan_failed_fit(tr.finish(_trial_fit.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials))
+        return fit if return_fit else fit.delta_chi2
 
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):

@@ -22,17 +22,13 @@ import math
 
 import torch
 
+from ._trial_fit import null_fit, null_products
 from .autograd import _RANK_TOL
 
 __all__ = ["Periodogram", "NORMALIZATIONS", "null_products", "finish"]
 
 Periodogram = collections.namedtuple("Periodogram", "power amplitude chi2_null")
 NORMALIZATIONS = ("standard", "chi2", "log_likelihood")
-
-
-def null_products(Z0, d):
-    """S0 (B, Q0, Q0) = Z0^T diag(1/d) Z0 for Z0 (B, N, Q0), d (B, N)."""
-    return torch.matmul((Z0 / d[..., None]).transpose(1, 2), Z0)
 
 
 def finish(S0, T, N, normalization="standard", ok=None):
@@ -42,33 +38,14 @@ def finish(S0, T, N, normalization="standard", ok=None):
     `ok` (B,) | None: series to take at all (the others hold NaN; their S0, T are not read)."""
     if normalization not in NORMALIZATIONS:
         raise ValueError("normalization must be one of %s" % (NORMALIZATIONS,))
-    B, Q0 = S0.shape[0], S0.shape[-1]
-    if S0.dim() != 3 or S0.shape[1] != Q0 or Q0 < 1:
-        raise ValueError("Invalid shape: S0 (must be (B, Q0, Q0), Q0 >= 1)")
-    if T.dim() != 3 or T.shape[0] != B or T.shape[2] != 3 + 2 * Q0:
-        raise ValueError("Invalid shape: T (must be (B, F, 3 + 2 Q0) = (%d, F, %d))" % (B, 3 + 2 * Q0))
+    Q0 = S0.shape[-1]
+    S0, T, bad, chi2_0, v, X = null_fit(S0, T, ok, ("F", "3 + 2 Q0", 3 + 2 * Q0), (3, 3 + Q0))   # X (B, P0, 2 F)
     P0, F = Q0 - 1, T.shape[1]
     nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
-    if ok is not None:
-        S0 = torch.where(ok[:, None, None], S0, torch.eye(Q0, dtype=S0.dtype, device=S0.device))
-        T = torch.where(ok[:, None, None], T, torch.zeros((), dtype=T.dtype, device=T.device))
-    bad = torch.zeros(B, dtype=torch.bool, device=S0.device) if ok is None else ~ok
-    s_yy = S0[:, P0, P0]
     a, b, c = T[..., 0], T[..., 1], T[..., 2]                         # Gtt
     r1, r2 = T[..., 3 + P0], T[..., 3 + Q0 + P0]                      # gty
-    chi2_0 = s_yy
     if P0:
-        G00, g0y = S0[:, :P0, :P0], S0[:, :P0, P0]
-        L0, info = torch.linalg.cholesky_ex(G00)
-        bad = bad | (info != 0)
-        bad = bad | ~((torch.diagonal(L0, dim1=-2, dim2=-1) ** 2 > _RANK_TOL * torch.diagonal(G00, dim1=-2, dim2=-1)).all(dim=-1))
-        # (the solves below stay finite: a bad series is solved against the identity, then overwritten)
-        L0 = torch.where(bad[:, None, None], torch.eye(P0, dtype=S0.dtype, device=S0.device), L0)
-        v = torch.linalg.solve_triangular(L0, g0y[..., None], upper=False)[..., 0]                    # (B, P0)
-        Gt0 = torch.cat([T[..., 3:3 + P0], T[..., 3 + Q0:3 + Q0 + P0]], dim=1)                          # (B, 2 F, P0)
-        X = torch.linalg.solve_triangular(L0, Gt0.transpose(1, 2), upper=False)                        # (B, P0, 2 F)
-        Xc, Xs = X[..., :F], X[..., F:]
-        chi2_0 = s_yy - (v * v).sum(dim=-1)
+        Xc, Xs = X[..., :F], X[..., F:]                                                                # (B, P0, F) each
         a_, b_, c_ = a - (Xc * Xc).sum(dim=1), b - (Xc * Xs).sum(dim=1), c - (Xs * Xs).sum(dim=1)     # M
         r1, r2 = r1 - (Xc * v[:, :, None]).sum(dim=1), r2 - (Xs * v[:, :, None]).sum(dim=1)           # r
     else:

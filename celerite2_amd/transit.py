@@ -7,7 +7,7 @@ without the template.  Everything that costs O(N) per trial is in one kernel (op
 include/celerite2_amd_transit.h has the rule for b_k); what is left is algebra on (B, K, .) arrays, here, in plain torch.
 With K + D = L diag(d) L^T, Z0 = L^-1 [A0 | y - mean] (B, N, Q0 = P0 + 1), z = L^-1 b_k and <a, b> = sum_n a_n b_n / d_n:
 
-    S0 = Z0^T diag(1/d) Z0     ->  G00 = S0[:P0, :P0],  g0y = S0[:P0, P0],  s_yy = S0[P0, P0]   (periodogram.null_products)
+    S0 = Z0^T diag(1/d) Z0     ->  G00 = S0[:P0, :P0],  g0y = S0[:P0, P0],  s_yy = S0[P0, P0]   (_trial_fit.null_products)
     T[b, k] (whitened_transits) ->  <z, z> = T[0],  Gt0 (P0) = T[1:1+P0],  gty = T[1+P0]
     chi2_0 = s_yy - g0y^T G00^-1 g0y               (the fit without the template; one per series)
     M      = <z, z> - Gt0 G00^-1 G0t,   r = gty - Gt0 G00^-1 g0y
@@ -24,6 +24,7 @@ import math
 
 import torch
 
+from ._trial_fit import null_fit
 from .autograd import _RANK_TOL
 
 __all__ = ["TransitSearch", "finish", "trial_grid", "in_domain"]
@@ -42,33 +43,16 @@ def finish(S0, T, N, ok=None, trials=None):
     and the series length N (the module docstring has the formulas).  `ok` (B,) | None: series to take at all (the others
     hold NaN; their S0, T are not read).  `trials` (K, 4) | (B, K, 4) | None: the trials T was made from, to hold NaN where one
     is outside the domain."""
-    B, Q0 = S0.shape[0], S0.shape[-1]
-    if S0.dim() != 3 or S0.shape[1] != Q0 or Q0 < 1:
-        raise ValueError("Invalid shape: S0 (must be (B, Q0, Q0), Q0 >= 1)")
-    if T.dim() != 3 or T.shape[0] != B or T.shape[2] != 1 + Q0:
-        raise ValueError("Invalid shape: T (must be (B, K, 1 + Q0) = (%d, K, %d))" % (B, 1 + Q0))
-    P0, K = Q0 - 1, T.shape[1]
+    Q0 = S0.shape[-1]
+    S0, T, bad, chi2_0, v, X = null_fit(S0, T, ok, ("K", "1 + Q0", 1 + Q0), (1,))                 # X (B, P0, K)
+    B, P0, K = S0.shape[0], Q0 - 1, T.shape[1]
     if trials is not None and (trials.dim() not in (2, 3) or tuple(trials.shape[-2:]) != (K, 4)
                                or (trials.dim() == 3 and trials.shape[0] != B)):
         raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4) = (%d, %d, 4))" % (B, K))
     nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
-    if ok is not None:
-        S0 = torch.where(ok[:, None, None], S0, torch.eye(Q0, dtype=S0.dtype, device=S0.device))
-        T = torch.where(ok[:, None, None], T, torch.zeros((), dtype=T.dtype, device=T.device))
-    bad = torch.zeros(B, dtype=torch.bool, device=S0.device) if ok is None else ~ok
-    s_yy = S0[:, P0, P0]
-    zz, r = T[..., 0], T[..., 1 + P0]
-    chi2_0, M = s_yy, zz
+    M = zz = T[..., 0]
+    r = T[..., 1 + P0]
     if P0:
-        G00, g0y = S0[:, :P0, :P0], S0[:, :P0, P0]
-        L0, info = torch.linalg.cholesky_ex(G00)
-        bad = bad | (info != 0)
-        bad = bad | ~((torch.diagonal(L0, dim1=-2, dim2=-1) ** 2 > _RANK_TOL * torch.diagonal(G00, dim1=-2, dim2=-1)).all(dim=-1))
-        # (the solves below stay finite: a bad series is solved against the identity, then overwritten)
-        L0 = torch.where(bad[:, None, None], torch.eye(P0, dtype=S0.dtype, device=S0.device), L0)
-        v = torch.linalg.solve_triangular(L0, g0y[..., None], upper=False)[..., 0]                    # (B, P0)
-        X = torch.linalg.solve_triangular(L0, T[..., 1:1 + P0].transpose(1, 2), upper=False)           # (B, P0, K)
-        chi2_0 = s_yy - (v * v).sum(dim=-1)
         M = zz - (X * X).sum(dim=1)
         r = r - (X * v[:, :, None]).sum(dim=1)
     sing = ~(M > _RANK_TOL * zz)

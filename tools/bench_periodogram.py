@@ -20,112 +20,35 @@ device library's large-argument sine and cosine, which a wavefront skips when no
 timed part turns lane-rows per second into a share of 39.3e12 fp64 instructions per lane and second -- the public
 78.6 TFLOP/s vector fp64 figure of the part counted as fused multiply-adds, half the 157.3 TFLOP/s fp32 vector peak."""
 import argparse
-import collections
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from trial_static import MIX_HEAD, fp64_valu, kept_block, kernel_asm, mix_cells, register_table, row_loop_mix, with_block  # noqa: E402
+
 FP64_PEAK = 78.6e12 / 2.0   # fp64 VALU instructions per lane and second
 SHAPES = [(64, 4096, 8, 4096), (1, 4096, 8, 4096), (1024, 1024, 4, 1024), (64, 4096, 32, 512)]
-BLOCKS = {"registers": "tools/bench_periodogram.py --static-only", "instructions": "tools/bench_periodogram.py --static-only"}
-
-
-def marks(key):
-    return "<!-- %s:begin (%s) -->" % (key, BLOCKS[key]), "<!-- %s:end -->" % key
-
-
-def register_table():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from kernel_regs import kernel_rows
-
-    rows = kernel_rows("c2_periodogram.o")
-    if not rows:
-        return None
-    lines = ["| kernel | registers (of them accumulation) | SGPRs | LDS bytes | scratch bytes | spilled registers |", "|---|---|---|---|---|---|"]
-    for _, name, vg, ag, scratch, lds, spill, sg in sorted(rows, key=lambda r: [int(v) for v in re.findall(r"\d+", re.sub(r"\(.*", "", r[1]))[-2:]]):
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("c2::pgram::", "")
-        lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (name, vg, ag, sg, lds, scratch, spill))
-    lines += ["", "Largest scratch %d bytes, %d spilled registers over %d kernels (`k_sinusoids<JR, QR>`: J rounded up to 4, 8, 16 "
-              "or 32, Q0 to 1, 2, 4 or 8).  About 80 of each instance's registers hold the double-precision constants of the sine "
-              "and cosine, which the compiler keeps in vector registers across the row loop."
-              % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows))]
-    return "\n".join(lines)
-
-
-def row_loop_mix(asm, jr, qr):
-    """Counter of the instructions one row of one lane issues in k_sinusoids<jr, qr>: the innermost loop of the kernel in the
-    compiler's assembly, without the forward-skipped regions that hold the device library's large-argument reduction
-    (v_trig_preop_f64)."""
-    name = "_ZN2c25pgram11k_sinusoidsILi%dELi%dEE" % (jr, qr)
-    i = asm.index("\n" + name) + 1
-    lines = asm[i:asm.index(".Lfunc_end", i)].split("\n")
-    labels = {m.group(1): k for k, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l.strip())] if m}
-    loops = []
-    for k, l in enumerate(lines):
-        m = re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
-        if m and labels.get(m.group(1), k) < k:
-            loops.append((labels[m.group(1)], k))
-    a = max(lp[0] for lp in loops if any("ds_read" in l for l in lines[lp[0]:lp[1]]))   # the innermost header ...
-    b = max(lp[1] for lp in loops if lp[0] == a)                                        # ... and its last back edge
-    skip = set()
-    for k in range(a, b + 1):
-        m = re.search(r"s_cbranch_execz\s+(\.LBB\d+_\d+)", lines[k])
-        if m and k < labels[m.group(1)] <= b and any("v_trig_preop_f64" in l for l in lines[k:labels[m.group(1)]]):
-            skip.update(range(k + 1, labels[m.group(1)]))
-    ins = [lines[k].split()[0] for k in range(a, b + 1) if k not in skip and lines[k].strip()
-           and not lines[k].strip().startswith((";", ".")) and not lines[k].strip().endswith(":")]
-    return collections.Counter(ins)
+TOOL = "tools/bench_periodogram.py --static-only"
+REGISTER_NOTE = ("  About 80 of each instance's registers hold the double-precision constants of the sine "
+                 "and cosine, which the compiler keeps in vector registers across the row loop.")
 
 
 def instruction_table():
-    """The row loop's instruction mix per width, from a device-only compile of the kernel with the build's own flags."""
-    from celerite2_amd import build
-
-    if not os.path.exists(build.HIPCC):
+    """The row loop's instruction mix per width, without the forward-skipped regions that hold the device library's
+    large-argument reduction (v_trig_preop_f64)."""
+    asm = kernel_asm("c2_periodogram.hip")
+    if asm is None:
         return None
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "c2_periodogram.s")
-        flags = [f for f in build.HIPFLAGS if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "c2_periodogram.hip"), "-o", out],
-                       check=True)
-        asm = open(out).read()
-    lines = ["| kernel | instructions a row | fp64 VALU | of them fma / mul / add / other | other VALU | LDS reads (b128 / b64 / other) | scalar |",
-             "|---|---|---|---|---|---|---|"]
+    mix = lambda jr, qr: row_loop_mix(asm, "_ZN2c25pgram11k_sinusoidsILi%dELi%dEE" % (jr, qr), "v_trig_preop_f64")[0]
+    lines = [MIX_HEAD, "|---|---|---|---|---|---|---|"]
     for jr, qr in ((4, 2), (8, 2), (16, 2), (32, 2), (8, 1), (8, 8)):
-        c = row_loop_mix(asm, jr, qr)
-        f64 = {k: v for k, v in c.items() if k.startswith("v_") and "_f64" in k}
-        fma = sum(v for k, v in f64.items() if "fma" in k)
-        mul, add = sum(v for k, v in f64.items() if k.startswith("v_mul")), sum(v for k, v in f64.items() if k.startswith("v_add"))
-        valu = sum(v for k, v in c.items() if k.startswith("v_"))
-        lds = sum(v for k, v in c.items() if k.startswith("ds_"))
-        lines.append("| `k_sinusoids<%d, %d>` | %d | %d | %d / %d / %d / %d | %d | %d / %d / %d | %d |"
-                     % (jr, qr, sum(c.values()), sum(f64.values()), fma, mul, add, sum(f64.values()) - fma - mul - add,
-                        valu - sum(f64.values()), c.get("ds_read_b128", 0), c.get("ds_read_b64", 0),
-                        lds - c.get("ds_read_b128", 0) - c.get("ds_read_b64", 0), sum(v for k, v in c.items() if k.startswith("s_"))))
+        lines.append("| `k_sinusoids<%d, %d>` | %s" % (jr, qr, mix_cells(mix(jr, qr))))
     lines += ["", "One row of one lane (one frequency; at JR = 32 one of a frequency's two columns), the path a wavefront takes when "
               "every phase is below kSincosFastMax.  fp64 VALU per lane-row, machine-readable: "
-              + " ".join("JR%d=%d" % (jr, sum(v for k, v in row_loop_mix(asm, jr, 2).items() if k.startswith("v_") and "_f64" in k))
-                         for jr in (4, 8, 16, 32))]
+              + " ".join("JR%d=%d" % (jr, fp64_valu(mix(jr, 2))) for jr in (4, 8, 16, 32))]
     return "\n".join(lines)
-
-
-def with_block(text, key, table, title):
-    begin, end = marks(key)
-    table = table or "(neither the built objects nor the compiler are on this machine: run `python tools/bench_periodogram.py --static-only --out <this file>` where the library was built)"
-    block = begin + "\n" + table + "\n" + end
-    if begin in text and end in text:
-        head, rest = text.split(begin, 1)
-        return head + block + rest.split(end, 1)[1]
-    return text + "\n## %s\n\n" % title + block + "\n"
-
-
-def kept_block(text, key):
-    begin, end = marks(key)
-    return text.split(begin, 1)[1].split(end, 1)[0].strip("\n") if begin in text and end in text else None
 
 
 def main():
@@ -139,8 +62,8 @@ def main():
     a = ap.parse_args()
     old = open(a.out).read() if a.out and os.path.exists(a.out) else ""
     if a.static_only:
-        text = with_block(old, "registers", register_table(), "Registers (gfx950, from the built objects)")
-        text = with_block(text, "instructions", instruction_table(), "The row loop (gfx950, from the compiler's assembly)")
+        text = with_block(old, "registers", register_table("c2_periodogram.o", "c2::pgram::", "k_sinusoids", REGISTER_NOTE), TOOL)
+        text = with_block(text, "instructions", instruction_table(), TOOL)
         if a.out:
             open(a.out, "w").write(text)
         print(text)
@@ -151,7 +74,7 @@ def main():
 
     assert torch.cuda.is_available(), "this measures the GPU: there is nothing to fall back to"
     dev = torch.device("cuda:0")
-    per_row = dict((int(k), int(v)) for k, v in re.findall(r"JR(\d+)=(\d+)", kept_block(old, "instructions") or ""))
+    per_row = dict((int(k), int(v)) for k, v in re.findall(r"JR(\d+)=(\d+)", kept_block(old, "instructions", TOOL) or ""))
 
     def stats(ms):
         ms = sorted(ms)
@@ -247,9 +170,8 @@ def main():
         torch.cuda.empty_cache()
     lines += ["", "Worst |fused - composed| power in units of the standing criterion: " + "; ".join(agree) + "."]
     text = "\n".join(lines) + "\n"
-    for key, title in (("registers", "Registers (gfx950, from the built objects)"),
-                       ("instructions", "The row loop (gfx950, from the compiler's assembly)")):
-        text = with_block(text, key, kept_block(old, key), title)
+    for key in ("registers", "instructions"):
+        text = with_block(text, key, kept_block(old, key, TOOL), TOOL)
     # whatever follows the generated part of an earlier file (hand-written notes) is kept
     if "<!-- notes -->" in old:
         text += "\n<!-- notes -->" + old.split("<!-- notes -->", 1)[1]
