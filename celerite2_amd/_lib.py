@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h and
-celerite2_amd_transit.h).
+"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
+celerite2_amd_transit.h and celerite2_amd_kepler.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -16,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # 
 LINEAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_linear.h")   # linear mean models
 PERIODOGRAM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_periodogram.h")   # the periodogram
 TRANSIT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_transit.h")   # the transit search
+KEPLER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_kepler.h")   # the Keplerian search
 
 
 class BackendError(RuntimeError):
@@ -103,6 +104,9 @@ PERIODOGRAM_SYMBOLS = ["c2_whitened_sinusoids"]
 # Every symbol include/celerite2_amd_transit.h declares (checked by tests/test_transit.py).
 TRANSIT_SYMBOLS = ["c2_whitened_transits"]
 
+# Every symbol include/celerite2_amd_kepler.h declares (checked by tests/test_kepler.py).
+KEPLER_SYMBOLS = ["c2_whitened_keplerians"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -169,6 +173,7 @@ def load():
     protos.update(_prototypes(_header(LINEAR_HEADER)))
     protos.update(_prototypes(_header(PERIODOGRAM_HEADER)))
     protos.update(_prototypes(_header(TRANSIT_HEADER)))
+    protos.update(_prototypes(_header(KEPLER_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

@@ -60,6 +60,7 @@ int c2_internal_factor_states_timepar(int64_t B, int64_t N, int64_t J, const dou
 // segments of C rows apart, words[2 w + 1] the same over single segments; +inf for unsorted / NaN times
 int c2_internal_anchor_spans(int64_t B, int64_t N, int64_t J, int C, int spw, const double *t, int64_t t_bs, const double *c,
                              int64_t c_bs, unsigned long long *words, c2_stream_t stream);
+size_t c2_internal_loglik_grad_rows_workspace_bytes(int64_t B, int64_t N, int64_t J);   // its `work` (not c2_loglik_grad's)
 int c2_internal_loglik_grad_rows(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                  int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
                                  double *ll, double *bt, double *bc, double *ba, double *bU, double *bV, double *by,

@@ -400,7 +400,7 @@ inline Plan plan(int64_t B, int64_t N, int64_t M, int64_t J, int method, int gra
       p.bU2 = take((size_t)B * R * J);
       p.bV2 = take((size_t)B * R * J);
       p.part = take((size_t)B * p.nch * M);
-      p.one_d = take(c2_loglik_grad_workspace_bytes(B, (int64_t)R, J) / sizeof(double));
+      p.one_d = take(c2_internal_loglik_grad_rows_workspace_bytes(B, (int64_t)R, J) / sizeof(double));
     }
   }
   p.total = o;
@@ -476,7 +476,7 @@ int c2_kron_loglik_grad(int64_t B, int64_t N, int64_t M, int64_t J, const double
     // by of the interleaved series IS by (B, N, M); bc is shared by both views
     if (int e = c2_internal_loglik_grad_rows(B, R, J, w + p.t2, t_bs ? R : 0, c, c_bs, w + p.a2, w + p.U2, w + p.V2, y, ll,
                                w + p.bt2, bc, w + p.ba2, w + p.bU2, w + p.bV2, by, flag, w + p.one_d,
-                               c2_loglik_grad_workspace_bytes(B, R, J), stream))
+                               c2_internal_loglik_grad_rows_workspace_bytes(B, R, J), stream))
       return e;
     hipLaunchKernelGGL(k_kron_expand_rev, dim3((unsigned)p.nch, (unsigned)B), dim3(kThreads), 0, s, B, N, (int)M,
                        (int)J, a, U, V, alpha, alpha_bs, w + p.bt2, w + p.ba2, w + p.bU2, w + p.bV2, bt, ba, bU, bV,

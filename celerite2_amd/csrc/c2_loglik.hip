@@ -1703,9 +1703,8 @@ int c2_internal_anchor_spans(int64_t B, int64_t N, int64_t J, int C, int spw, co
   return launch_ok();
 }
 
-size_t c2_loglik_grad_workspace_bytes(int64_t B, int64_t N, int64_t J) {
-  if (B < 1 || N < 1 || J < 1 || J > C2_MAX_WIDTH) return 0;
-  if (J > C2_FAST_WIDTH) return c2_loglik_grad_composite_workspace_bytes(B, N, J);   // (d, W, S, z, F, seeds: the op chain)
+// what the row-by-row forms of loglik_grad_impl take (doubles; J <= C2_FAST_WIDTH)
+static size_t grad_rows_doubles(int64_t B, int64_t N, int64_t J) {
   size_t n = grad_ws(B, N, J, use_back(N, J)).total;
   if (use_lanes4(B, J, true)) {   // [guard words] [records of the four-lane pair | workspace of the replay fallback]
     const size_t r = c2_internal_loglik_q4_record_doubles(B, N), f = grad_ws(B, N, J).total;
@@ -1720,6 +1719,12 @@ size_t c2_loglik_grad_workspace_bytes(int64_t B, int64_t N, int64_t J) {
     const size_t f = grad_ws(B, N, J).total, r = c2_internal_loglik_k2_record_doubles(B, N);
     n = lanes1_gate_words(B) + (r > f ? r : f);
   }
+  return n;
+}
+size_t c2_loglik_grad_workspace_bytes(int64_t B, int64_t N, int64_t J) {
+  if (B < 1 || N < 1 || J < 1 || J > C2_MAX_WIDTH) return 0;
+  if (J > C2_FAST_WIDTH) return c2_loglik_grad_composite_workspace_bytes(B, N, J);   // (d, W, S, z, F, seeds: the op chain)
+  size_t n = grad_rows_doubles(B, N, J);
   if (use_timepar_grad(B, N, J)) {   // [verification words | its scratch, or the workspace of the gated row-by-row pair]
     const size_t r = c2_internal_timepar_grad_doubles(B, N, J), f = grad_ws(B, N, J).total + kTimeparVerifyWords;
     n = r > f ? r : f;
@@ -1743,7 +1748,16 @@ int c2_loglik_grad(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_b
                           stream);
 }
 // the same, never parallel along time (the interleaved 2-D construction: runs of identical times, conditioning 1e3-1e4 --
-// the row-by-row kernels hold every element to 1e-12 of the largest there, the chunk maps to 3e-12)
+// the row-by-row kernels hold every element to 1e-12 of the largest there, the chunk maps to 3e-12).  Its workspace is its
+// own: where c2_loglik_grad would run parallel along time, c2_loglik_grad_workspace_bytes is the room of THAT form, which
+// can be less than the row-by-row forms write (2 x 12000 x 4: 651268 doubles against 1248290 with the W records of the
+// backward recursion).
+size_t c2_internal_loglik_grad_rows_workspace_bytes(int64_t B, int64_t N, int64_t J) {
+  const size_t n = c2_loglik_grad_workspace_bytes(B, N, J);
+  if (n == 0 || J > C2_FAST_WIDTH) return n;
+  const size_t rows = grad_rows_doubles(B, N, J) * sizeof(double);
+  return rows > n ? rows : n;
+}
 int c2_internal_loglik_grad_rows(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                  int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
                                  double *ll, double *bt, double *bc, double *ba, double *bU, double *bV, double *by,
@@ -1759,7 +1773,8 @@ static int loglik_grad_impl(int64_t B, int64_t N, int64_t J, const double *t, in
   if (J > C2_MAX_WIDTH) return C2_ERR_UNSUPPORTED;
   if (!t || !c || !a || !U || !V || !y || !ll || !bt || !bc || !ba || !bU || !bV || !by || !flag || !work)
     return C2_ERR_INVALID;
-  if (work_bytes < c2_loglik_grad_workspace_bytes(B, N, J)) return C2_ERR_INVALID;
+  if (work_bytes < (allow_timepar ? c2_loglik_grad_workspace_bytes(B, N, J) : c2_internal_loglik_grad_rows_workspace_bytes(B, N, J)))
+    return C2_ERR_INVALID;
   if (J > C2_FAST_WIDTH) {
     if (int e = c2_loglik_grad_composite(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work,
                                          work_bytes, stream))

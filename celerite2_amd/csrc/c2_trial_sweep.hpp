@@ -1,5 +1,5 @@
 // c2_trial_sweep.hpp -- the ROW STAGING of the forward sweeps that carry one trial per lane (k_sinusoids, c2_periodogram.hip;
-// k_transits, c2_transit.hip), once.  Such a kernel runs internal::forward (internal.hpp:107-146) on right-hand sides that
+// k_transits, c2_transit.hip; k_keplerians, c2_kepler.hip), once.  Such a kernel runs internal::forward (internal.hpp:107-146) on right-hand sides that
 // its lanes form in registers; everything else about a row -- t_n, 1 / d_n, the Z0 row, u_n, w_{n-1}, p_n -- is the same for
 // all 64 lanes: the wavefront stages R rows at a time in LDS, lane (r, j) loading u, w and forming ONE decay factor, and
 // every lane reads the block back by broadcast.  The next block's global loads are issued before a block's rows are swept

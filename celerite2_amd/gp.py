@@ -387,6 +387,72 @@ class GaussianProcess:
         fit = self._nan_failed_fit(tr.finish(_trial_fit.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials))
         return fit if return_fit else fit.delta_chi2
 
+    # -- the Keplerian search under the factored covariance (ops.whitened_keplerians; no counterpart in the reference) ---
+    def keplerian_search(self, y, trials, *, A="mean", normalization="standard", return_fit=False):
+        """The Keplerian periodogram of `y` (B, N) under the factored covariance, (B, K): for each trial (angular frequency
+        w = 2 pi / P, eccentricity e, time of periastron tp) of `trials` ((K, 3) shared | (B, K, 3); kepler.trial_grid makes
+        a regular grid) the model y = mean + A beta0 + K [cos(nu(t) + omega) + e cos omega] + GP, nu the true anomaly of
+        the orbit, is fitted by generalized least squares in (alpha, beta) = (K cos omega, -K sin omega) and compared with
+        the fit without the orbit (chi2_null - chi2 = dchi2).  `A`: the nuisance columns, as for `periodogram`; the
+        orbit's constant K e cos omega needs a constant column among them ("mean" has it).  `normalization`: as for
+        `periodogram`.  `return_fit=True`: kepler.KeplerianSearch(power (B, K), amplitude (B, K, 2) = (alpha, beta),
+        semi_amplitude (B, K), omega (B, K), chi2_null (B,)).
+        One solve_lower with P0 + 1 columns, one sweep with a lane per trial that solves Kepler's equation in registers
+        (ops.whitened_keplerians; include/celerite2_amd_kepler.h has the rule), then torch on (B, K, .) arrays
+        (celerite2_amd/kepler.py).  Not differentiable and never raising under compute(..., quiet=True): a trial outside
+        w > 0, 0 <= e <= 0.99, tp finite, one at which the two columns are not identifiable beside A, a series whose
+        factorisation failed or whose A is rank-deficient, and every trial when N < P0 + 3 hold NaN.  Times with a large
+        offset keep their accuracy with tp at the offset.  J <= 32."""
+        from . import _trial_fit, kepler as kp, periodogram as pg
+
+        self._need()
+        self._check_vector(y)
+        B, N = self._diag.shape
+        if normalization not in pg.NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
+        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
+                or trials.shape[-1] != 3 or trials.shape[-2] < 1:
+            raise ValueError("Invalid shape: trials (must be (K, 3) or (B, K, 3) with B = %d, K >= 1)" % B)
+        trials = trials.contiguous()
+        Z0 = self._whitened_columns(y, A)
+        T = ops.whitened_keplerians(self._t, self._c, self._U, self._W, self._d, Z0, trials)
+        fit = self._nan_failed_fit(kp.finish(_trial_fit.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0,
+                                             trials=trials))
+        return fit if return_fit else fit.power
+
+    def keplerian_periodogram(self, y, freq, ecc, n_phase, *, A="mean", normalization="standard", t0=0.0, max_trials=None):
+        """`keplerian_search` on the regular grid kepler.trial_grid(freq, ecc, n_phase, t0=t0) -- ANGULAR frequencies `freq`
+        (F,), eccentricities `ecc` (E), n_phase times of periastron over a period -- profiled over eccentricity and
+        periastron: (power (B, F), best_trial (B, F, 3), amplitude (B, F, 2)), the maximum over the E n_phase trials of each
+        frequency (NaN trials ignored; NaN where all are), the maximising (w, e, tp) and its (alpha, beta).
+        `max_trials`: run the search in blocks of whole frequencies of at most that many trials, so that the (B, K, 3 + 2 Q0)
+        products stay bounded (ValueError when one frequency's E n_phase trials exceed it); the result does not depend on
+        it, to the bit."""
+        from . import kepler as kp
+
+        self._need()
+        grid = kp.trial_grid(freq, ecc, n_phase, t0=t0).to(self._diag.device)
+        F = int(torch.as_tensor(freq).numel())
+        if F < 1 or grid.shape[0] < F:
+            raise ValueError("Invalid shape: freq, ecc (at least one frequency and one eccentricity)")
+        per = grid.shape[0] // F
+        if max_trials is None:
+            step = F
+        else:
+            step = int(max_trials) // per
+            if step < 1:
+                raise ValueError("max_trials = %d is below the %d trials of one frequency (E n_phase)" % (int(max_trials), per))
+        power, index, amplitude = [], [], []
+        for f0 in range(0, F, step):
+            f1 = min(F, f0 + step)
+            fit = self.keplerian_search(y, grid[f0 * per:f1 * per], A=A, normalization=normalization, return_fit=True)
+            p, idx = kp.profile(fit, f1 - f0)
+            power.append(p)
+            amplitude.append(torch.gather(fit.amplitude, 1, idx[..., None].expand(-1, -1, 2)))
+            index.append(idx + f0 * per)
+        index = torch.cat(index, dim=1)
+        return torch.cat(power, dim=1), grid[index], torch.cat(amplitude, dim=1)
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

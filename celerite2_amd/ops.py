@@ -25,10 +25,10 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
-# (`whitened_gram`, `whitened_sinusoids` and `whitened_transits`, the ops of include/celerite2_amd_linear.h,
-# celerite2_amd_periodogram.h and celerite2_amd_transit.h, are public as well; they are listed with their headers' symbols,
-# _lib.LINEAR_SYMBOLS, _lib.PERIODOGRAM_SYMBOLS and _lib.TRANSIT_SYMBOLS, and this list stays the ops of
-# include/celerite2_amd.h)
+# (`whitened_gram`, `whitened_sinusoids`, `whitened_transits` and `whitened_keplerians`, the ops of
+# include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h and celerite2_amd_kepler.h, are public
+# as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS, _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS
+# and _lib.KEPLER_SYMBOLS, and this list stays the ops of include/celerite2_amd.h)
 
 
 def _p(x):
@@ -487,6 +487,37 @@ def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
     rc = _lib.load().c2_whitened_transits(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
                                           0 if trials.dim() == 2 else 4 * K, out, _stream())
     _lib.check(rc, "whitened_transits")
+    return out
+
+
+def whitened_keplerians(t, c, U, W, d, Z0, trials, *, out=None):
+    """T (B, K, 3 + 2 Q0): for every series and every trial (angular frequency w, eccentricity e, time of periastron tp) of
+    `trials` ((K, 3) shared by the batch or (B, K, 3)), with nu(t) the true anomaly of that orbit, z_c = L^-1 cos nu,
+    z_s = L^-1 sin nu and <a, b> = sum_n a_n b_n / d_n,
+
+        T[b, k] = [<z_c, z_c>, <z_c, z_s>, <z_s, z_s>, <z_c, Z0[:, j]> for j < Q0, <z_s, Z0[:, j]> for j < Q0]
+
+    (the layout of `whitened_sinusoids`) from the factors (d, W) of `factor` and Z0 (B, N, Q0) = solve_lower of
+    [A0 | y - mean], in one forward sweep that solves Kepler's equation and forms the two columns in registers, one lane per
+    trial (c2_whitened_keplerians, csrc/c2_kepler.hip; the header has the rule for the columns and the solver).  What the
+    Keplerian search under correlated noise reads (celerite2_amd/kepler.py).  Every trial is evaluated as written; the
+    domain w > 0, 0 <= e <= 0.99 is the caller's to mask.  Caller-owned `out` is accepted (nothing is allocated then:
+    capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two calls give identical
+    bits."""
+    B, N, J = _dims(U)
+    if Z0.dim() != 3:
+        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
+    if trials.dim() not in (2, 3) or trials.shape[-1] != 3:
+        raise ValueError("Invalid shape: trials (must be (K, 3) or (B, K, 3))")
+    Q0, K = Z0.shape[-1], trials.shape[-2]
+    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=3, R=3 + 2 * Q0)
+    if out is None:
+        out, = _empty(U.device, dims, "BKR")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
+                 ("trials", trials, "KF|BKF")], [("out", out, "BKR")])
+    rc = _lib.load().c2_whitened_keplerians(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
+                                            0 if trials.dim() == 2 else 3 * K, out, _stream())
+    _lib.check(rc, "whitened_keplerians")
     return out
 
 

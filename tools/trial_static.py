@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""The static tables of the one-lane-per-trial sweeps (csrc/c2_periodogram.hip, csrc/c2_transit.hip), shared by
-tools/bench_periodogram.py and tools/bench_transit.py: the register table from the built objects, the row loop's instruction
+"""The static tables of the one-lane-per-trial sweeps (csrc/c2_periodogram.hip, csrc/c2_transit.hip, csrc/c2_kepler.hip), shared
+by tools/bench_periodogram.py, tools/bench_transit.py and tools/bench_kepler.py: the register table from the built objects, the row loop's instruction
 mix from the compiler's assembly, and the marked blocks of a profile that hold them.  No GPU."""
 import collections
 import os
