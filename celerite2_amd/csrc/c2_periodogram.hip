@@ -32,18 +32,11 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd_periodogram.h"
 #include "c2_launch.hpp"
+#include "c2_trial_columns.hpp"
 #include "c2_trial_sweep.hpp"
 
 namespace c2 {
 namespace pgram {
-
-// x = fl(w * fl(t - t_ref)): the two roundings of the header, kept apart from whatever uses x
-__device__ __forceinline__ double phase(double w, double t, double t_ref) {
-#pragma clang fp contract(off)
-  const double dt = t - t_ref;
-  const double x = w * dt;
-  return x;
-}
 
 constexpr int freqs_per_wave(int JR) { return JR >= 32 ? kWave / 2 : kWave; }
 

@@ -27,25 +27,11 @@
 #include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd_transit.h"
 #include "c2_launch.hpp"
+#include "c2_trial_columns.hpp"
 #include "c2_trial_sweep.hpp"
 
 namespace c2 {
 namespace transit {
-
-// b_n of the header's rule from the lane's constants: invP = fl(1 / P), or 0 for a single event (then q = 0 and phi = x);
-// hw = 0.5 w (exact).  The ramp's division is met only by a wavefront with a lane on an ingress or egress at that row.
-__device__ __forceinline__ double template_value(double t, double P, double invP, double t0, double hw, double tau) {
-#pragma clang fp contract(off)
-  const double x = t - t0;
-  const double q = __builtin_rint(x * invP);
-  const double qp = q * P;
-  const double phi = x - qp;
-  const double u = hw - __builtin_fabs(phi);
-  double b = u >= tau ? 1.0 : 0.0;
-  const bool ramp = u >= 0.0 && u < tau;
-  if (__builtin_amdgcn_ballot_w64(ramp) != 0) b = ramp ? u / tau : b;   // (wave-uniform: the division is skipped, not masked)
-  return b;
-}
 
 template <int JR, int QR>
 __global__ __launch_bounds__(kWave) void k_transits(int64_t N, int J, int Q0, int64_t K, int64_t KB,

@@ -453,6 +453,102 @@ class GaussianProcess:
         index = torch.cat(index, dim=1)
         return torch.cat(power, dim=1), grid[index], torch.cat(amplitude, dim=1)
 
+    # -- false-alarm probabilities of the three searches (ops.trial_projections; no counterpart in the reference) -------
+    def search_significance(self, kind, y, trials, *, draws=1000, A="mean", normalization="standard", t_ref=0.0,
+                            dips_only=False, generator=None, normals=None, max_trials=None, max_draws=None):
+        """The search `kind` ("periodogram", "transit" or "keplerian") on `y` (B, N) with the Monte-Carlo false-alarm
+        probability of every trial: significance.Significance(statistic (B, K), fap (B, K), null_maxima (B, draws)).
+        `trials`: what the search takes -- ANGULAR frequencies (F,) | (B, F) for the periodogram, (K, 4) | (B, K, 4) for the
+        transit, (K, 3) | (B, K, 3) for the keplerian.  `statistic` is that search's result: the power of `periodogram` /
+        `keplerian_search` in `normalization`; for the transit delta_chi2 / chi2_null ("standard"), delta_chi2 ("chi2") or
+        half of it ("log_likelihood"), and with `dips_only` 0 where the fitted depth is positive.  `null_maxima[b, r]` is
+        the largest statistic over the trials (NaN ones ignored) of the same search on the r-th draw
+        y_r = mean + L D^1/2 n_r from the factored covariance, and
+        fap = (1 + #{r : null_maxima[b, r] >= statistic}) / (draws + 1): the probability that noise alone puts the
+        HIGHEST peak of the grid at or above this trial's statistic (a maximum within 1e-10 of the statistic, relative,
+        counts as at it).
+
+        THE PROBABILITY IS CONDITIONAL ON THE HYPER-PARAMETERS: the draws come from the covariance `compute` factored and
+        the kernel is not refitted per draw, as it would be on real data; where the hyper-parameters were fitted to `y`
+        itself, a signal absorbed by the kernel is not counted.
+
+        One sweep on `y` (the search's own) gives the statistic and every product that does not depend on the data; a
+        draw adds one column to one solve_upper and to ops.trial_projections, which forms each trial's column(s) once for
+        all draws (celerite2_amd/significance.py has the identities) -- no sweep per draw.  `normals` (B, N, draws): the
+        standard normals n_r, for reproducibility; otherwise torch.randn(..., generator=generator).  `max_trials`,
+        `max_draws`: take the trials / draws in blocks of at most that many, which bounds the (B, K, C, draws) and
+        (B, K, draws) arrays; the result does not depend on `max_trials`, to the bit, and on `max_draws` to rounding (the
+        solve may take another kernel at another column count).  `A`, `t_ref`: as for the searches.  Not differentiable
+        and never raising under compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32."""
+        from . import _trial_fit, kepler as kp, periodogram as pg, significance as sg, transit as tr
+
+        self._need()
+        self._check_vector(y)
+        (B, N), dev = self._diag.shape, self._diag.device
+        if kind not in sg.KINDS:
+            raise ValueError("kind must be one of %s" % (sg.KINDS,))
+        if normalization not in pg.NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
+        words = {"periodogram": None, "transit": 4, "keplerian": 3}[kind]
+        lead = 1 if words is None else 2
+        if not torch.is_tensor(trials) or trials.dim() not in (lead, lead + 1) or (trials.dim() == lead + 1 and trials.shape[0] != B) \
+                or (words is not None and trials.shape[-1] != words) or trials.shape[-1 if words is None else -2] < 1:
+            raise ValueError("Invalid shape: trials (must be %s with B = %d, K >= 1)"
+                             % ("(F,) or (B, F)" if words is None else "(K, %d) or (B, K, %d)" % (words, words), B))
+        if normals is not None:
+            if not torch.is_tensor(normals) or normals.dim() != 3 or tuple(normals.shape[:2]) != (B, N):
+                raise ValueError("Invalid shape: normals (must be (B, N, draws) = (%d, %d, draws))" % (B, N))
+            draws = normals.shape[-1]
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError("draws must be at least 1")
+        trials = trials.contiguous()
+        K = trials.shape[-1] if words is None else trials.shape[-2]
+        kstep = K if max_trials is None else int(max_trials)
+        rstep = draws if max_draws is None else int(max_draws)
+        if kstep < 1 or rstep < 1:
+            raise ValueError("max_trials and max_draws must be at least 1")
+        ok = self._flag == 0
+        Z0 = self._whitened_columns(y, A)
+        S0 = _trial_fit.null_products(Z0, self._d)
+        sweep_args = (self._t, self._c, self._U, self._W, self._d, Z0, trials)
+        if kind == "periodogram":
+            T = ops.whitened_sinusoids(*sweep_args, t_ref=t_ref)
+            statistic = pg.finish(S0, T, N, normalization, ok=ok).power
+        elif kind == "keplerian":
+            T = ops.whitened_keplerians(*sweep_args)
+            statistic = kp.finish(S0, T, N, normalization, ok=ok, trials=trials).power
+        else:
+            T = ops.whitened_transits(*sweep_args)
+            fit = tr.finish(S0, T, N, ok=ok, trials=trials)
+            statistic = sg._normalize(fit.delta_chi2, fit.chi2_null[:, None], normalization)
+            if dips_only:
+                statistic = torch.where(fit.depth > 0, torch.zeros_like(statistic), statistic)
+        statistic, = self._nan_failed(statistic)
+        if normals is None:
+            normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
+        rsd = torch.rsqrt(self._d)[..., None]
+        ZA = Z0[..., :-1].transpose(1, 2)                                        # (B, P0, N)
+        per_series = trials.dim() == lead + 1
+        maxima = []
+        for r0 in range(0, draws, rstep):
+            n = normals[..., r0:r0 + rstep]
+            scaled = (n * rsd).contiguous()                                      # D^-1/2 n_r
+            s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
+            alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
+            best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
+            for k0 in range(0, K, kstep):
+                tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
+                P = ops.trial_projections(kind, self._t, alpha, tk, t_ref=t_ref)
+                stat = sg.null_statistics(kind, S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization=normalization,
+                                          trials=tk, dips_only=dips_only, ok=ok)
+                best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
+            maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
+        null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
+        # (a draw's maximum comes through the projection, the statistic through the sweep: a tie of the two to the standing
+        # criterion's relative part counts as at or above -- the larger probability)
+        return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

@@ -25,10 +25,11 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
-# (`whitened_gram`, `whitened_sinusoids`, `whitened_transits` and `whitened_keplerians`, the ops of
-# include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h and celerite2_amd_kepler.h, are public
-# as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS, _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS
-# and _lib.KEPLER_SYMBOLS, and this list stays the ops of include/celerite2_amd.h)
+# (`whitened_gram`, `whitened_sinusoids`, `whitened_transits`, `whitened_keplerians` and `trial_projections`, the ops of
+# include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h, celerite2_amd_kepler.h and
+# celerite2_amd_trials.h, are public as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
+# _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
+# include/celerite2_amd.h)
 
 
 def _p(x):
@@ -518,6 +519,44 @@ def whitened_keplerians(t, c, U, W, d, Z0, trials, *, out=None):
     rc = _lib.load().c2_whitened_keplerians(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
                                             0 if trials.dim() == 2 else 3 * K, out, _stream())
     _lib.check(rc, "whitened_keplerians")
+    return out
+
+
+# kind -> (C2_TRIAL_*, doubles per trial, columns per trial C, vectors per wavefront C2_TRIAL_*_DRAWS) of celerite2_amd_trials.h
+TRIAL_KINDS = {"periodogram": (0, 1, 2, 64), "transit": (1, 4, 1, 32), "keplerian": (2, 3, 2, 128)}
+
+
+def trial_projections(kind, t, alpha, trials, *, t_ref=0.0, out=None):
+    """P (B, K, C, R): P[b, k, c, r] = sum_n col_c(trial k; t[b, n]) alpha[b, n, r] for alpha (B, N, R), t (N,) shared by the
+    batch or (B, N), and the trials of `kind`: "periodogram" (ANGULAR frequencies (K,) | (B, K); columns cos, sin of
+    w (t - t_ref); C = 2), "transit" ((K, 4) | (B, K, 4) = (P, t0, w, tau); the template; C = 1) or "keplerian" ((K, 3) |
+    (B, K, 3) = (w, e, tp); columns cos nu, sin nu; C = 2).  The columns are formed in registers, bit for bit the ones
+    `whitened_sinusoids` / `whitened_transits` / `whitened_keplerians` whiten, and contracted with alpha on the matrix cores
+    (c2_trial_projections, csrc/c2_trial_project.hip): with alpha = (K + D)^-1 (y_r - mean), P is the one entry of those ops'
+    T that depends on y, for R series y_r at once.  What gp.search_significance reads.  Caller-owned `out` is accepted
+    (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No atomics: two calls give
+    identical bits."""
+    if kind not in TRIAL_KINDS:
+        raise ValueError("kind must be one of %s" % (tuple(TRIAL_KINDS),))
+    code, words, C, _ = TRIAL_KINDS[kind]
+    if alpha.dim() != 3:
+        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
+    B, N, R = alpha.shape
+    if code == 0:
+        if trials.dim() not in (1, 2):
+            raise ValueError("Invalid shape: trials (must be (K,) or (B, K))")
+        K, spec, shared = trials.shape[-1], "K|BK", trials.dim() == 1
+    else:
+        if trials.dim() not in (2, 3) or trials.shape[-1] != words:
+            raise ValueError("Invalid shape: trials (must be (K, %d) or (B, K, %d))" % (words, words))
+        K, spec, shared = trials.shape[-2], "KF|BKF", trials.dim() == 2
+    dims = dict(B=B, N=N, R=R, K=K, F=words, C=C)
+    if out is None:
+        out, = _empty(alpha.device, dims, "BKCR")
+    _args(dims, [("t", t, _T), ("alpha", alpha, "BNR"), ("trials", trials, spec)], [("out", out, "BKCR")])
+    rc = _lib.load().c2_trial_projections(code, B, N, K, R, t, _bs(t, N), trials, 0 if shared else words * K, float(t_ref),
+                                          alpha, out, _stream())
+    _lib.check(rc, "trial_projections")
     return out
 
 
