@@ -453,7 +453,7 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_fwd(int64_t B, int64_t N,
         // (b) the chain of step n
         fwd_chain<G>(pc, uc, v, an, yn, pXc, uXc, SX, F, w, d, z, rd, xs[2], lane);
         if (REC) {
-          if (FACTOR && stw && (((fl == 0) & (d > 0.0)) | (n == 0))) wst[n * J] = w;   // (W_0 unconditionally: forward.hpp:108)
+          if (FACTOR && stw && (((fl == 0) & !(d <= 0.0)) | (n == 0))) wst[n * J] = w;   // (W_0 unconditionally: forward.hpp:108; a NaN pivot passes `d <= 0` and stores its row, as the reference does)
           if (CKPT && wrec) wrp[(size_t)n * kWave] = w;
           sout[grp][r] = make_double2(d, z);
         }
@@ -726,6 +726,17 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
   double carR = rcp_nr(carDZ.x);
   // FR: the last row's W and bW (seeds: bV_{N-1} = bW_{N-1}/d_{N-1}, ba_{N-1} = bd_{N-1} - W_{N-1}.bV_{N-1})
   const double wlast = (FR && act) ? Vb[(N - 1) * J] : 0.0, bwlast = (FR && act) ? fbWb[(N - 1) * J] : 0.0;
+  // log-likelihood: what stands for W_{N-1} in the seed of ba_{N-1} = ... - W_{N-1} . bV_{N-1} (reverse.hpp:65).  bV_{N-1} is
+  // 0 / d_{N-1}, so the product is +-0 or NaN and only the FINITENESS of the factor matters.  BACK: the recorded row W_{N-1}
+  // itself.  The replay has not formed W_{N-1} = (V_{N-1} - tau) / d_{N-1} when it seeds and takes V_{N-1}: this is NOT the
+  // reference's expression, only equivalent to it in finiteness -- W_{N-1} is not finite iff V_{N-1} is not, or tau or
+  // d_{N-1} is not, and a non-finite tau makes d_{N-1} = a - tau . u non-finite, which bV_{N-1} already carries.
+  // Coefficient level: U, V are not inputs (a NaN coefficient reaches d_{N-1}).
+  double wl0 = 0.0;
+  if constexpr (!FR && !TT) {
+    if constexpr (BACK) wl0 = V[((size_t)blockIdx.x * N + (N - 1)) * kWave + lane];
+    else wl0 = act ? Vb[(N - 1) * J] : 0.0;
+  }
   if (nseg > 0) load_segment(nseg - 1);
   // -DC2_REV_TIMING: s_memtime deltas of the four phases, summed per wavefront into c2_dbg (tools/rev_phase_timing.py)
 #ifdef C2_REV_TIMING
@@ -891,9 +902,10 @@ __global__ __launch_bounds__(kWave, OCC) void k_loglik_rev(int64_t B, int64_t N,
         bVn = bwlast * rd;
         ban = z - gsum<G>(wlast * bwlast) * rd;
       } else {
-        ban = 0.5 * rd * (z * z * rd - 1.0);
         bzn = -z * rd;
-        bVn = 0.0;
+        bVn = 0.0 * rd;   // bW_{N-1} / d_{N-1}, bW_{N-1} = 0 (reverse.hpp:55): NaN behind a NaN pivot, as the reference's division
+        // ... minus W_{N-1} . bV_{N-1} (reverse.hpp:65): +-0 unless W_{N-1} is not finite, which turns every gradient NaN
+        ban = 0.5 * rd * (z * z * rd - 1.0) - gsum<G>(wl0 * bVn);
         if (st0) byb[N - 1] = bzn;
       }
       if (st0) bab[N - 1] = ban;   // (the rows below leave with their segments' runs)
@@ -1379,6 +1391,13 @@ extern "C" void c2_internal_set_debug_sink(double *device_ptr) { g_debug_sink = 
 extern "C" double *c2_internal_get_debug_sink() { return g_debug_sink; }
 // C2_VERIFY_FALLBACK=0 (diagnostics only): leave the result of the time-parallel form in place whatever its words say
 static bool verify_fallback_enabled() { return !opt::off(opt::k_verify_fallback); }
+// raises `guard` (a launch-wide gate word, gate_closed) when a series of the batch failed or its log-likelihood is not finite
+__global__ void k_ll_guard(int64_t B, const double *__restrict__ ll, const int32_t *__restrict__ flag,
+                           unsigned long long *__restrict__ guard) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B && (flag[b] != 0 || !(fabs(ll[b]) < __builtin_huge_val())))
+    atomicMax(guard, (unsigned long long)__double_as_longlong(__builtin_inf()));
+}
 static void c2_internal_debug_capture(const double *words, const double *, hipStream_t s) {
   if (g_debug_sink) (void)hipMemcpyAsync(g_debug_sink, words, kTimeparVerifyWords * sizeof(double), hipMemcpyDeviceToDevice, s);
 }
@@ -1475,8 +1494,22 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
     // d, W by Newton iterations on the chunk start states, z by the chunk-map solve, a reduction
     const size_t nd = c2_internal_loglik_wide_doubles(B, N, J);
     void *tmp = nullptr;
-    if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
-      int rc = c2_internal_loglik_wide(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
+    if (nd > 0 && c2::temp_alloc(&tmp, (nd + 1) * sizeof(double), s) == hipSuccess) {
+      // That form composes c2_factor -- which hands a batch with a failed or NaN pivot to the row-by-row factor on its own --
+      // with the chunk-map solve: its healthy series would then carry the bits of neither formulation.  Behind a series
+      // that failed (flag != 0: an ordinary non positive definite matrix as much as a NaN -- c2_factor has fallen back for
+      // the batch there already) or whose value is not finite, the row-by-row kernel recomputes the batch: k_ll_guard opens
+      // its gate.  A healthy batch pays the two launches (the gated kernel returns at once).
+      unsigned long long *guard = (unsigned long long *)((double *)tmp + nd);
+      int rc = hip_check(hipMemsetAsync(guard, 0, sizeof(unsigned long long), s));
+      if (rc == C2_OK) rc = c2_internal_loglik_wide(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
+      if (rc == C2_OK && verify_fallback_enabled()) {
+        hipLaunchKernelGGL(k_ll_guard, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const double *)ll,
+                           (const int32_t *)flag, guard);
+        rc = launch_ok();
+        if (rc == C2_OK)
+          rc = launch_fwd<0>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, nullptr, 0, nullptr, nullptr, s, guard);
+      }
       rc = keep_first(rc, hipFreeAsync(tmp, s));
       return rc;
     }

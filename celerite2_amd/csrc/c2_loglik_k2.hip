@@ -585,6 +585,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   const double rdl = 1.0 / fabs(dzl.x);
   double ban = 0.5 * rdl * (dzl.y * dzl.y * rdl - 1.0), bzn = -dzl.y * rdl;   // seeds of the last row
   if (failed) { ban = nan; bzn = nan; }
+  // bV_{N-1} = bW_{N-1} / d_{N-1} with bW_{N-1} = 0 (reverse.hpp:55): +0 behind a positive pivot, NaN behind a NaN one -- the
+  // reference divides, it does not select
+  if (!failed) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) bVn[j] = 0.0 * rdl;
+  }
   double tcur = recT[(size_t)nf * SPW + sl];
 
   // slots are consumed in reverse order of writing
@@ -611,6 +617,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   if (N >= 2) {
     // ---- prologue: bV, ba, by of the last row are pure seeds ---------------------------------------------------------------
     const int ph0 = (int)(nf & 1);
+    {  // ba_{N-1} -= W_{N-1} . bV_{N-1} (reverse.hpp:65): +-0 unless the recorded W_{N-1} is not finite, which turns every gradient NaN
+      double wl[J];
+      w_fetch(nf, wl);
+#pragma unroll
+      for (int j = 0; j < J; ++j) ban = fma(-wl[j], bVn[j], ban);
+    }
     if constexpr (!TERMS) row_write_half(tBV, sl, h, ph0, bVn);
     tBA[sl * SSTRR + (nf & (STR - 1))] = ban;
     tBY[sl * SSTRR + (nf & (STR - 1))] = bzn;

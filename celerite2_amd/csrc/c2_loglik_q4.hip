@@ -703,9 +703,11 @@ __global__ __launch_bounds__(kWave, 1) void k_q4_rev(int64_t B, int64_t N, const
     }
     if (k == nseg - 1) {   // cotangents of the last row: pure seeds
       const double rdl = rowR[cnt][grp], zl = rowZ[cnt][grp];
-      ban = 0.5 * rdl * (zl * zl * rdl - 1.0);
       bzn = -zl * rdl;
-      bVn[0] = 0.0; bVn[1] = 0.0;
+      bVn[0] = 0.0 * rdl; bVn[1] = bVn[0];   // bW_{N-1} / d_{N-1}, bW_{N-1} = 0 (reverse.hpp:55): NaN behind a NaN pivot, as the reference's division
+      // ... minus W_{N-1} . bV_{N-1} (reverse.hpp:65): +-0 unless the recorded W_{N-1} is not finite, which turns every gradient NaN
+      const double2 wl = wrp[(size_t)(N - 1) * kWave];
+      ban = 0.5 * rdl * (zl * zl * rdl - 1.0) - gsum<LG>(fma(wl.x, bVn[0], wl.y * bVn[1]));
       if (alive) { byb[N - 1] = bzn; bab[N - 1] = ban; }
     }
     carT = rowT[0][grp]; carDZ = make_double2(rowD[0][grp], rowZ[0][grp]); carR = rowR[0][grp];

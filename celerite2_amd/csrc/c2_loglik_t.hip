@@ -891,6 +891,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
   // A failed series gets NaN seeds: every gradient of the series is an arithmetic function of them (bF <- u bz,
   // M <- x = bV + 2 ba u, bp <- F bF + ..., bt <- bp, bc <- bp), so NaN reaches all six outputs by propagation.
   if (failed) { ban = nan; bzn = nan; }
+  // bV_{N-1} = bW_{N-1} / d_{N-1} with bW_{N-1} = 0 (reverse.hpp:55): +0 behind a positive pivot, NaN behind a NaN one -- the
+  // reference divides, it does not select
+  if (!failed) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) bVn[j] = 0.0 * rdl;
+  }
   double tcur = recT[(size_t)(N - 1) * rs1 + lane];
 
   // The recorded S / F of a checkpointed row replace the recursed ones.  The 36 elements of S go straight into their
@@ -942,6 +948,12 @@ __device__ __forceinline__ void rev_body(int64_t B, int64_t N, const double *__r
     // series): it leaves at once; otherwise it waits in row 1 of the pair tile for the first (odd) step
     const int ph0 = (int)(nf % RT);          // row of the last row inside its tile
     const bool bv_seed_waits = BVPAIR && ph0 != 0;
+    {  // ba_{N-1} -= W_{N-1} . bV_{N-1} (reverse.hpp:65): +-0 unless the recorded W_{N-1} is not finite, which turns every gradient NaN
+      double wl[J];
+      w_fetch(nf, wl);
+#pragma unroll
+      for (int j = 0; j < J; ++j) ban = fma(-wl[j], bVn[j], ban);
+    }
     if constexpr (!TERMS) {
       if (bv_seed_waits) row_write(tBV, lane, ph0, bVn);
       else row1_write(tBV, lane, bVn);

@@ -38,6 +38,21 @@
  *     definite matrix is NOT an error code: `flag[b]` receives the first row
  *     index n >= 1 with d[n] <= 0, or 0 on success (forward.hpp:128,134), and
  *     rows 0..n of d / 0..n-1 of W are already written, as in the reference.
+ *   - Non-finite values.  A NaN or an infinity in a, U, V, y, a right-hand side
+ *     or a cotangent is handled per series as the reference handles it: the
+ *     only test is `d[n] <= 0`, which a NaN pivot passes, so such a series
+ *     keeps flag 0 (-inf on the diagonal fails the test like any non-positive
+ *     pivot), the NaN propagates through the recursions as IEEE arithmetic
+ *     carries it (rows before it in a lower sweep or a factorisation, rows
+ *     after it in an upper sweep, and every other right-hand-side column stay
+ *     finite), nothing is sanitised and nothing is reported.  No other series
+ *     of the batch is affected: its results are those it would have had
+ *     without the poisoned neighbour, up to WHICH formulation computed them
+ *     (a time-parallel form hands the whole batch to the row-by-row kernels
+ *     when its device-side verification sees a NaN; either one meets the same
+ *     accuracy).  Non-finite TIMES and RATES (t, c, query times, trial grids,
+ *     frequencies) are outside this contract: they steer merges and searches,
+ *     and the Python front end rejects such grids.
  *
  * Two families
  *   c2_*   device entry points: every pointer is a DEVICE pointer, there is a
