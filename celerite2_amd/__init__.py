@@ -9,6 +9,7 @@ semiseparable GP linear algebra.
     celerite2_amd.periodogram                       the periodogram under correlated noise: the torch part
     celerite2_amd.transit                           the transit search under correlated noise: the torch part
     celerite2_amd.kepler                            the Keplerian search under correlated noise: the torch part
+    celerite2_amd.shapes                            the tabulated-shape search under correlated noise: builders, the torch part
 
 Nothing is imported eagerly: the compiled pieces fail loudly on first use if the
 HIP library has not been built (`python -m celerite2_amd.build`).

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
-celerite2_amd_transit.h, celerite2_amd_kepler.h and celerite2_amd_trials.h).
+celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h and celerite2_amd_shapes.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -18,6 +18,7 @@ PERIODOGRAM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_
 TRANSIT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_transit.h")   # the transit search
 KEPLER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_kepler.h")   # the Keplerian search
 TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_trials.h")   # projections on trial columns
+SHAPES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_shapes.h")   # the tabulated-shape search
 
 
 class BackendError(RuntimeError):
@@ -111,6 +112,9 @@ KEPLER_SYMBOLS = ["c2_whitened_keplerians"]
 # Every symbol include/celerite2_amd_trials.h declares (checked by tests/test_significance.py).
 TRIALS_SYMBOLS = ["c2_trial_projections"]
 
+# Every symbol include/celerite2_amd_shapes.h declares (checked by tests/test_shapes.py).
+SHAPES_SYMBOLS = ["c2_whitened_shapes", "c2_shape_projections"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -179,6 +183,7 @@ def load():
     protos.update(_prototypes(_header(TRANSIT_HEADER)))
     protos.update(_prototypes(_header(KEPLER_HEADER)))
     protos.update(_prototypes(_header(TRIALS_HEADER)))
+    protos.update(_prototypes(_header(SHAPES_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

@@ -1,0 +1,120 @@
+// c2_shape_project.hip -- THE PROJECTIONS OF MANY VECTORS ON THE COLUMNS OF A TABULATED-SHAPE TRIAL GRID
+// (c2_shape_projections, include/celerite2_amd_shapes.h): for every series b, trial k and vector r,
+//   P[b, k, r] = sum_n b_k(t[b, n]) * alpha[b, n, r]
+// with the column formed in registers by the very function the whitening sweep uses (shape::value, c2_shape_column.hpp), so
+// the column values are c2_whitened_shapes' bit for bit.  With alpha = (K + D)^-1 (y_r - mean) this is gty_r of a shape
+// search for R series y_r at once: what its Monte-Carlo false-alarm probability reads (celerite2_amd/significance.py).  No
+// counterpart in the reference.
+//
+// k_shape_project<NQ> restates k_project's walk (c2_trial_project.hip) for a one-column kind: ONE WAVEFRONT takes 16 trials
+// and RB = 16 NQ vectors and walks all N rows four at a time on the matrix cores, v_mfma_f64_16x16x4_f64 (lane maps:
+// tools/ubench/mfma64.hip):
+//   A operand: lane l forms the column value of trial k0 + (l & 15) at row n0 + (l >> 4) -- one value per lane, in place;
+//   B operand of vector tile q: alpha[b, n0 + (l >> 4), r0 + 16 q + (l & 15)] (16 lanes read 128 contiguous bytes);
+//   C/D: one 4-register accumulator per tile: lane l holds trials k0 + (l >> 4) + 4 reg, vector r0 + 16 q + (l & 15), so the
+//        stores along r are contiguous.
+// The next step's B values and time are loaded before this step's column is formed.  Tails: a row n >= N loads row N - 1
+// and takes A = 0; a trial k >= K is the null trial (0, 0, 0, 0) and stores nothing; a vector r >= R loads 0 and stores
+// nothing.  Every element of P is written by exactly one lane: no atomics, no allocation, no host read, two calls give
+// identical bits.  Blocks: B * ceil(R / RB) * ceil(K / 16) in grid.x, the trial blocks of one (series, vector block) next to
+// each other (they read the same rows of alpha).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "c2_common.hpp"
+#include "c2_loglik_helpers.hpp"
+#include "../../include/celerite2_amd_shapes.h"
+#include "c2_launch.hpp"
+#include "c2_shape_column.hpp"
+
+namespace c2 {
+namespace shape {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ d4 mfma(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+template <int NQ>
+__global__ __launch_bounds__(kWave) void k_shape_project(int64_t N, int64_t K, int64_t R, int64_t KB, int64_t RBn,
+                                                         const double *__restrict__ t, int64_t t_bs,
+                                                         const double *__restrict__ trials, int64_t tr_bs,
+                                                         const double *__restrict__ alpha, double *__restrict__ P,
+                                                         const double *__restrict__ shapes, int64_t sh_bs, int NS, int S) {
+  const int l = threadIdx.x, lo = l & 15, hi = l >> 4;
+  const int64_t kb = blockIdx.x % KB, rb = (blockIdx.x / KB) % RBn, b = blockIdx.x / (KB * RBn);
+  const int64_t k0 = kb * 16, r0 = rb * (16 * NQ);
+  const bool live = k0 + lo < K;
+  const Trial tr = make_trial(trials + b * tr_bs + (live ? k0 + lo : 0) * 4, live, shapes + b * sh_bs, NS, S);
+
+  const double *tb = t + b * t_bs, *ab = alpha + b * N * R;
+  // this lane's vectors: one per tile (clamped for the load, zeroed after it)
+  bool rlive[NQ];
+  int64_t rcol[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int64_t r = r0 + 16 * q + lo;
+    rlive[q] = r < R;
+    rcol[q] = rlive[q] ? r : R - 1;
+  }
+
+  d4 acc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
+
+  // the step at rows n0 .. n0 + 3: this lane's row, clamped to the series
+  auto load = [&](int64_t n0, double &tn, double (&bv)[NQ]) {
+    const int64_t n = n0 + hi < N ? n0 + hi : N - 1;
+    tn = tb[n];
+    const double *ar = ab + n * R;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) bv[q] = ar[rcol[q]];
+  };
+
+  double tn, bv[NQ];
+  load(0, tn, bv);
+  for (int64_t n0 = 0; n0 < N; n0 += 4) {
+    double tnext, bnext[NQ];
+    load(n0 + 4 < N ? n0 + 4 : n0, tnext, bnext);            // (the last step loads its own rows again)
+    double a = value(tr, tn);
+    a = n0 + hi < N ? a : 0.0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = mfma(a, rlive[q] ? bv[q] : 0.0, acc[q]);
+    tn = tnext;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) bv[q] = bnext[q];
+  }
+
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int64_t k = k0 + hi + 4 * reg;
+    if (k < K) {
+      double *Pk = P + (b * K + k) * R;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        if (rlive[q]) Pk[rcol[q]] = acc[q][reg];
+    }
+  }
+}
+
+}  // namespace shape
+}  // namespace c2
+
+using namespace c2;
+using namespace c2::shape;
+
+extern "C" int c2_shape_projections(int64_t B, int64_t N, int64_t K, int64_t R, const double *t, int64_t t_bs,
+                                    const double *trials, int64_t tr_bs, const double *alpha, double *P, const double *shapes,
+                                    int64_t sh_bs, int64_t NS, int64_t S, c2_stream_t stream) {
+  constexpr int NQ = C2_SHAPE_DRAWS / 16;
+  static_assert(C2_SHAPE_DRAWS % 16 == 0 && NQ >= 1, "C2_SHAPE_DRAWS is a multiple of 16");
+  if (B < 1 || N < 1 || K < 1 || R < 1 || NS < 1 || S < 2) return C2_ERR_INVALID;
+  if (NS > kMaxNodes || S > kMaxNodes || NS * S > kMaxNodes) return C2_ERR_UNSUPPORTED;
+  if (!t || !trials || !alpha || !P || !shapes) return C2_ERR_INVALID;
+  if (t_bs < 0 || tr_bs < 0 || (sh_bs != 0 && sh_bs != NS * S)) return C2_ERR_INVALID;
+  const int64_t KB = (K + 15) / 16, RBn = (R + 16 * NQ - 1) / (16 * NQ);
+  if (KB > 0x7fffffffLL || RBn > 0x7fffffffLL / KB || B > 0x7fffffffLL / (KB * RBn)) return C2_ERR_UNSUPPORTED;   // 2^31 blocks or more
+  hipLaunchKernelGGL((k_shape_project<NQ>), dim3((unsigned)(B * KB * RBn)), dim3(kWave), 0, (hipStream_t)stream, N, K, R, KB,
+                     RBn, t, t_bs, trials, tr_bs, alpha, P, shapes, sh_bs, (int)NS, (int)S);
+  return launch_ok();
+}

@@ -549,6 +549,110 @@ class GaussianProcess:
         # criterion's relative part counts as at or above -- the larger probability)
         return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
 
+    # -- the tabulated-shape search under the factored covariance (ops.whitened_shapes; no counterpart in the reference) --
+    def _shape_args(self, trials, shapes):
+        """(trials, shapes, NS) contiguous, after the shape checks of shape_search and shape_search_significance."""
+        B = self._diag.shape[0]
+        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
+                or trials.shape[-1] != 4 or trials.shape[-2] < 1:
+            raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4) with B = %d, K >= 1)" % B)
+        if not torch.is_tensor(shapes) or shapes.dim() not in (2, 3) or (shapes.dim() == 3 and shapes.shape[0] != B):
+            raise ValueError("Invalid shape: shapes (must be (NS, S) or (B, NS, S) with B = %d)" % B)
+        return trials.contiguous(), shapes.contiguous(), shapes.shape[-2]
+
+    def shape_search(self, y, trials, shapes, *, A="mean", return_fit=False):
+        """Least squares of `y` (B, N) with an event of a TABULATED SHAPE under the factored covariance, (B, K): for each
+        trial (period P, epoch t0, width w, shape index s) of `trials` ((K, 4) shared | (B, K, 4); shapes.trial_grid makes a
+        folded grid) the model y = mean + A beta0 + delta b_k(t) + GP is fitted by generalized least squares and compared
+        with the fit without the event (chi2_null - chi2 = delta_chi2).  b_k is the s-th row of the bank `shapes` ((NS, S)
+        shared | (B, NS, S), NS * S <= 1024; shapes.limb_darkened, flare, trapezoid, box and stack build one), S values on a
+        uniform grid from the leading to the trailing edge of an event of full width w centred on t0, linearly interpolated,
+        zero outside, folded at P or a single event when P = 0 (include/celerite2_amd_shapes.h has the rule).  `A`: the
+        nuisance columns, as for `periodogram`.  `return_fit=True`: shapes.ShapeSearch(delta_chi2, amplitude,
+        amplitude_err, snr (each (B, K)), chi2_null (B,)); a dip under a shape with peak +1 has a negative amplitude.
+        One solve_lower with P0 + 1 columns, one sweep with a lane per trial (ops.whitened_shapes), then torch on (B, K, .)
+        arrays (celerite2_amd/shapes.py).  Not differentiable and never raising under compute(..., quiet=True): a trial with
+        no sample in the event, one whose column lies in the span of A, one outside w > 0, P >= 0, w <= P (P > 0), (P, t0, w)
+        finite, s an integer in [0, NS), a series whose factorisation failed or whose A is rank-deficient, and every trial
+        when N < P0 + 2 hold NaN.  J <= 32."""
+        from . import _trial_fit, shapes as sh
+
+        self._need()
+        self._check_vector(y)
+        N = self._diag.shape[1]
+        trials, shapes, NS = self._shape_args(trials, shapes)
+        Z0 = self._whitened_columns(y, A)
+        T = ops.whitened_shapes(self._t, self._c, self._U, self._W, self._d, Z0, trials, shapes)
+        fit = self._nan_failed_fit(sh.finish(_trial_fit.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials,
+                                             n_shapes=NS))
+        return fit if return_fit else fit.delta_chi2
+
+    def shape_search_significance(self, y, trials, shapes, *, draws=1000, A="mean", normalization="standard", dips_only=False,
+                                  generator=None, normals=None, max_trials=None, max_draws=None):
+        """`shape_search` on `y` (B, N) with the Monte-Carlo false-alarm probability of every trial:
+        significance.Significance(statistic (B, K), fap (B, K), null_maxima (B, draws)) -- `search_significance`'s transit
+        branch with the tabulated column: `statistic` is delta_chi2 / chi2_null ("standard"), delta_chi2 ("chi2") or half
+        of it ("log_likelihood"), with `dips_only` 0 where the fitted amplitude is positive; `null_maxima[b, r]` the largest
+        statistic over the trials (NaN ones ignored) of the same search on the r-th draw y_r = mean + L D^1/2 n_r, and
+        fap = (1 + #{r : null_maxima[b, r] >= statistic}) / (draws + 1).  The probability is CONDITIONAL ON THE
+        HYPER-PARAMETERS, as there.  One sweep on `y`; a draw adds one column to one solve_upper and to
+        ops.shape_projections -- no sweep per draw.  `normals`, `generator`, `max_trials` (same bits), `max_draws` (to
+        rounding), `A`: as for `search_significance`.  Not differentiable and never raising under
+        compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32."""
+        from . import _trial_fit, periodogram as pg, shapes as sh, significance as sg
+
+        self._need()
+        self._check_vector(y)
+        (B, N), dev = self._diag.shape, self._diag.device
+        if normalization not in pg.NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
+        trials, shapes, NS = self._shape_args(trials, shapes)
+        if normals is not None:
+            if not torch.is_tensor(normals) or normals.dim() != 3 or tuple(normals.shape[:2]) != (B, N):
+                raise ValueError("Invalid shape: normals (must be (B, N, draws) = (%d, %d, draws))" % (B, N))
+            draws = normals.shape[-1]
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError("draws must be at least 1")
+        K = trials.shape[-2]
+        kstep = K if max_trials is None else int(max_trials)
+        rstep = draws if max_draws is None else int(max_draws)
+        if kstep < 1 or rstep < 1:
+            raise ValueError("max_trials and max_draws must be at least 1")
+        ok = self._flag == 0
+        Z0 = self._whitened_columns(y, A)
+        S0 = _trial_fit.null_products(Z0, self._d)
+        T = ops.whitened_shapes(self._t, self._c, self._U, self._W, self._d, Z0, trials, shapes)
+        fit = sh.finish(S0, T, N, ok=ok, trials=trials, n_shapes=NS)
+        statistic = sg._normalize(fit.delta_chi2, fit.chi2_null[:, None], normalization)
+        if dips_only:
+            statistic = torch.where(fit.amplitude > 0, torch.zeros_like(statistic), statistic)
+        statistic, = self._nan_failed(statistic)
+        if normals is None:
+            normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
+        rsd = torch.rsqrt(self._d)[..., None]
+        ZA = Z0[..., :-1].transpose(1, 2)                                        # (B, P0, N)
+        per_series = trials.dim() == 3
+        nan = torch.full((), math.nan, dtype=torch.float64, device=dev)
+        maxima = []
+        for r0 in range(0, draws, rstep):
+            n = normals[..., r0:r0 + rstep]
+            scaled = (n * rsd).contiguous()                                      # D^-1/2 n_r
+            s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
+            alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
+            best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
+            for k0 in range(0, K, kstep):
+                tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
+                P = ops.shape_projections(self._t, alpha, tk, shapes)
+                stat = sg.null_statistics("transit", S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization=normalization,
+                                          trials=None, dips_only=dips_only, ok=ok)
+                stat = torch.where(sh.in_domain(tk, NS).expand(B, tk.shape[-2])[..., None], stat, nan)
+                best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
+            maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
+        null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
+        # (a tie to the standing criterion's relative part counts as at or above, as in search_significance)
+        return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
+
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):
         """Draws (B, M) -- (B, size, M) when `size` is given -- from the conditional distribution of the process at the

@@ -29,7 +29,7 @@ __all__ = [
 # include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h, celerite2_amd_kepler.h and
 # celerite2_amd_trials.h, are public as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
 # _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
-# include/celerite2_amd.h)
+# include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS)
 
 
 def _p(x):
@@ -557,6 +557,81 @@ def trial_projections(kind, t, alpha, trials, *, t_ref=0.0, out=None):
     rc = _lib.load().c2_trial_projections(code, B, N, K, R, t, _bs(t, N), trials, 0 if shared else words * K, float(t_ref),
                                           alpha, out, _stream())
     _lib.check(rc, "trial_projections")
+    return out
+
+
+SHAPE_MAX_NODES, SHAPE_DRAWS = 1024, 32   # C2_SHAPE_MAX_NODES, C2_SHAPE_DRAWS of celerite2_amd_shapes.h
+
+
+def _bank(shapes, B):
+    """(NS, S, batch stride) of a shape bank (NS, S) | (B, NS, S); its limits are checked here, from its shape."""
+    if shapes.dim() not in (2, 3) or (shapes.dim() == 3 and shapes.shape[0] != B):
+        raise ValueError("Invalid shape: shapes (must be (NS, S) or (B, NS, S) with B = %d)" % B)
+    NS, S = shapes.shape[-2:]
+    if NS < 1 or S < 2:
+        raise ValueError("Invalid shape: shapes (NS >= 1 shapes of S >= 2 nodes; got NS = %d, S = %d)" % (NS, S))
+    if NS * S > SHAPE_MAX_NODES:
+        raise ValueError("Invalid shape: shapes (NS * S <= %d; got %d * %d = %d -- a larger bank takes several calls)"
+                         % (SHAPE_MAX_NODES, NS, S, NS * S))
+    return NS, S, 0 if shapes.dim() == 2 else NS * S
+
+
+def whitened_shapes(t, c, U, W, d, Z0, trials, shapes, *, out=None):
+    """T (B, K, 1 + Q0): for every series and every trial (period P, epoch t0, width w, shape index s) of `trials` ((K, 4)
+    shared by the batch or (B, K, 4)) and the bank `shapes` ((NS, S) shared or (B, NS, S): NS event profiles tabulated on S
+    uniform nodes from the leading to the trailing edge; NS * S <= 1024), with z = L^-1 b_k(t) and
+    <a, b> = sum_n a_n b_n / d_n,
+
+        T[b, k] = [<z, z>, <z, Z0[:, j]> for j < Q0]
+
+    (the layout of `whitened_transits`) from the factors (d, W) of `factor` and Z0 (B, N, Q0) = solve_lower of
+    [A0 | y - mean], in one forward sweep that interpolates the shape in registers, one lane per trial (c2_whitened_shapes,
+    csrc/c2_shapes.hip; include/celerite2_amd_shapes.h has the rule; P = 0 is a single event, P > 0 folds).  What the shape
+    search under correlated noise reads (celerite2_amd/shapes.py).  Every trial is evaluated as written and none can read
+    outside the bank (the index is clamped); the domain is the caller's to mask.  Caller-owned `out` is accepted (nothing
+    is allocated then: capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two
+    calls give identical bits."""
+    B, N, J = _dims(U)
+    if Z0.dim() != 3:
+        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
+    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
+        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
+    NS, S, sh_bs = _bank(shapes, B)
+    Q0, K = Z0.shape[-1], trials.shape[-2]
+    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=4, R=1 + Q0, H=NS, S=S)
+    if out is None:
+        out, = _empty(U.device, dims, "BKR")
+    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
+                 ("trials", trials, "KF|BKF"), ("shapes", shapes, "HS|BHS")], [("out", out, "BKR")])
+    rc = _lib.load().c2_whitened_shapes(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
+                                        0 if trials.dim() == 2 else 4 * K, out, shapes, sh_bs, NS, S, _stream())
+    _lib.check(rc, "whitened_shapes")
+    return out
+
+
+def shape_projections(t, alpha, trials, shapes, *, out=None):
+    """P (B, K, 1, R): P[b, k, 0, r] = sum_n b_k(t[b, n]) alpha[b, n, r] for alpha (B, N, R), t (N,) shared by the batch or
+    (B, N), the trials (K, 4) | (B, K, 4) = (P, t0, w, s) and the bank `shapes` (NS, S) | (B, NS, S) of `whitened_shapes`:
+    `trial_projections` for the tabulated shape, in the layout significance.null_statistics takes for a one-column kind.
+    The column is formed in registers, bit for bit the one `whitened_shapes` whitens, and contracted with alpha on the
+    matrix cores (c2_shape_projections, csrc/c2_shape_project.hip).  What gp.shape_search_significance reads.  Caller-owned
+    `out` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No atomics: two
+    calls give identical bits."""
+    if alpha.dim() != 3:
+        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
+    B, N, R = alpha.shape
+    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
+        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
+    NS, S, sh_bs = _bank(shapes, B)
+    K = trials.shape[-2]
+    dims = dict(B=B, N=N, R=R, K=K, F=4, C=1, H=NS, S=S)
+    if out is None:
+        out, = _empty(alpha.device, dims, "BKCR")
+    _args(dims, [("t", t, _T), ("alpha", alpha, "BNR"), ("trials", trials, "KF|BKF"), ("shapes", shapes, "HS|BHS")],
+          [("out", out, "BKCR")])
+    rc = _lib.load().c2_shape_projections(B, N, K, R, t, _bs(t, N), trials, 0 if trials.dim() == 2 else 4 * K, alpha, out,
+                                          shapes, sh_bs, NS, S, _stream())
+    _lib.check(rc, "shape_projections")
     return out
 
 
