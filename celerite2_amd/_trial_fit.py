@@ -17,12 +17,12 @@ def null_products(Z0, d):
 
 
 def null_fit(S0, T, ok, layout, cross):
-    """(S0, T, bad, chi2_0, v, X) for S0 (B, Q0, Q0) and T (B, K, width); `layout` = (K's name, the width in words, the
+    """(S0, T, bad, chi2_0, v, X, L0) for S0 (B, Q0, Q0) and T (B, K, width); `layout` = (K's name, the width in words, the
     width), e.g. ("F", "3 + 2 Q0", 3 + 2 * Q0).  `ok` (B,) | None: series to take at all; S0, T come back with the others
     replaced by the identity and zeros, and `bad` (B,) holds them and the series whose G00 is rank-deficient (to _RANK_TOL of
     its own diagonal) or did not factor.  `cross`: the first columns of the slices T[..., i:i + P0] that hold the trial
     columns' products with A0; X (B, P0, K) -- for two slices (B, P0, 2 K), side by side -- is L0^-1 of them and v (B, P0) =
-    L0^-1 g0y; both None when P0 = 0."""
+    L0^-1 g0y; L0 (B, P0, P0) the factor of G00, the identity in a bad series; all three None when P0 = 0."""
     B, Q0 = S0.shape[0], S0.shape[-1]
     if S0.dim() != 3 or S0.shape[1] != Q0 or Q0 < 1:
         raise ValueError("Invalid shape: S0 (must be (B, Q0, Q0), Q0 >= 1)")
@@ -36,7 +36,7 @@ def null_fit(S0, T, ok, layout, cross):
     bad = torch.zeros(B, dtype=torch.bool, device=S0.device) if ok is None else ~ok
     s_yy = S0[:, P0, P0]
     if not P0:
-        return S0, T, bad, s_yy, None, None
+        return S0, T, bad, s_yy, None, None, None
     G00, g0y = S0[:, :P0, :P0], S0[:, :P0, P0]
     L0, info = torch.linalg.cholesky_ex(G00)
     bad = bad | (info != 0)
@@ -47,4 +47,4 @@ def null_fit(S0, T, ok, layout, cross):
     Gt0 = [T[..., i:i + P0] for i in cross]
     Gt0 = torch.cat(Gt0, dim=1) if len(Gt0) > 1 else Gt0[0]
     X = torch.linalg.solve_triangular(L0, Gt0.transpose(1, 2), upper=False)
-    return S0, T, bad, s_yy - (v * v).sum(dim=-1), v, X
+    return S0, T, bad, s_yy - (v * v).sum(dim=-1), v, X, L0

@@ -29,7 +29,7 @@ inline auto dispatch_group(int64_t J, F &&f) {
   }
 }
 
-// the kernels that keep a J- or Q-long vector in registers pad it to 4, 8, 16 or 32 (k_gram, k_sinusoids, k_transits, k_keplerians)
+// the kernels that keep a J- or Q-long vector in registers pad it to 4, 8, 16 or 32 (k_gram, k_trial_sweep)
 inline int padded(int64_t n) { return n <= 4 ? 4 : group_size(n); }
 
 // f(std::integral_constant<int, R>{}) for R = padded(n); f(... group_size(n)) for n <= 8 columns (1, 2, 4 or 8)

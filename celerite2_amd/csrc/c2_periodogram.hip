@@ -12,133 +12,21 @@
 // The phase is two roundings, the difference and then the product, neither contracted into a later fma: numpy forms it the
 // same way, so a restatement has the argument bit for bit.  sincos_cw takes its fast path below kSincosFastMax.
 //
-// k_sinusoids<JR, QR> (JR: J rounded up to 4, 8, 16 or 32; QR: Q0 rounded up to 1, 2, 4 or 8).  Up to JR = 16: ONE LANE PER
-// FREQUENCY, a wavefront takes 64 consecutive frequencies of one series and needs no exchange between lanes; a lane holds
-// the two columns of F (2 JR registers) and the 3 + 2 QR sums.  At JR = 32 the two columns alone are 128 registers and,
-// with the constants of the sine and cosine, do not fit 256 beside the sums: there a frequency takes TWO neighbouring
-// lanes, one column each (32 frequencies per wavefront), the cosine lane keeps <z_c, .>, the sine lane <z_s, .>, and the
-// one value a row exchanges is the partner's z for <z_c, z_s> (a DPP move inside the quad).  Both forms make the same
-// statements per value, so T does not depend on which one ran.
-// Everything else about a row is the same for all 64 lanes and comes staged through LDS, R = 16 rows a block (8 in the
-// two-lane form), by trial::sweep_rows (c2_trial_sweep.hpp); the row body below is this kernel's own.  Lanes with f >= F
-// carry w = 0 and store nothing.  Every element of T is written by exactly one lane: no atomics, two calls give identical
-// bits.  Blocks: B * ceil(F / frequencies per wavefront) in grid.x, the frequency blocks of a series next to each other.
+// The kernel is trial::k_trial_sweep<trial::Sinusoid, JR, QR> (c2_trial_sweep.hpp), the column source trial::Sinusoid
+// (c2_trial_columns.hpp): two columns, so a frequency takes two neighbouring lanes at J > 16.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
-#include "c2_common.hpp"
-#include "c2_loglik_helpers.hpp"
 #include "../../include/celerite2_amd_periodogram.h"
-#include "c2_launch.hpp"
 #include "c2_trial_columns.hpp"
 #include "c2_trial_sweep.hpp"
 
-namespace c2 {
-namespace pgram {
-
-constexpr int freqs_per_wave(int JR) { return JR >= 32 ? kWave / 2 : kWave; }
-
-template <int JR, int QR>
-__global__ __launch_bounds__(kWave) void k_sinusoids(int64_t N, int J, int Q0, int64_t F, int64_t FB,
-                                                     const double *__restrict__ t, int64_t t_bs, const double *__restrict__ c,
-                                                     int64_t c_bs, const double *__restrict__ U, const double *__restrict__ W,
-                                                     const double *__restrict__ d, const double *__restrict__ Z0,
-                                                     const double *__restrict__ freq, int64_t f_bs, double t_ref,
-                                                     double *__restrict__ T) {
-  constexpr bool SPLIT = freqs_per_wave(JR) < kWave;        // a lane holds one column (cos: even lane, sin: odd), not both
-  constexpr int NC = SPLIT ? 1 : 2;
-  constexpr int R = SPLIT ? 8 : 16;                         // rows per staged block
-  const int lane = threadIdx.x;
-  const int64_t b = blockIdx.x / FB, f = (blockIdx.x % FB) * freqs_per_wave(JR) + (SPLIT ? lane >> 1 : lane);
-  const bool sine = SPLIT && (lane & 1);
-  const double om = f < F ? freq[b * f_bs + f] : 0.0;
-
-  // column 0: the cosine's (SPLIT: this lane's own), column 1: the sine's
-  double Fst[NC][JR], T0[NC][QR], Tsq[NC], z[NC], Tcs = 0.0;
-#pragma unroll
-  for (int a = 0; a < NC; ++a) {
-#pragma unroll
-    for (int i = 0; i < JR; ++i) Fst[a][i] = 0.0;
-#pragma unroll
-    for (int k = 0; k < QR; ++k) T0[a][k] = 0.0;
-    Tsq[a] = z[a] = 0.0;
-  }
-
-  // one row: sx = (t_n, 1 / d_n) and the staged LDS rows p_n, w_{n-1}, u_n, Z0[n]
-  auto row = [&](const double *sx, const double *sp, const double *sw, const double *su, const double *sz) {
-    const double x = phase(om, sx[0], t_ref), rd = sx[1];
-    double rhs[2];
-    sincos_cw(x, rhs[1], rhs[0]);
-    if (SPLIT) rhs[0] = sine ? rhs[1] : rhs[0];
-    double acc[NC][4];
-#pragma unroll
-    for (int a = 0; a < NC; ++a) acc[a][0] = acc[a][1] = acc[a][2] = acc[a][3] = 0.0;
-#pragma unroll
-    for (int i = 0; i < JR; ++i) {
-      const double p = sp[i], w = sw[i], u = su[i];
-#pragma unroll
-      for (int a = 0; a < NC; ++a) {
-        const double fa = p * fma(w, z[a], Fst[a][i]);   // :140, :143
-        Fst[a][i] = fa;
-        acc[a][i & 3] = fma(fa, u, acc[a][i & 3]);
-      }
-    }
-    double zd[NC];
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-      z[a] = rhs[a] - ((acc[a][0] + acc[a][1]) + (acc[a][2] + acc[a][3]));   // :144
-      zd[a] = z[a] * rd;
-      Tsq[a] = fma(z[a], zd[a], Tsq[a]);
-    }
-    // <z_c, z_s> as (z_c / d) z_s: the sine's z is the partner lane's when a lane holds one column (kept by the cosine lane)
-    Tcs = fma(zd[0], SPLIT ? dpp_mov<kDppXor1>(z[0]) : z[NC - 1], Tcs);
-#pragma unroll
-    for (int k = 0; k < QR; ++k) {
-      const double z0 = sz[k];
-#pragma unroll
-      for (int a = 0; a < NC; ++a) T0[a][k] = fma(zd[a], z0, T0[a][k]);
-    }
-  };
-  trial::sweep_rows<JR, QR, R>(N, J, Q0, b, t, t_bs, c, c_bs, U, W, d, Z0, row);
-
-  if (f < F) {
-    double *Tb = T + (b * F + f) * (3 + 2 * Q0);
-    if (!sine) { Tb[0] = Tsq[0]; Tb[1] = Tcs; }
-    if (!SPLIT || sine) Tb[2] = Tsq[NC - 1];
-#pragma unroll
-    for (int k = 0; k < QR; ++k)
-      if (k < Q0) {
-        if (!sine) Tb[3 + k] = T0[0][k];
-        if (!SPLIT || sine) Tb[3 + Q0 + k] = T0[NC - 1][k];
-      }
-  }
-}
-
-}  // namespace pgram
-}  // namespace c2
-
 using namespace c2;
-using namespace c2::pgram;
 
 extern "C" int c2_whitened_sinusoids(int64_t B, int64_t N, int64_t J, int64_t Q0, int64_t F, const double *t, int64_t t_bs,
                                      const double *c, int64_t c_bs, const double *U, const double *W, const double *d,
                                      const double *Z0, const double *freq, int64_t f_bs, double t_ref, double *T,
                                      c2_stream_t stream) {
-  if (B < 1 || N < 1 || J < 1 || Q0 < 1 || F < 1) return C2_ERR_INVALID;
-  if (J > C2_FAST_WIDTH || Q0 > trial::kMaxQ0) return C2_ERR_UNSUPPORTED;
-  if (!t || !c || !U || !W || !d || !Z0 || !freq || !T) return C2_ERR_INVALID;
-  if (t_bs < 0 || c_bs < 0 || f_bs < 0) return C2_ERR_INVALID;
-  const int64_t fpw = freqs_per_wave(padded(J)), FB = (F + fpw - 1) / fpw;
-  if (FB > 0x7fffffffLL || B > 0x7fffffffLL / FB) return C2_ERR_UNSUPPORTED;   // 2^31 blocks or more
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)(B * FB));
-  dispatch_padded(J, [&](auto jr) {
-    dispatch_columns(Q0, [&](auto qr) {
-      hipLaunchKernelGGL((k_sinusoids<decltype(jr)::value, decltype(qr)::value>), grid, dim3(kWave), 0, s, N, (int)J, (int)Q0,
-                         F, FB, t, t_bs, c, c_bs, U, W, d, Z0, freq, f_bs, t_ref, T);
-    });
-  });
-  return launch_ok();
+  return trial::launch_sweep<trial::Sinusoid>(B, N, J, Q0, F, t, t_bs, c, c_bs, U, W, d, Z0, freq, f_bs, T, {t_ref}, stream);
 }

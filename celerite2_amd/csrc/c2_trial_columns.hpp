@@ -1,8 +1,13 @@
-// c2_trial_columns.hpp -- THE COLUMNS OF A TRIAL as a lane forms them in registers: the periodogram's phase, the transit
-// template and the Keplerian pair.  One statement of each rule, shared by the sweeps that whiten the columns
-// (c2_periodogram.hip, c2_transit.hip, c2_kepler.hip) and by the projection of null draws onto them (c2_trial_project.hip),
-// so that both see the same column values bit for bit.  The public headers (celerite2_amd_periodogram.h, _transit.h,
-// _kepler.h) state the rules line by line; tests/periodogram_ref.py, tests/transit_ref.py and tests/kepler_ref.py restate them.
+// c2_trial_columns.hpp -- THE COLUMNS OF A TRIAL as a lane forms them in registers, one COLUMN SOURCE per kind of trial
+// (namespace trial, at the end): the periodogram's phase, the transit template, the Keplerian pair and the tabulated shape.
+// One statement of each rule, shared by the sweep that whitens the columns (k_trial_sweep, c2_trial_sweep.hpp) and by the
+// projection of null draws onto them (k_project, c2_trial_project.hip), so that both see the same column values bit for
+// bit.  The public headers (celerite2_amd_periodogram.h, _transit.h, _kepler.h, _shapes.h) state the rules line by line;
+// tests/periodogram_ref.py, tests/transit_ref.py, tests/kepler_ref.py and tests/shapes_ref.py restate them.
+//
+// A source states NC (its columns, 1 or 2), WORDS (doubles per trial) and Params (what a launch hands every lane beside the
+// trials); it is built from (this lane's trial -- trial 0 when the lane is beyond K --, live, the series, Params), a lane
+// that is not live taking the INERT trial (all zeros) without reading; columns(t, a[NC]) gives the column values at a time.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,24 +27,23 @@ __device__ __forceinline__ double phase(double w, double t, double t_ref) {
 
 }  // namespace pgram
 
-namespace transit {
-
-// b_n of the header's rule from the lane's constants: invP = fl(1 / P), or 0 for a single event (then q = 0 and phi = x);
-// hw = 0.5 w (exact).  The ramp's division is met only by a wavefront with a lane on an ingress or egress at that row.
-__device__ __forceinline__ double template_value(double t, double P, double invP, double t0, double hw, double tau) {
+// THE FOLD of a repeating event, shared by the transit template and the tabulated shape: what a lane keeps of (P, t0, w) --
+// invP = fl(1 / P), or 0 for a single event (then q = 0 and phi = x); hw = 0.5 w (exact) -- and the time from the nearest
+// event's centre, every line rounded once and none contracted into an fma.
+struct Fold {
+  double P, invP, t0, hw;
+  __device__ __forceinline__ Fold(const double *tr, bool live) : P(live ? tr[0] : 0.0), t0(live ? tr[1] : 0.0), hw(live ? 0.5 * tr[2] : 0.0) {
+    invP = P != 0.0 ? 1.0 / P : 0.0;                           // (a correctly rounded division, once per lane)
+  }
+  __device__ __forceinline__ double phi(double t) const {
 #pragma clang fp contract(off)
-  const double x = t - t0;
-  const double q = __builtin_rint(x * invP);
-  const double qp = q * P;
-  const double phi = x - qp;
-  const double u = hw - __builtin_fabs(phi);
-  double b = u >= tau ? 1.0 : 0.0;
-  const bool ramp = u >= 0.0 && u < tau;
-  if (__builtin_amdgcn_ballot_w64(ramp) != 0) b = ramp ? u / tau : b;   // (wave-uniform: the division is skipped, not masked)
-  return b;
-}
-
-}  // namespace transit
+    const double x = t - t0;
+    const double q = __builtin_rint(x * invP);
+    const double qp = q * P;
+    const double phi = x - qp;
+    return phi;
+  }
+};
 
 namespace kepler {
 
@@ -114,4 +118,110 @@ __device__ __forceinline__ void columns(const Trial &tr, double t, double &cnu, 
 }
 
 }  // namespace kepler
+
+namespace trial {
+
+struct NoParams {};
+
+// What a kind's own arguments add to the three stages of an entry point's checks, made in this order by every launcher:
+// sizes (C2_ERR_INVALID), limits (C2_ERR_UNSUPPORTED), pointers and strides (C2_ERR_INVALID).
+struct KindChecks {
+  bool bad_size = false, too_large = false, bad_arg = false;
+};
+
+// (w): cos x, sin x at x = fl(w * fl(t - t_ref))
+struct Sinusoid {
+  static constexpr int NC = 2, WORDS = 1;
+  struct Params { double t_ref; };
+  double om, t_ref;
+  __device__ __forceinline__ Sinusoid(const double *tr, bool live, int64_t, const Params &p) : om(live ? tr[0] : 0.0), t_ref(p.t_ref) {}
+  __device__ __forceinline__ void columns(double t, double (&a)[2]) const { sincos_cw(pgram::phase(om, t, t_ref), a[1], a[0]); }
+};
+
+// (P, t0, w, tau): b_n of celerite2_amd_transit.h.  The ramp's division is met only by a wavefront with a lane on an
+// ingress or egress at that row.
+struct Transit {
+  static constexpr int NC = 1, WORDS = 4;
+  typedef NoParams Params;
+  Fold fold;
+  double tau;
+  __device__ __forceinline__ Transit(const double *tr, bool live, int64_t, const Params &) : fold(tr, live), tau(live ? tr[3] : 0.0) {}
+  // b_n from the folded time.  (By value: as a member reading hw and tau through `this`, the compiler ran the division on
+  // every row instead of branching round it.)
+  static __device__ __forceinline__ double edge(double phi, double hw, double tau) {
+#pragma clang fp contract(off)
+    const double u = hw - __builtin_fabs(phi);
+    double b = u >= tau ? 1.0 : 0.0;
+    const bool ramp = u >= 0.0 && u < tau;
+    if (__builtin_amdgcn_ballot_w64(ramp) != 0) b = ramp ? u / tau : b;   // (wave-uniform: the division is skipped, not masked)
+    return b;
+  }
+  __device__ __forceinline__ void columns(double t, double (&a)[1]) const { a[0] = edge(fold.phi(t), fold.hw, tau); }
+};
+
+// (w, e, tp): cos nu, sin nu of the orbit
+struct Keplerian {
+  static constexpr int NC = 2, WORDS = 3;
+  typedef NoParams Params;
+  kepler::Trial tr;
+  __device__ __forceinline__ Keplerian(const double *p, bool live, int64_t, const Params &)
+      : tr(kepler::make_trial(live ? p[0] : 0.0, live ? p[1] : 0.0, live ? p[2] : 0.0)) {}
+  __device__ __forceinline__ void columns(double t, double (&a)[2]) const { kepler::columns(tr, t, a[0], a[1]); }
+};
+
+// (P, t0, w, s) and a bank of NS profiles on S nodes ((NS, S) doubles a series, `stride` apart, 0 when shared): b_n of
+// celerite2_amd_shapes.h, the profile interpolated linearly between its two nodes around the sample.
+// THE BANK IS READ THROUGH THE VECTOR CACHE, not staged in LDS: a bank at the cap (1024 doubles, 8 KB; 16 KB as (value,
+// difference) pairs) next to the 13.5 KB of staged rows of a one-wave block would take the blocks per compute unit from 11
+// to 5 at J = 32 (DESIGN.md 5n has the table); 8 KB shared by every wavefront of a series stays in the cache.  The two nodes
+// are adjacent doubles.  The gather is skipped, wave-uniformly, at a row where no lane is in an event; what a lane computes
+// does not depend on which lanes share its wavefront.
+struct Shape {
+  static constexpr int NC = 1, WORDS = 4;
+  struct Params { const double *bank; int64_t stride; int NS, S; };
+  Fold fold;
+  double ginv, top;     // ginv = fl(fl(S - 1) / w); top = fl(S - 1)
+  const double *node;   // shape[is]: the clamped index, never a trusted one
+  int last;             // S - 2: the last interval
+  __device__ __forceinline__ Shape(const double *tr, bool live, int64_t b, const Params &p) : fold(tr, live) {
+#pragma clang fp contract(off)
+    const double w = live ? tr[2] : 0.0, s = live ? tr[3] : 0.0;
+    top = (double)(p.S - 1);
+    ginv = top / w;                                                // (correctly rounded; w == 0: inf, w NaN: NaN -- g then takes 0)
+    const int is = (s >= 0.0 && s < (double)p.NS) ? (int)s : 0;    // (NaN fails both comparisons)
+    node = p.bank + b * p.stride + (int64_t)is * p.S;
+    last = p.S - 2;
+  }
+  // Whatever the trial holds, the two reads are node[i], node[i + 1] with 0 <= i <= S - 2.
+  __device__ __forceinline__ void columns(double t, double (&a)[1]) const {
+#pragma clang fp contract(off)
+    const double phi = fold.phi(t);
+    const double u = fold.hw - __builtin_fabs(phi);
+    const double v = phi + fold.hw;
+    double g = v * ginv;
+    g = g > 0.0 ? g : 0.0;                                     // (a NaN g takes 0)
+    g = g < top ? g : top;
+    const int fl = (int)__builtin_floor(g);
+    const int i = fl < last ? fl : last;
+    const double fr = g - (double)i;                           // (exact)
+    const bool in = !(u < 0.0);
+    double lo = 0.0, hi = 0.0;
+    if (__builtin_amdgcn_ballot_w64(in) != 0) {                // (wave-uniform: the loads are skipped, not masked)
+      lo = node[i];
+      hi = node[i + 1];
+    }
+    const double dlt = hi - lo;
+    const double fd = fr * dlt;
+    const double b = lo + fd;
+    a[0] = in ? b : 0.0;
+  }
+};
+
+constexpr int kMaxNodes = 1024;   // NS * S of a bank (C2_SHAPE_MAX_NODES)
+
+inline KindChecks bank_checks(const double *shapes, int64_t sh_bs, int64_t NS, int64_t S) {
+  return {NS < 1 || S < 2, NS > kMaxNodes || S > kMaxNodes || NS * S > kMaxNodes, !shapes || (sh_bs != 0 && sh_bs != NS * S)};
+}
+
+}  // namespace trial
 }  // namespace c2

@@ -1,14 +1,15 @@
 // c2_trial_project.hip -- THE PROJECTIONS OF MANY VECTORS ON THE COLUMNS OF A TRIAL GRID (c2_trial_projections,
-// include/celerite2_amd_trials.h): for every series b, trial k, column c of that trial and vector r,
+// include/celerite2_amd_trials.h; c2_shape_projections, include/celerite2_amd_shapes.h): for every series b, trial k,
+// column c of that trial and vector r,
 //   P[b, k, c, r] = sum_n col_c(trial k; t[b, n]) * alpha[b, n, r]
-// with the columns of the three searches -- (cos, sin) of the periodogram's phase, the transit template, (cos nu, sin nu) of
-// a Keplerian orbit -- formed in registers by the very functions the whitening sweeps use (c2_trial_columns.hpp), so the
-// column values are theirs bit for bit.  With alpha = (K + D)^-1 (y_r - mean) this is gty_r of a search for R series y_r at
+// with the columns of the four searches -- (cos, sin) of the periodogram's phase, the transit template, (cos nu, sin nu) of
+// a Keplerian orbit, the tabulated shape -- formed in registers by the very column sources the whitening sweep uses
+// (c2_trial_columns.hpp), so the column values are its bit for bit.  With alpha = (K + D)^-1 (y_r - mean) this is gty_r of a search for R series y_r at
 // once: what the Monte-Carlo false-alarm probability reads (celerite2_amd/significance.py).  It is a (K x N) . (N x R)
 // matrix product whose left operand is never in memory and has no recurrence: the cost of forming a column -- for the
 // Keplerian, one solve of Kepler's equation -- is paid once for all R vectors.  No counterpart in the reference.
 //
-// k_project<KIND, NQ>: ONE WAVEFRONT takes 16 trials and RB = 16 NQ vectors and walks all N rows four at a time on the
+// k_project<Column, NQ>: ONE WAVEFRONT takes 16 trials and RB = 16 NQ vectors and walks all N rows four at a time on the
 // matrix cores, v_mfma_f64_16x16x4_f64 (lane maps: tools/ubench/mfma64.hip):
 //   A operand: lane l forms the column value(s) of trial k0 + (l & 15) at row n0 + (l >> 4) -- one value per lane, in place;
 //   B operand of vector tile q: alpha[b, n0 + (l >> 4), r0 + 16 q + (l & 15)] (16 lanes read 128 contiguous bytes);
@@ -26,6 +27,7 @@
 
 #include "c2_common.hpp"
 #include "c2_loglik_helpers.hpp"
+#include "../../include/celerite2_amd_shapes.h"
 #include "../../include/celerite2_amd_trials.h"
 #include "c2_launch.hpp"
 #include "c2_trial_columns.hpp"
@@ -37,54 +39,18 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ d4 mfma(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 
-constexpr int columns_of(int kind) { return kind == C2_TRIAL_TRANSIT ? 1 : 2; }
-constexpr int words_of(int kind) { return kind == C2_TRIAL_SINUSOID ? 1 : kind == C2_TRIAL_TRANSIT ? 4 : 3; }
-// vector tiles of 16 per wavefront (RB / 16): the header's C2_TRIAL_*_DRAWS
-constexpr int tiles_of(int kind) {
-  return (kind == C2_TRIAL_SINUSOID ? C2_TRIAL_SINUSOID_DRAWS : kind == C2_TRIAL_TRANSIT ? C2_TRIAL_TRANSIT_DRAWS
-                                                                                       : C2_TRIAL_KEPLERIAN_DRAWS) / 16;
-}
-
-// what a lane keeps of its trial, and its column value(s) at a time
-template <int KIND>
-struct Lane;
-
-template <>
-struct Lane<C2_TRIAL_SINUSOID> {
-  double om, t_ref;
-  __device__ __forceinline__ Lane(const double *tr, bool live, double t_ref_) : om(live ? tr[0] : 0.0), t_ref(t_ref_) {}
-  __device__ __forceinline__ void columns(double t, double (&a)[2]) const { sincos_cw(pgram::phase(om, t, t_ref), a[1], a[0]); }
-};
-
-template <>
-struct Lane<C2_TRIAL_TRANSIT> {
-  double P, invP, t0, hw, tau;
-  __device__ __forceinline__ Lane(const double *tr, bool live, double)
-      : P(live ? tr[0] : 0.0), t0(live ? tr[1] : 0.0), hw(live ? 0.5 * tr[2] : 0.0), tau(live ? tr[3] : 0.0) {
-    invP = P != 0.0 ? 1.0 / P : 0.0;                         // (a correctly rounded division, once per lane)
-  }
-  __device__ __forceinline__ void columns(double t, double (&a)[1]) const { a[0] = transit::template_value(t, P, invP, t0, hw, tau); }
-};
-
-template <>
-struct Lane<C2_TRIAL_KEPLERIAN> {
-  kepler::Trial tr;
-  __device__ __forceinline__ Lane(const double *p, bool live, double)
-      : tr(kepler::make_trial(live ? p[0] : 0.0, live ? p[1] : 0.0, live ? p[2] : 0.0)) {}
-  __device__ __forceinline__ void columns(double t, double (&a)[2]) const { kepler::columns(tr, t, a[0], a[1]); }
-};
-
-template <int KIND, int NQ>
+template <class Column, int NQ>
 __global__ __launch_bounds__(kWave) void k_project(int64_t N, int64_t K, int64_t R, int64_t KB, int64_t RBn,
                                                    const double *__restrict__ t, int64_t t_bs,
-                                                   const double *__restrict__ trials, int64_t tr_bs, double t_ref,
-                                                   const double *__restrict__ alpha, double *__restrict__ P) {
-  constexpr int C = columns_of(KIND), WORDS = words_of(KIND);
+                                                   const double *__restrict__ trials, int64_t tr_bs,
+                                                   const double *__restrict__ alpha, double *__restrict__ P,
+                                                   const typename Column::Params prm) {
+  constexpr int C = Column::NC;
   const int l = threadIdx.x, lo = l & 15, hi = l >> 4;
   const int64_t kb = blockIdx.x % KB, rb = (blockIdx.x / KB) % RBn, b = blockIdx.x / (KB * RBn);
   const int64_t k0 = kb * 16, r0 = rb * (16 * NQ);
   const bool live = k0 + lo < K;
-  const Lane<KIND> lane(trials + b * tr_bs + (live ? k0 + lo : 0) * WORDS, live, t_ref);
+  const Column lane(trials + b * tr_bs + (live ? k0 + lo : 0) * Column::WORDS, live, b, prm);
 
   const double *tb = t + b * t_bs, *ab = alpha + b * N * R;
   // this lane's vectors: one per tile (clamped for the load, zeroed after it)
@@ -147,14 +113,19 @@ __global__ __launch_bounds__(kWave) void k_project(int64_t N, int64_t K, int64_t
   }
 }
 
-template <int KIND>
+// NQ: vector tiles of 16 per wavefront (RB / 16), from the headers' C2_TRIAL_*_DRAWS and C2_SHAPE_DRAWS
+template <class Column, int DRAWS>
 int launch(int64_t B, int64_t N, int64_t K, int64_t R, const double *t, int64_t t_bs, const double *trials, int64_t tr_bs,
-           double t_ref, const double *alpha, double *P, hipStream_t s) {
-  constexpr int NQ = tiles_of(KIND);
+           const double *alpha, double *P, const typename Column::Params &prm, c2_stream_t stream, const trial::KindChecks &kind = {}) {
+  constexpr int NQ = DRAWS / 16;
+  static_assert(DRAWS % 16 == 0 && NQ >= 1, "the draws of a wavefront are a multiple of 16");
+  if (B < 1 || N < 1 || K < 1 || R < 1 || kind.bad_size) return C2_ERR_INVALID;
+  if (kind.too_large) return C2_ERR_UNSUPPORTED;
+  if (!t || !trials || !alpha || !P || t_bs < 0 || tr_bs < 0 || kind.bad_arg) return C2_ERR_INVALID;
   const int64_t KB = (K + 15) / 16, RBn = (R + 16 * NQ - 1) / (16 * NQ);
   if (KB > 0x7fffffffLL || RBn > 0x7fffffffLL / KB || B > 0x7fffffffLL / (KB * RBn)) return C2_ERR_UNSUPPORTED;   // 2^31 blocks or more
-  hipLaunchKernelGGL((k_project<KIND, NQ>), dim3((unsigned)(B * KB * RBn)), dim3(kWave), 0, s, N, K, R, KB, RBn, t, t_bs,
-                     trials, tr_bs, t_ref, alpha, P);
+  hipLaunchKernelGGL((k_project<Column, NQ>), dim3((unsigned)(B * KB * RBn)), dim3(kWave), 0, (hipStream_t)stream, N, K, R, KB, RBn,
+                     t, t_bs, trials, tr_bs, alpha, P, prm);
   return launch_ok();
 }
 
@@ -166,12 +137,18 @@ using namespace c2;
 extern "C" int c2_trial_projections(int kind, int64_t B, int64_t N, int64_t K, int64_t R, const double *t, int64_t t_bs,
                                     const double *trials, int64_t tr_bs, double t_ref, const double *alpha, double *P,
                                     c2_stream_t stream) {
-  if (kind != C2_TRIAL_SINUSOID && kind != C2_TRIAL_TRANSIT && kind != C2_TRIAL_KEPLERIAN) return C2_ERR_INVALID;
-  if (B < 1 || N < 1 || K < 1 || R < 1) return C2_ERR_INVALID;
-  if (!t || !trials || !alpha || !P) return C2_ERR_INVALID;
-  if (t_bs < 0 || tr_bs < 0) return C2_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  if (kind == C2_TRIAL_SINUSOID) return project::launch<C2_TRIAL_SINUSOID>(B, N, K, R, t, t_bs, trials, tr_bs, t_ref, alpha, P, s);
-  if (kind == C2_TRIAL_TRANSIT) return project::launch<C2_TRIAL_TRANSIT>(B, N, K, R, t, t_bs, trials, tr_bs, t_ref, alpha, P, s);
-  return project::launch<C2_TRIAL_KEPLERIAN>(B, N, K, R, t, t_bs, trials, tr_bs, t_ref, alpha, P, s);
+  if (kind == C2_TRIAL_SINUSOID)
+    return project::launch<trial::Sinusoid, C2_TRIAL_SINUSOID_DRAWS>(B, N, K, R, t, t_bs, trials, tr_bs, alpha, P, {t_ref}, stream);
+  if (kind == C2_TRIAL_TRANSIT)
+    return project::launch<trial::Transit, C2_TRIAL_TRANSIT_DRAWS>(B, N, K, R, t, t_bs, trials, tr_bs, alpha, P, {}, stream);
+  if (kind == C2_TRIAL_KEPLERIAN)
+    return project::launch<trial::Keplerian, C2_TRIAL_KEPLERIAN_DRAWS>(B, N, K, R, t, t_bs, trials, tr_bs, alpha, P, {}, stream);
+  return C2_ERR_INVALID;
+}
+
+extern "C" int c2_shape_projections(int64_t B, int64_t N, int64_t K, int64_t R, const double *t, int64_t t_bs,
+                                    const double *trials, int64_t tr_bs, const double *alpha, double *P, const double *shapes,
+                                    int64_t sh_bs, int64_t NS, int64_t S, c2_stream_t stream) {
+  return project::launch<trial::Shape, C2_SHAPE_DRAWS>(B, N, K, R, t, t_bs, trials, tr_bs, alpha, P, {shapes, sh_bs, (int)NS, (int)S},
+                                                       stream, trial::bank_checks(shapes, sh_bs, NS, S));
 }

@@ -24,6 +24,65 @@ class LinAlgError(Exception):
     pass
 
 
+def _significance(self, kind, y, trials, shapes, draws, A, normalization, t_ref, dips_only, generator, normals, max_trials,
+                  max_draws):
+    """search_significance and shape_search_significance (`shapes`: its bank, None for the kinds named): what differs
+    between the searches comes from significance.SEARCHES."""
+    from . import _trial_fit, periodogram as pg, significance as sg
+
+    self._need()
+    self._check_vector(y)
+    (B, N), dev = self._diag.shape, self._diag.device
+    if shapes is None and kind not in sg.KINDS:
+        raise ValueError("kind must be one of %s" % (sg.KINDS,))
+    if normalization not in pg.NORMALIZATIONS:
+        raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
+    search, NS = sg.SEARCHES[kind], None
+    if shapes is None:
+        trials = sg.check_trials(kind, trials, B)
+    else:
+        trials, shapes, NS = self._shape_args(trials, shapes)
+    if normals is not None:
+        if not torch.is_tensor(normals) or normals.dim() != 3 or tuple(normals.shape[:2]) != (B, N):
+            raise ValueError("Invalid shape: normals (must be (B, N, draws) = (%d, %d, draws))" % (B, N))
+        draws = normals.shape[-1]
+    draws = int(draws)
+    if draws < 1:
+        raise ValueError("draws must be at least 1")
+    per_series = trials.dim() == (2 if kind == "periodogram" else 3)
+    K = trials.shape[1 if per_series else 0]
+    kstep = K if max_trials is None else int(max_trials)
+    rstep = draws if max_draws is None else int(max_draws)
+    if kstep < 1 or rstep < 1:
+        raise ValueError("max_trials and max_draws must be at least 1")
+    ok = self._flag == 0
+    Z0 = self._whitened_columns(y, A)
+    S0 = _trial_fit.null_products(Z0, self._d)
+    T = search.sweep(self._t, self._c, self._U, self._W, self._d, Z0, trials, t_ref=t_ref, shapes=shapes)
+    statistic, = self._nan_failed(sg.observed_statistic(kind, S0, T, N, normalization, trials, NS, dips_only, ok))
+    if normals is None:
+        normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
+    rsd = torch.rsqrt(self._d)[..., None]
+    ZA = Z0[..., :-1].transpose(1, 2)                                        # (B, P0, N)
+    maxima = []
+    for r0 in range(0, draws, rstep):
+        n = normals[..., r0:r0 + rstep]
+        scaled = (n * rsd).contiguous()                                      # D^-1/2 n_r
+        s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
+        alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
+        best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
+        for k0 in range(0, K, kstep):
+            tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
+            P = search.project(self._t, alpha, tk, t_ref=t_ref, shapes=shapes)
+            stat = sg._null_statistics(kind, S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization, tk, NS, dips_only, ok)
+            best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
+        maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
+    null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
+    # (a draw's maximum comes through the projection, the statistic through the sweep: a tie of the two to the standing
+    # criterion's relative part counts as at or above -- the larger probability)
+    return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
+
+
 class GaussianProcess:
     def __init__(self, kernel, t=None, *, mean=0.0, **kwargs):
         self.kernel = kernel
@@ -344,17 +403,16 @@ class GaussianProcess:
         compute(..., quiet=True): a frequency at which the sinusoid is not identifiable (w = 0 beside a constant column),
         a series whose factorisation failed or whose A is rank-deficient, and every frequency when N < P0 + 3 hold NaN.
         Times with a large offset keep their phase accuracy with `t_ref` at the offset.  J <= 32."""
-        from . import periodogram as pg
+        from . import periodogram as pg, significance as sg
 
         self._need()
         self._check_vector(y)
         B, N = self._diag.shape
         if normalization not in pg.NORMALIZATIONS:
             raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
-        if not torch.is_tensor(freq) or freq.dim() not in (1, 2) or (freq.dim() == 2 and freq.shape[0] != B) or freq.shape[-1] < 1:
-            raise ValueError("Invalid shape: freq (must be (F,) or (B, F) with B = %d, F >= 1)" % B)
+        freq = sg.check_trials("periodogram", freq, B, "freq", "F")
         Z0 = self._whitened_columns(y, A)
-        T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq.contiguous(), t_ref=t_ref)
+        T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq, t_ref=t_ref)
         fit = self._nan_failed_fit(pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0))
         return fit if return_fit else fit.power
 
@@ -373,15 +431,12 @@ class GaussianProcess:
         w > 0, 0 <= tau <= w / 2, P >= 0, w <= P (P > 0), a series whose factorisation failed or whose A is rank-deficient, and
         every trial when N < P0 + 2 hold NaN.  A TermConvolution kernel is accepted: only the factored matrix is used.
         J <= 32."""
-        from . import _trial_fit, transit as tr
+        from . import _trial_fit, significance as sg, transit as tr
 
         self._need()
         self._check_vector(y)
         B, N = self._diag.shape
-        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
-                or trials.shape[-1] != 4 or trials.shape[-2] < 1:
-            raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4) with B = %d, K >= 1)" % B)
-        trials = trials.contiguous()
+        trials = sg.check_trials("transit", trials, B)
         Z0 = self._whitened_columns(y, A)
         T = ops.whitened_transits(self._t, self._c, self._U, self._W, self._d, Z0, trials)
         fit = self._nan_failed_fit(tr.finish(_trial_fit.null_products(Z0, self._d), T, N, ok=self._flag == 0, trials=trials))
@@ -403,17 +458,14 @@ class GaussianProcess:
         w > 0, 0 <= e <= 0.99, tp finite, one at which the two columns are not identifiable beside A, a series whose
         factorisation failed or whose A is rank-deficient, and every trial when N < P0 + 3 hold NaN.  Times with a large
         offset keep their accuracy with tp at the offset.  J <= 32."""
-        from . import _trial_fit, kepler as kp, periodogram as pg
+        from . import _trial_fit, kepler as kp, periodogram as pg, significance as sg
 
         self._need()
         self._check_vector(y)
         B, N = self._diag.shape
         if normalization not in pg.NORMALIZATIONS:
             raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
-        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
-                or trials.shape[-1] != 3 or trials.shape[-2] < 1:
-            raise ValueError("Invalid shape: trials (must be (K, 3) or (B, K, 3) with B = %d, K >= 1)" % B)
-        trials = trials.contiguous()
+        trials = sg.check_trials("keplerian", trials, B)
         Z0 = self._whitened_columns(y, A)
         T = ops.whitened_keplerians(self._t, self._c, self._U, self._W, self._d, Z0, trials)
         fit = self._nan_failed_fit(kp.finish(_trial_fit.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0,
@@ -480,85 +532,19 @@ class GaussianProcess:
         (B, K, draws) arrays; the result does not depend on `max_trials`, to the bit, and on `max_draws` to rounding (the
         solve may take another kernel at another column count).  `A`, `t_ref`: as for the searches.  Not differentiable
         and never raising under compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32."""
-        from . import _trial_fit, kepler as kp, periodogram as pg, significance as sg, transit as tr
-
-        self._need()
-        self._check_vector(y)
-        (B, N), dev = self._diag.shape, self._diag.device
-        if kind not in sg.KINDS:
-            raise ValueError("kind must be one of %s" % (sg.KINDS,))
-        if normalization not in pg.NORMALIZATIONS:
-            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
-        words = {"periodogram": None, "transit": 4, "keplerian": 3}[kind]
-        lead = 1 if words is None else 2
-        if not torch.is_tensor(trials) or trials.dim() not in (lead, lead + 1) or (trials.dim() == lead + 1 and trials.shape[0] != B) \
-                or (words is not None and trials.shape[-1] != words) or trials.shape[-1 if words is None else -2] < 1:
-            raise ValueError("Invalid shape: trials (must be %s with B = %d, K >= 1)"
-                             % ("(F,) or (B, F)" if words is None else "(K, %d) or (B, K, %d)" % (words, words), B))
-        if normals is not None:
-            if not torch.is_tensor(normals) or normals.dim() != 3 or tuple(normals.shape[:2]) != (B, N):
-                raise ValueError("Invalid shape: normals (must be (B, N, draws) = (%d, %d, draws))" % (B, N))
-            draws = normals.shape[-1]
-        draws = int(draws)
-        if draws < 1:
-            raise ValueError("draws must be at least 1")
-        trials = trials.contiguous()
-        K = trials.shape[-1] if words is None else trials.shape[-2]
-        kstep = K if max_trials is None else int(max_trials)
-        rstep = draws if max_draws is None else int(max_draws)
-        if kstep < 1 or rstep < 1:
-            raise ValueError("max_trials and max_draws must be at least 1")
-        ok = self._flag == 0
-        Z0 = self._whitened_columns(y, A)
-        S0 = _trial_fit.null_products(Z0, self._d)
-        sweep_args = (self._t, self._c, self._U, self._W, self._d, Z0, trials)
-        if kind == "periodogram":
-            T = ops.whitened_sinusoids(*sweep_args, t_ref=t_ref)
-            statistic = pg.finish(S0, T, N, normalization, ok=ok).power
-        elif kind == "keplerian":
-            T = ops.whitened_keplerians(*sweep_args)
-            statistic = kp.finish(S0, T, N, normalization, ok=ok, trials=trials).power
-        else:
-            T = ops.whitened_transits(*sweep_args)
-            fit = tr.finish(S0, T, N, ok=ok, trials=trials)
-            statistic = sg._normalize(fit.delta_chi2, fit.chi2_null[:, None], normalization)
-            if dips_only:
-                statistic = torch.where(fit.depth > 0, torch.zeros_like(statistic), statistic)
-        statistic, = self._nan_failed(statistic)
-        if normals is None:
-            normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
-        rsd = torch.rsqrt(self._d)[..., None]
-        ZA = Z0[..., :-1].transpose(1, 2)                                        # (B, P0, N)
-        per_series = trials.dim() == lead + 1
-        maxima = []
-        for r0 in range(0, draws, rstep):
-            n = normals[..., r0:r0 + rstep]
-            scaled = (n * rsd).contiguous()                                      # D^-1/2 n_r
-            s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
-            alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
-            best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
-            for k0 in range(0, K, kstep):
-                tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
-                P = ops.trial_projections(kind, self._t, alpha, tk, t_ref=t_ref)
-                stat = sg.null_statistics(kind, S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization=normalization,
-                                          trials=tk, dips_only=dips_only, ok=ok)
-                best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
-            maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
-        null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
-        # (a draw's maximum comes through the projection, the statistic through the sweep: a tie of the two to the standing
-        # criterion's relative part counts as at or above -- the larger probability)
-        return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
+        return _significance(self, kind, y, trials, None, draws, A, normalization, t_ref, dips_only, generator, normals, max_trials,
+                                  max_draws)
 
     # -- the tabulated-shape search under the factored covariance (ops.whitened_shapes; no counterpart in the reference) --
     def _shape_args(self, trials, shapes):
         """(trials, shapes, NS) contiguous, after the shape checks of shape_search and shape_search_significance."""
+        from . import significance as sg
+
         B = self._diag.shape[0]
-        if not torch.is_tensor(trials) or trials.dim() not in (2, 3) or (trials.dim() == 3 and trials.shape[0] != B) \
-                or trials.shape[-1] != 4 or trials.shape[-2] < 1:
-            raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4) with B = %d, K >= 1)" % B)
+        trials = sg.check_trials("shape", trials, B)
         if not torch.is_tensor(shapes) or shapes.dim() not in (2, 3) or (shapes.dim() == 3 and shapes.shape[0] != B):
             raise ValueError("Invalid shape: shapes (must be (NS, S) or (B, NS, S) with B = %d)" % B)
-        return trials.contiguous(), shapes.contiguous(), shapes.shape[-2]
+        return trials, shapes.contiguous(), shapes.shape[-2]
 
     def shape_search(self, y, trials, shapes, *, A="mean", return_fit=False):
         """Least squares of `y` (B, N) with an event of a TABULATED SHAPE under the factored covariance, (B, K): for each
@@ -599,59 +585,8 @@ class GaussianProcess:
         ops.shape_projections -- no sweep per draw.  `normals`, `generator`, `max_trials` (same bits), `max_draws` (to
         rounding), `A`: as for `search_significance`.  Not differentiable and never raising under
         compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32."""
-        from . import _trial_fit, periodogram as pg, shapes as sh, significance as sg
-
-        self._need()
-        self._check_vector(y)
-        (B, N), dev = self._diag.shape, self._diag.device
-        if normalization not in pg.NORMALIZATIONS:
-            raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
-        trials, shapes, NS = self._shape_args(trials, shapes)
-        if normals is not None:
-            if not torch.is_tensor(normals) or normals.dim() != 3 or tuple(normals.shape[:2]) != (B, N):
-                raise ValueError("Invalid shape: normals (must be (B, N, draws) = (%d, %d, draws))" % (B, N))
-            draws = normals.shape[-1]
-        draws = int(draws)
-        if draws < 1:
-            raise ValueError("draws must be at least 1")
-        K = trials.shape[-2]
-        kstep = K if max_trials is None else int(max_trials)
-        rstep = draws if max_draws is None else int(max_draws)
-        if kstep < 1 or rstep < 1:
-            raise ValueError("max_trials and max_draws must be at least 1")
-        ok = self._flag == 0
-        Z0 = self._whitened_columns(y, A)
-        S0 = _trial_fit.null_products(Z0, self._d)
-        T = ops.whitened_shapes(self._t, self._c, self._U, self._W, self._d, Z0, trials, shapes)
-        fit = sh.finish(S0, T, N, ok=ok, trials=trials, n_shapes=NS)
-        statistic = sg._normalize(fit.delta_chi2, fit.chi2_null[:, None], normalization)
-        if dips_only:
-            statistic = torch.where(fit.amplitude > 0, torch.zeros_like(statistic), statistic)
-        statistic, = self._nan_failed(statistic)
-        if normals is None:
-            normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
-        rsd = torch.rsqrt(self._d)[..., None]
-        ZA = Z0[..., :-1].transpose(1, 2)                                        # (B, P0, N)
-        per_series = trials.dim() == 3
-        nan = torch.full((), math.nan, dtype=torch.float64, device=dev)
-        maxima = []
-        for r0 in range(0, draws, rstep):
-            n = normals[..., r0:r0 + rstep]
-            scaled = (n * rsd).contiguous()                                      # D^-1/2 n_r
-            s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
-            alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
-            best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
-            for k0 in range(0, K, kstep):
-                tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
-                P = ops.shape_projections(self._t, alpha, tk, shapes)
-                stat = sg.null_statistics("transit", S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization=normalization,
-                                          trials=None, dips_only=dips_only, ok=ok)
-                stat = torch.where(sh.in_domain(tk, NS).expand(B, tk.shape[-2])[..., None], stat, nan)
-                best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
-            maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
-        null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
-        # (a tie to the standing criterion's relative part counts as at or above, as in search_significance)
-        return sg.Significance(statistic, sg.false_alarm_probability(statistic, null_maxima, rtol=1e-10), null_maxima)
+        return _significance(self, "shape", y, trials, shapes, draws, A, normalization, 0.0, dips_only, generator, normals, max_trials,
+                                  max_draws)
 
     # -- draws at NEW times in linear time (ops.prior_draw + Matheron's rule; no counterpart in the reference) ----
     def sample_at(self, y, t, *, size=None, include_mean=True, generator=None, normals=None, check_sorted=True):

@@ -8,6 +8,7 @@ contiguous, on one HIP device; t may be (B,N) or shared (N,), c (B,J) or (J,).
 Launches go on torch's current stream.  torch is plumbing here (device memory,
 streams); the arithmetic is in the gfx950 kernels.
 """
+import collections
 import ctypes
 
 import torch
@@ -435,6 +436,92 @@ def whitened_gram(t, c, U, W, d, A, y=None, S=None):
     return S
 
 
+# THE KINDS OF TRIAL: what the sweep (c2_whitened_*) and the projection (c2_trial_projections, c2_shape_projections) of each
+# take.  code: C2_TRIAL_* of celerite2_amd_trials.h (None: the kind has entry points of its own); words: doubles per trial;
+# columns: C; width: T's last axis as (constant, per column of Z0); draws: vectors per wavefront of the projection
+# (C2_TRIAL_*_DRAWS, C2_SHAPE_DRAWS); bank: whether a shape bank goes with the trials.  tests/test_significance.py holds it
+# to the headers.
+_TrialKind = collections.namedtuple("_TrialKind", "code words columns width draws bank")
+_TRIAL_TABLE = {"periodogram": _TrialKind(0, 1, 2, (3, 2), 64, False), "transit": _TrialKind(1, 4, 1, (1, 1), 32, False),
+                "keplerian": _TrialKind(2, 3, 2, (3, 2), 128, False), "shape": _TrialKind(None, 4, 1, (1, 1), 32, True)}
+# kind -> (C2_TRIAL_*, doubles per trial, columns per trial C, vectors per wavefront C2_TRIAL_*_DRAWS) of celerite2_amd_trials.h
+TRIAL_KINDS = {k: (v.code, v.words, v.columns, v.draws) for k, v in _TRIAL_TABLE.items() if v.code is not None}
+SHAPE_MAX_NODES, SHAPE_DRAWS = 1024, _TRIAL_TABLE["shape"].draws   # C2_SHAPE_MAX_NODES, C2_SHAPE_DRAWS of celerite2_amd_shapes.h
+
+
+def _trial_grid(kd, trials, name="trials", k="K"):
+    """(K, shape spec, batch stride) of the trials of kind `kd`: (K,) | (B, K) at one double per trial, (K, words) |
+    (B, K, words) otherwise."""
+    lead = 1 if kd.words == 1 else 2
+    if trials.dim() not in (lead, lead + 1) or (lead == 2 and trials.shape[-1] != kd.words):
+        raise ValueError("Invalid shape: %s (must be %s)" % (name, "(%s,) or (B, %s)" % (k, k) if lead == 1 else
+                                                             "(K, %d) or (B, K, %d)" % (kd.words, kd.words)))
+    K = trials.shape[-lead]
+    return K, "K|BK" if lead == 1 else "KF|BKF", 0 if trials.dim() == lead else kd.words * K
+
+
+def _bank(shapes, B):
+    """(NS, S, batch stride) of a shape bank (NS, S) | (B, NS, S); its limits are checked here, from its shape."""
+    if shapes.dim() not in (2, 3) or (shapes.dim() == 3 and shapes.shape[0] != B):
+        raise ValueError("Invalid shape: shapes (must be (NS, S) or (B, NS, S) with B = %d)" % B)
+    NS, S = shapes.shape[-2:]
+    if NS < 1 or S < 2:
+        raise ValueError("Invalid shape: shapes (NS >= 1 shapes of S >= 2 nodes; got NS = %d, S = %d)" % (NS, S))
+    if NS * S > SHAPE_MAX_NODES:
+        raise ValueError("Invalid shape: shapes (NS * S <= %d; got %d * %d = %d -- a larger bank takes several calls)"
+                         % (SHAPE_MAX_NODES, NS, S, NS * S))
+    return NS, S, 0 if shapes.dim() == 2 else NS * S
+
+
+def _whitened(op, kind, t, c, U, W, d, Z0, trials, out, *, t_ref=None, shapes=None, name="trials", k="K"):
+    """The sweep c2_<op> of one kind of _TRIAL_TABLE: T (B, K, width).  `t_ref` goes before T in the call, the bank after it."""
+    kd = _TRIAL_TABLE[kind]
+    B, N, J = _dims(U)
+    if Z0.dim() != 3:
+        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
+    K, spec, tr_bs = _trial_grid(kd, trials, name, k)
+    Q0 = Z0.shape[-1]
+    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=kd.words, R=kd.width[0] + kd.width[1] * Q0)
+    ins = [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"), (name, trials, spec)]
+    bank = ()
+    if kd.bank:
+        NS, S, sh_bs = _bank(shapes, B)
+        dims.update(H=NS, S=S)
+        ins.append(("shapes", shapes, "HS|BHS"))
+        bank = (shapes, sh_bs, NS, S)
+    if out is None:
+        out, = _empty(U.device, dims, "BKR")
+    _args(dims, ins, [("out", out, "BKR")])
+    rc = getattr(_lib.load(), "c2_" + op)(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials, tr_bs,
+                                          *(() if t_ref is None else (float(t_ref),)), out, *bank, _stream())
+    _lib.check(rc, op)
+    return out
+
+
+def _projections(op, kind, t, alpha, trials, out, *, t_ref=0.0, shapes=None):
+    """The projection of one kind of _TRIAL_TABLE: P (B, K, C, R)."""
+    kd = _TRIAL_TABLE[kind]
+    if alpha.dim() != 3:
+        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
+    B, N, R = alpha.shape
+    K, spec, tr_bs = _trial_grid(kd, trials)
+    dims = dict(B=B, N=N, R=R, K=K, F=kd.words, C=kd.columns)
+    ins = [("t", t, _T), ("alpha", alpha, "BNR"), ("trials", trials, spec)]
+    if kd.bank:
+        NS, S, sh_bs = _bank(shapes, B)
+        dims.update(H=NS, S=S)
+        ins.append(("shapes", shapes, "HS|BHS"))
+    if out is None:
+        out, = _empty(alpha.device, dims, "BKCR")
+    _args(dims, ins, [("out", out, "BKCR")])
+    if kd.bank:
+        rc = _lib.load().c2_shape_projections(B, N, K, R, t, _bs(t, N), trials, tr_bs, alpha, out, shapes, sh_bs, NS, S, _stream())
+    else:
+        rc = _lib.load().c2_trial_projections(kd.code, B, N, K, R, t, _bs(t, N), trials, tr_bs, float(t_ref), alpha, out, _stream())
+    _lib.check(rc, op)
+    return out
+
+
 def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
     """T (B, F, 3 + 2 Q0): for every series and every ANGULAR trial frequency freq ((F,) shared by the batch or (B, F)), with
     z_c = L^-1 cos(w (t - t_ref)), z_s = L^-1 sin(w (t - t_ref)) and <a, b> = sum_n a_n b_n / d_n,
@@ -446,21 +533,7 @@ def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
     for the phase).  What the periodogram under correlated noise reads (celerite2_amd/periodogram.py).  Caller-owned `out` is
     accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.
     No atomics: two calls give identical bits."""
-    B, N, J = _dims(U)
-    if Z0.dim() != 3:
-        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
-    if freq.dim() not in (1, 2):
-        raise ValueError("Invalid shape: freq (must be (F,) or (B, F))")
-    Q0, F = Z0.shape[-1], freq.shape[-1]
-    dims = dict(B=B, N=N, J=J, Q=Q0, F=F, K=3 + 2 * Q0)
-    if out is None:
-        out, = _empty(U.device, dims, "BFK")
-    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
-                 ("freq", freq, "F|BF")], [("out", out, "BFK")])
-    rc = _lib.load().c2_whitened_sinusoids(B, N, J, Q0, F, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, freq, _bs(freq, F),
-                                           float(t_ref), out, _stream())
-    _lib.check(rc, "whitened_sinusoids")
-    return out
+    return _whitened("whitened_sinusoids", "periodogram", t, c, U, W, d, Z0, freq, out, t_ref=t_ref, name="freq", k="F")
 
 
 def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
@@ -474,21 +547,7 @@ def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
     the header has the rule for the template; P = 0 is a single event, P > 0 folds).  What the transit search under
     correlated noise reads (celerite2_amd/transit.py).  Caller-owned `out` is accepted (nothing is allocated then: capturable
     in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two calls give identical bits."""
-    B, N, J = _dims(U)
-    if Z0.dim() != 3:
-        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
-    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
-        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
-    Q0, K = Z0.shape[-1], trials.shape[-2]
-    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=4, R=1 + Q0)
-    if out is None:
-        out, = _empty(U.device, dims, "BKR")
-    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
-                 ("trials", trials, "KF|BKF")], [("out", out, "BKR")])
-    rc = _lib.load().c2_whitened_transits(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
-                                          0 if trials.dim() == 2 else 4 * K, out, _stream())
-    _lib.check(rc, "whitened_transits")
-    return out
+    return _whitened("whitened_transits", "transit", t, c, U, W, d, Z0, trials, out)
 
 
 def whitened_keplerians(t, c, U, W, d, Z0, trials, *, out=None):
@@ -505,75 +564,7 @@ def whitened_keplerians(t, c, U, W, d, Z0, trials, *, out=None):
     domain w > 0, 0 <= e <= 0.99 is the caller's to mask.  Caller-owned `out` is accepted (nothing is allocated then:
     capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two calls give identical
     bits."""
-    B, N, J = _dims(U)
-    if Z0.dim() != 3:
-        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
-    if trials.dim() not in (2, 3) or trials.shape[-1] != 3:
-        raise ValueError("Invalid shape: trials (must be (K, 3) or (B, K, 3))")
-    Q0, K = Z0.shape[-1], trials.shape[-2]
-    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=3, R=3 + 2 * Q0)
-    if out is None:
-        out, = _empty(U.device, dims, "BKR")
-    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
-                 ("trials", trials, "KF|BKF")], [("out", out, "BKR")])
-    rc = _lib.load().c2_whitened_keplerians(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
-                                            0 if trials.dim() == 2 else 3 * K, out, _stream())
-    _lib.check(rc, "whitened_keplerians")
-    return out
-
-
-# kind -> (C2_TRIAL_*, doubles per trial, columns per trial C, vectors per wavefront C2_TRIAL_*_DRAWS) of celerite2_amd_trials.h
-TRIAL_KINDS = {"periodogram": (0, 1, 2, 64), "transit": (1, 4, 1, 32), "keplerian": (2, 3, 2, 128)}
-
-
-def trial_projections(kind, t, alpha, trials, *, t_ref=0.0, out=None):
-    """P (B, K, C, R): P[b, k, c, r] = sum_n col_c(trial k; t[b, n]) alpha[b, n, r] for alpha (B, N, R), t (N,) shared by the
-    batch or (B, N), and the trials of `kind`: "periodogram" (ANGULAR frequencies (K,) | (B, K); columns cos, sin of
-    w (t - t_ref); C = 2), "transit" ((K, 4) | (B, K, 4) = (P, t0, w, tau); the template; C = 1) or "keplerian" ((K, 3) |
-    (B, K, 3) = (w, e, tp); columns cos nu, sin nu; C = 2).  The columns are formed in registers, bit for bit the ones
-    `whitened_sinusoids` / `whitened_transits` / `whitened_keplerians` whiten, and contracted with alpha on the matrix cores
-    (c2_trial_projections, csrc/c2_trial_project.hip): with alpha = (K + D)^-1 (y_r - mean), P is the one entry of those ops'
-    T that depends on y, for R series y_r at once.  What gp.search_significance reads.  Caller-owned `out` is accepted
-    (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No atomics: two calls give
-    identical bits."""
-    if kind not in TRIAL_KINDS:
-        raise ValueError("kind must be one of %s" % (tuple(TRIAL_KINDS),))
-    code, words, C, _ = TRIAL_KINDS[kind]
-    if alpha.dim() != 3:
-        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
-    B, N, R = alpha.shape
-    if code == 0:
-        if trials.dim() not in (1, 2):
-            raise ValueError("Invalid shape: trials (must be (K,) or (B, K))")
-        K, spec, shared = trials.shape[-1], "K|BK", trials.dim() == 1
-    else:
-        if trials.dim() not in (2, 3) or trials.shape[-1] != words:
-            raise ValueError("Invalid shape: trials (must be (K, %d) or (B, K, %d))" % (words, words))
-        K, spec, shared = trials.shape[-2], "KF|BKF", trials.dim() == 2
-    dims = dict(B=B, N=N, R=R, K=K, F=words, C=C)
-    if out is None:
-        out, = _empty(alpha.device, dims, "BKCR")
-    _args(dims, [("t", t, _T), ("alpha", alpha, "BNR"), ("trials", trials, spec)], [("out", out, "BKCR")])
-    rc = _lib.load().c2_trial_projections(code, B, N, K, R, t, _bs(t, N), trials, 0 if shared else words * K, float(t_ref),
-                                          alpha, out, _stream())
-    _lib.check(rc, "trial_projections")
-    return out
-
-
-SHAPE_MAX_NODES, SHAPE_DRAWS = 1024, 32   # C2_SHAPE_MAX_NODES, C2_SHAPE_DRAWS of celerite2_amd_shapes.h
-
-
-def _bank(shapes, B):
-    """(NS, S, batch stride) of a shape bank (NS, S) | (B, NS, S); its limits are checked here, from its shape."""
-    if shapes.dim() not in (2, 3) or (shapes.dim() == 3 and shapes.shape[0] != B):
-        raise ValueError("Invalid shape: shapes (must be (NS, S) or (B, NS, S) with B = %d)" % B)
-    NS, S = shapes.shape[-2:]
-    if NS < 1 or S < 2:
-        raise ValueError("Invalid shape: shapes (NS >= 1 shapes of S >= 2 nodes; got NS = %d, S = %d)" % (NS, S))
-    if NS * S > SHAPE_MAX_NODES:
-        raise ValueError("Invalid shape: shapes (NS * S <= %d; got %d * %d = %d -- a larger bank takes several calls)"
-                         % (SHAPE_MAX_NODES, NS, S, NS * S))
-    return NS, S, 0 if shapes.dim() == 2 else NS * S
+    return _whitened("whitened_keplerians", "keplerian", t, c, U, W, d, Z0, trials, out)
 
 
 def whitened_shapes(t, c, U, W, d, Z0, trials, shapes, *, out=None):
@@ -591,22 +582,22 @@ def whitened_shapes(t, c, U, W, d, Z0, trials, shapes, *, out=None):
     outside the bank (the index is clamped); the domain is the caller's to mask.  Caller-owned `out` is accepted (nothing
     is allocated then: capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.  No atomics: two
     calls give identical bits."""
-    B, N, J = _dims(U)
-    if Z0.dim() != 3:
-        raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
-    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
-        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
-    NS, S, sh_bs = _bank(shapes, B)
-    Q0, K = Z0.shape[-1], trials.shape[-2]
-    dims = dict(B=B, N=N, J=J, Q=Q0, K=K, F=4, R=1 + Q0, H=NS, S=S)
-    if out is None:
-        out, = _empty(U.device, dims, "BKR")
-    _args(dims, [("t", t, _T), ("c", c, _C), ("U", U, "BNJ"), ("W", W, "BNJ"), ("d", d, "BN"), ("Z0", Z0, "BNQ"),
-                 ("trials", trials, "KF|BKF"), ("shapes", shapes, "HS|BHS")], [("out", out, "BKR")])
-    rc = _lib.load().c2_whitened_shapes(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials,
-                                        0 if trials.dim() == 2 else 4 * K, out, shapes, sh_bs, NS, S, _stream())
-    _lib.check(rc, "whitened_shapes")
-    return out
+    return _whitened("whitened_shapes", "shape", t, c, U, W, d, Z0, trials, out, shapes=shapes)
+
+
+def trial_projections(kind, t, alpha, trials, *, t_ref=0.0, out=None):
+    """P (B, K, C, R): P[b, k, c, r] = sum_n col_c(trial k; t[b, n]) alpha[b, n, r] for alpha (B, N, R), t (N,) shared by the
+    batch or (B, N), and the trials of `kind`: "periodogram" (ANGULAR frequencies (K,) | (B, K); columns cos, sin of
+    w (t - t_ref); C = 2), "transit" ((K, 4) | (B, K, 4) = (P, t0, w, tau); the template; C = 1) or "keplerian" ((K, 3) |
+    (B, K, 3) = (w, e, tp); columns cos nu, sin nu; C = 2).  The columns are formed in registers, bit for bit the ones
+    `whitened_sinusoids` / `whitened_transits` / `whitened_keplerians` whiten, and contracted with alpha on the matrix cores
+    (c2_trial_projections, csrc/c2_trial_project.hip): with alpha = (K + D)^-1 (y_r - mean), P is the one entry of those ops'
+    T that depends on y, for R series y_r at once.  What gp.search_significance reads.  Caller-owned `out` is accepted
+    (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No atomics: two calls give
+    identical bits."""
+    if kind not in TRIAL_KINDS:
+        raise ValueError("kind must be one of %s" % (tuple(TRIAL_KINDS),))
+    return _projections("trial_projections", kind, t, alpha, trials, out, t_ref=t_ref)
 
 
 def shape_projections(t, alpha, trials, shapes, *, out=None):
@@ -614,25 +605,10 @@ def shape_projections(t, alpha, trials, shapes, *, out=None):
     (B, N), the trials (K, 4) | (B, K, 4) = (P, t0, w, s) and the bank `shapes` (NS, S) | (B, NS, S) of `whitened_shapes`:
     `trial_projections` for the tabulated shape, in the layout significance.null_statistics takes for a one-column kind.
     The column is formed in registers, bit for bit the one `whitened_shapes` whitens, and contracted with alpha on the
-    matrix cores (c2_shape_projections, csrc/c2_shape_project.hip).  What gp.shape_search_significance reads.  Caller-owned
+    matrix cores (c2_shape_projections, csrc/c2_trial_project.hip).  What gp.shape_search_significance reads.  Caller-owned
     `out` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No atomics: two
     calls give identical bits."""
-    if alpha.dim() != 3:
-        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
-    B, N, R = alpha.shape
-    if trials.dim() not in (2, 3) or trials.shape[-1] != 4:
-        raise ValueError("Invalid shape: trials (must be (K, 4) or (B, K, 4))")
-    NS, S, sh_bs = _bank(shapes, B)
-    K = trials.shape[-2]
-    dims = dict(B=B, N=N, R=R, K=K, F=4, C=1, H=NS, S=S)
-    if out is None:
-        out, = _empty(alpha.device, dims, "BKCR")
-    _args(dims, [("t", t, _T), ("alpha", alpha, "BNR"), ("trials", trials, "KF|BKF"), ("shapes", shapes, "HS|BHS")],
-          [("out", out, "BKCR")])
-    rc = _lib.load().c2_shape_projections(B, N, K, R, t, _bs(t, N), trials, 0 if trials.dim() == 2 else 4 * K, alpha, out,
-                                          shapes, sh_bs, NS, S, _stream())
-    _lib.check(rc, "shape_projections")
-    return out
+    return _projections("shape_projections", "shape", t, alpha, trials, out, shapes=shapes)
 
 
 _KRON_METHODS = {"collapsed": 0, "interleaved": 1}

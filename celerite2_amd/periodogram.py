@@ -39,7 +39,7 @@ def finish(S0, T, N, normalization="standard", ok=None):
     if normalization not in NORMALIZATIONS:
         raise ValueError("normalization must be one of %s" % (NORMALIZATIONS,))
     Q0 = S0.shape[-1]
-    S0, T, bad, chi2_0, v, X = null_fit(S0, T, ok, ("F", "3 + 2 Q0", 3 + 2 * Q0), (3, 3 + Q0))   # X (B, P0, 2 F)
+    S0, T, bad, chi2_0, v, X, _ = null_fit(S0, T, ok, ("F", "3 + 2 Q0", 3 + 2 * Q0), (3, 3 + Q0))   # X (B, P0, 2 F)
     P0, F = Q0 - 1, T.shape[1]
     nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
     a, b, c = T[..., 0], T[..., 1], T[..., 2]                         # Gtt

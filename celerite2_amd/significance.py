@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""False-alarm probabilities of the three searches (periodogram, transit, keplerian) under a correlated-noise covariance, by
-Monte Carlo under the null: the torch part.  It runs on CPU tensors as well.
+"""False-alarm probabilities of the searches (periodogram, transit, keplerian, tabulated shape) under a correlated-noise
+covariance, by Monte Carlo under the null: the torch part.  It runs on CPU tensors as well.
 
 The white-noise formulae for the highest peak do not apply under a GP covariance.  What does: draw noise from the factored
 covariance, run the same search on every draw, and compare the observed statistic with the distribution of the per-draw
@@ -29,7 +29,9 @@ import math
 import torch
 
 from . import kepler as _kp
+from . import ops as _ops
 from . import periodogram as _pg
+from . import shapes as _sh
 from . import transit as _tr
 from ._trial_fit import null_fit
 from .autograd import _RANK_TOL
@@ -38,6 +40,45 @@ __all__ = ["Significance", "KINDS", "null_statistics", "false_alarm_probability"
 
 Significance = collections.namedtuple("Significance", "statistic fap null_maxima")
 KINDS = ("periodogram", "transit", "keplerian")
+
+# WHAT DIFFERS BETWEEN THE SEARCHES, beside ops._TRIAL_TABLE's words and columns under the same key:
+#   sweep    (t, c, U, W, d, Z0, trials, t_ref, shapes) -> T, the op that whitens the trials' columns
+#   project  (t, alpha, trials, t_ref, shapes) -> P (B, K, C, R), the op that contracts them with many vectors
+#   finish   (S0, T, N, normalization, ok, trials, n_shapes) -> the fit of the observed series: a two-column kind's has .power,
+#            a one-column kind's delta_chi2, chi2_null and, second, the fitted amplitude
+#   domain   (trials, n_shapes) -> (..., K) bool, or None where every trial is in the domain
+#   dips     whether `dips_only` applies
+# KINDS are the ones `search_significance` and `null_statistics` take by name; "shape" has methods of its own (a bank goes
+# with its trials).
+_Search = collections.namedtuple("_Search", "sweep project finish domain dips")
+SEARCHES = {
+    "periodogram": _Search(lambda *a, t_ref, shapes: _ops.whitened_sinusoids(*a, t_ref=t_ref),
+                           lambda *a, t_ref, shapes: _ops.trial_projections("periodogram", *a, t_ref=t_ref),
+                           lambda S0, T, N, norm, ok, trials, n: _pg.finish(S0, T, N, norm, ok=ok), None, False),
+    "transit": _Search(lambda *a, t_ref, shapes: _ops.whitened_transits(*a),
+                       lambda *a, t_ref, shapes: _ops.trial_projections("transit", *a),
+                       lambda S0, T, N, norm, ok, trials, n: _tr.finish(S0, T, N, ok=ok, trials=trials),
+                       lambda trials, n: _tr.in_domain(trials), True),
+    "keplerian": _Search(lambda *a, t_ref, shapes: _ops.whitened_keplerians(*a),
+                         lambda *a, t_ref, shapes: _ops.trial_projections("keplerian", *a),
+                         lambda S0, T, N, norm, ok, trials, n: _kp.finish(S0, T, N, norm, ok=ok, trials=trials),
+                         lambda trials, n: _kp.in_domain(trials), False),
+    "shape": _Search(lambda *a, t_ref, shapes: _ops.whitened_shapes(*a, shapes),
+                     lambda *a, t_ref, shapes: _ops.shape_projections(*a, shapes),
+                     lambda S0, T, N, norm, ok, trials, n: _sh.finish(S0, T, N, ok=ok, trials=trials, n_shapes=n), _sh.in_domain, True),
+}
+
+
+def check_trials(kind, trials, B, name="trials", count="K"):
+    """`trials` contiguous, after the shape check every search makes on them: (K,) | (B, K) at one double per trial,
+    (K, words) | (B, K, words) otherwise, K >= 1."""
+    words = _ops._TRIAL_TABLE[kind].words
+    lead = 1 if words == 1 else 2
+    if not torch.is_tensor(trials) or trials.dim() not in (lead, lead + 1) or (trials.dim() == lead + 1 and trials.shape[0] != B) \
+            or (lead == 2 and trials.shape[-1] != words) or trials.shape[-lead] < 1:
+        raise ValueError("Invalid shape: %s (must be %s with B = %d, %s >= 1)"
+                         % (name, "(F,) or (B, F)" if lead == 1 else "(K, %d) or (B, K, %d)" % (words, words), B, count))
+    return trials.contiguous()
 
 
 def _xtv(X, V):
@@ -65,29 +106,33 @@ def null_statistics(kind, S0, T, G0Y, s_yy, P, N, *, normalization="standard", t
     to take at all.  With R = 1 and the series' own products this is the `finish` of the kind."""
     if kind not in KINDS:
         raise ValueError("kind must be one of %s" % (KINDS,))
+    return _null_statistics(kind, S0, T, G0Y, s_yy, P, N, normalization, trials, None, dips_only, ok)
+
+
+def _null_statistics(kind, S0, T, G0Y, s_yy, P, N, normalization, trials, n_shapes, dips_only, ok):
+    """null_statistics for any kind of SEARCHES; `n_shapes`: the bank's, for the shape's domain."""
     if normalization not in _pg.NORMALIZATIONS:
         raise ValueError("normalization must be one of %s" % (_pg.NORMALIZATIONS,))
     Q0 = S0.shape[-1]
-    two = kind != "transit"
+    words, C, domain = _ops._TRIAL_TABLE[kind].words, _ops._TRIAL_TABLE[kind].columns, SEARCHES[kind].domain
+    two = C == 2
     layout = ("K", "3 + 2 Q0", 3 + 2 * Q0) if two else ("K", "1 + Q0", 1 + Q0)
-    S0, T, bad, _, _, X = null_fit(S0, T, ok, layout, (3, 3 + Q0) if two else (1,))
-    B, P0, K, C = S0.shape[0], Q0 - 1, T.shape[1], 2 if two else 1
+    S0, T, bad, _, _, X, L0 = null_fit(S0, T, ok, layout, (3, 3 + Q0) if two else (1,))
+    B, P0, K = S0.shape[0], Q0 - 1, T.shape[1]
     if P.dim() != 4 or tuple(P.shape[:3]) != (B, K, C):
         raise ValueError("Invalid shape: P (must be (B, K, C, R) = (%d, %d, %d, R))" % (B, K, C))
     R = P.shape[-1]
     if tuple(s_yy.shape) != (B, R) or tuple(G0Y.shape) != (B, P0, R):
         raise ValueError("Invalid shape: s_yy, G0Y (must be (B, R) and (B, P0, R) = (%d, %d) and (%d, %d, %d))" % (B, R, B, P0, R))
-    if trials is not None and kind != "periodogram":
-        words = 4 if kind == "transit" else 3
+    if domain is None:
+        trials = None
+    if trials is not None:
         if trials.dim() not in (2, 3) or tuple(trials.shape[-2:]) != (K, words) or (trials.dim() == 3 and trials.shape[0] != B):
             raise ValueError("Invalid shape: trials (must be (K, %d) or (B, K, %d) = (%d, %d, %d))" % (words, words, B, K, words))
     nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
     one = torch.ones((), dtype=S0.dtype, device=S0.device)
     chi2_0 = s_yy
     if P0:
-        # the null fit's factor once more (null_fit keeps it to itself), made harmless on the same series
-        L0 = torch.linalg.cholesky_ex(S0[:, :P0, :P0])[0]
-        L0 = torch.where(bad[:, None, None], torch.eye(P0, dtype=S0.dtype, device=S0.device), L0)
         G0Y = torch.where(bad[:, None, None], torch.zeros((), dtype=S0.dtype, device=S0.device), G0Y)
         V = torch.linalg.solve_triangular(L0, G0Y, upper=False)                                          # (B, P0, R)
         chi2_0 = s_yy - (V * V).sum(dim=1)
@@ -112,8 +157,6 @@ def null_statistics(kind, S0, T, G0Y, s_yy, P, N, *, normalization="standard", t
         stat = _normalize(w1 * w1 + w2 * w2, chi2_0, normalization)
         if N < P0 + 3:
             sing = torch.ones_like(sing)
-        if trials is not None and kind == "keplerian":
-            sing = sing | ~_kp.in_domain(trials).expand(B, K)
     else:
         M = zz = T[..., 0]
         r = P[:, :, 0]
@@ -121,15 +164,25 @@ def null_statistics(kind, S0, T, G0Y, s_yy, P, N, *, normalization="standard", t
             M = zz - (X * X).sum(dim=1)
             r = r - _xtv(X, V)
         sing = ~(M > _RANK_TOL * zz)
-        if trials is not None:
-            sing = sing | ~_tr.in_domain(trials)
         if N < P0 + 2:
             sing = torch.ones_like(sing)
         snr = r / torch.sqrt(torch.where(sing | bad[:, None], one, M))[..., None]
         stat = _normalize(snr * snr, chi2_0, normalization)
-        if dips_only:
+        if dips_only and SEARCHES[kind].dips:
             stat = torch.where(r > 0, torch.zeros((), dtype=S0.dtype, device=S0.device), stat)
+    if trials is not None:
+        sing = sing | ~domain(trials, n_shapes).expand(B, K)
     return torch.where((sing | bad[:, None])[..., None], nan, stat)
+
+
+def observed_statistic(kind, S0, T, N, normalization, trials, n_shapes, dips_only, ok):
+    """(B, K): the statistic of the observed series from its own products -- the power of a two-column kind; of a
+    one-column kind delta_chi2 in `normalization`, with `dips_only` 0 where the fitted amplitude is positive."""
+    fit = SEARCHES[kind].finish(S0, T, N, normalization, ok, trials, n_shapes)
+    if _ops._TRIAL_TABLE[kind].columns == 2:
+        return fit.power
+    statistic = _normalize(fit.delta_chi2, fit.chi2_null[:, None], normalization)
+    return torch.where(fit[1] > 0, torch.zeros_like(statistic), statistic) if dips_only and SEARCHES[kind].dips else statistic
 
 
 def false_alarm_probability(statistic, maxima, *, rtol=0.0):

@@ -44,7 +44,7 @@ def finish(S0, T, N, ok=None, trials=None):
     hold NaN; their S0, T are not read).  `trials` (K, 4) | (B, K, 4) | None: the trials T was made from, to hold NaN where one
     is outside the domain."""
     Q0 = S0.shape[-1]
-    S0, T, bad, chi2_0, v, X = null_fit(S0, T, ok, ("K", "1 + Q0", 1 + Q0), (1,))                 # X (B, P0, K)
+    S0, T, bad, chi2_0, v, X, _ = null_fit(S0, T, ok, ("K", "1 + Q0", 1 + Q0), (1,))                 # X (B, P0, K)
     B, P0, K = S0.shape[0], Q0 - 1, T.shape[1]
     if trials is not None and (trials.dim() not in (2, 3) or tuple(trials.shape[-2:]) != (K, 4)
                                or (trials.dim() == 3 and trials.shape[0] != B)):

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""numpy restatement of the whitened-Keplerian sweep (celerite2_amd/csrc/c2_kepler.hip) and of what it and the torch finish
+"""numpy restatement of the whitened-Keplerian sweep (celerite2_amd/csrc/c2_kepler.hip: trial::k_trial_sweep on trial::Keplerian) and of what it and the torch finish
 (celerite2_amd/kepler.py) are checked against: a bracketed extended-precision solution of Kepler's equation, dense algebra on
 the matrix the celerite matrices stand for, and two dense generalized-least-squares fits per trial.  Test infrastructure
 only -- nothing here is imported by the package.

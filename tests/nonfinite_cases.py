@@ -417,9 +417,9 @@ NOT_RUN = {
 # B = 9 series of 33 rows; one series' d row, W entry or Z0 / z / alpha entry set to NaN.  These ops have no pivot test, no
 # verification word and no fallback: every healthy series owes the bits of the clean run (criterion (d) as bit-identity),
 # and (b) is held against the numpy restatements under tests/*_ref.py run on the same poisoned arrays.
-# Loop reading (none value-steered): c2_invdiag.hip, c2_gram.hip, c2_periodogram.hip, c2_transit.hip, c2_kepler.hip,
-# c2_trial_project.hip and c2_trial_sweep.hpp:89 loop over rows, trials and columns by count; c2_trial_columns.hpp:94 is three
-# fixed Newton steps on the TRIAL's eccentric anomaly and :32 / :69 round phases of t x trial (times and trials are never
+# Loop reading (none value-steered): c2_invdiag.hip, c2_gram.hip, c2_trial_project.hip and the one sweep of c2_periodogram.hip,
+# c2_transit.hip and c2_kepler.hip (c2_trial_sweep.hpp:89) loop over rows, trials and columns by count; c2_trial_columns.hpp:98 is three
+# fixed Newton steps on the TRIAL's eccentric anomaly and :41 / :73 round phases of t x trial (times and trials are never
 # poisoned); the event loop of c2_predvar.hip:100 runs N + M times and picks data or query by `tn <= tq` (:110), times only.
 CONSUMER_SHAPE = dict(B=9, N=33, rows=(0, 16, 32), series=(0, 4, 8))
 CONSUMERS = {

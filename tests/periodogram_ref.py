@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""numpy restatement of the whitened-sinusoid sweep (celerite2_amd/csrc/c2_periodogram.hip) and of what it and the torch
+"""numpy restatement of the whitened-sinusoid sweep (celerite2_amd/csrc/c2_periodogram.hip: trial::k_trial_sweep on trial::Sinusoid) and of what it and the torch
 finish (celerite2_amd/periodogram.py) are checked against: dense algebra on the matrix the celerite matrices stand for,
 dense generalized least squares per frequency, and the classical floating-mean periodogram in closed form.  Test
 infrastructure only -- nothing here is imported by the package.

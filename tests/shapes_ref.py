@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""numpy restatement of the tabulated-shape column (celerite2_amd/csrc/c2_shape_column.hpp), of the sweep that whitens it
-(c2_shapes.hip) and of the projection onto it (c2_shape_project.hip), and of what they and the torch finish
+"""numpy restatement of the tabulated-shape column (trial::Shape, celerite2_amd/csrc/c2_trial_columns.hpp), of the sweep that whitens it
+(c2_shapes.hip) and of the projection onto it (c2_trial_project.hip), and of what they and the torch finish
 (celerite2_amd/shapes.py) are checked against: dense algebra on the matrix the celerite matrices stand for with the column
 built another way, and two dense generalized-least-squares fits per trial.  Test infrastructure only -- nothing here is
 imported by the package.

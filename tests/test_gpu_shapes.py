@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """GPU checks of the tabulated-shape search under correlated noise: ops.whitened_shapes (c2_whitened_shapes,
-csrc/c2_shapes.hip), ops.shape_projections (c2_shape_projections, csrc/c2_shape_project.hip),
+csrc/c2_shapes.hip), ops.shape_projections (c2_shape_projections, csrc/c2_trial_project.hip),
 GaussianProcess.shape_search and GaussianProcess.shape_search_significance.
 
 References: the numpy restatement of the rule, the sweep and the projection (tests/shapes_ref.py, pinned to dense algebra by

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """The tabulated-shape search under correlated noise on the CPU: the numpy restatement of the column rule and of the sweep
-(tests/shapes_ref.py, what csrc/c2_shape_column.hpp and csrc/c2_shapes.hip implement) against dense algebra with the column
+(tests/shapes_ref.py, what trial::Shape of csrc/c2_trial_columns.hpp and csrc/c2_shapes.hip implement) against dense algebra with the column
 built another way, against the transit restatement where the two rules must coincide (bit for bit for the box), the torch
 finish and the builders (celerite2_amd/shapes.py), an injected limb-darkened transit, and the binding of the seventh public
 header (include/celerite2_amd_shapes.h), which needs no device.  Criterion: the standing one,
@@ -123,6 +123,70 @@ def test_box_is_the_transit_box_bit_for_bit():
             assert np.array_equal(R.column(ts, trials, ones), TR.template(ts, trials))
         args = [D[x] for x in ("t", "c", "U", "W", "d", "Z0", "trials")]
         assert np.array_equal(R.whitened_shapes(*args, ones), TR.whitened_transits(*args))
+
+
+def test_significance_with_a_box_bank_is_the_transit_branch_bit_for_bit(monkeypatch):
+    """gp.shape_search_significance with the all-ones S = 2 bank (shapes.box()) and gp.search_significance("transit", ...) on
+    the same tau = 0 trials and the same normals give the same bits -- statistic, fap and null_maxima, NaN positions
+    included -- at every normalization, with and without dips_only, in blocks of trials and draws as well: one loop serves
+    both.  On CPU tensors: the ops are replaced by the restatements (the two columns by R.column and TR.template, which the
+    test above holds equal; one contraction for both projections, so that no summation order stands between them)."""
+    import types
+
+    import trial_projections_ref as PJ
+    from celerite2_amd import gp as G, ops, shapes as sh
+
+    B, N, J = 2, 40, 3
+    Ds = [TR.case(7 + b, N, J, 1, K=29, kinds=("fold-box", "single-box")) for b in range(B)]
+    t = Ds[0]["t"]
+    for D in Ds[1:]:                                                              # (one time axis: the trials are shared)
+        D["t"] = t
+        D["d"], D["W"] = R.factor(t, D["c"], D["a"], D["U"], D["V"])
+    trials = np.concatenate([Ds[0]["trials"], [[1.0, 0.5, 2.0, 0.0], [0.0, 1.0, 0.0, 0.0], [-1.0, 1.0, 0.5, 0.0]]])   # three outside
+    assert np.all(trials[:, 3] == 0.0)
+    tn = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    stack = lambda k: tn(np.stack([D[k] for D in Ds]))
+    npy = lambda x: x.numpy()
+    Ls = [PJ.lower(t, D["c"], D["U"], D["W"]) for D in Ds]
+    per_series = lambda f, *xs: tn(np.stack([f(b, *[npy(x)[b] for x in xs]) for b in range(B)]))
+
+    def project(col, alpha):                                                       # col (N, K), alpha (N, R) -> (K, 1, R)
+        return np.einsum("nk,nr->kr", col.astype(np.longdouble), alpha.astype(np.longdouble)).astype(float)[:, None, :]
+
+    sweep_args = lambda b, Z0: (t, Ds[b]["c"], Ds[b]["U"], Ds[b]["W"], Ds[b]["d"], Z0)
+    monkeypatch.setattr(ops, "solve_lower", lambda t_, c, U, W, Y: per_series(lambda b, y: np.linalg.solve(Ls[b], y), Y))
+    monkeypatch.setattr(ops, "solve_upper", lambda t_, c, U, W, Y: per_series(lambda b, y: np.linalg.solve(Ls[b].T, y), Y))
+    monkeypatch.setattr(ops, "whitened_transits",
+                        lambda t_, c, U, W, d, Z0, tr: per_series(lambda b, z: TR.whitened_transits(*sweep_args(b, z), npy(tr)), Z0))
+    monkeypatch.setattr(ops, "whitened_shapes",
+                        lambda t_, c, U, W, d, Z0, tr, bank: per_series(lambda b, z: R.whitened_shapes(*sweep_args(b, z), npy(tr), npy(bank)), Z0))
+    monkeypatch.setattr(ops, "trial_projections",
+                        lambda kind, t_, alpha, tr, t_ref=0.0: per_series(lambda b, a: project(TR.template(t, npy(tr)), a), alpha))
+    monkeypatch.setattr(ops, "shape_projections",
+                        lambda t_, alpha, tr, bank: per_series(lambda b, a: project(R.column(t, npy(tr), npy(bank)), a), alpha))
+
+    gp = types.SimpleNamespace(_need=lambda: None, _check_vector=lambda y: None, mean=0.0, _t=tn(t), _c=stack("c"), _U=stack("U"),
+                               _W=stack("W"), _d=stack("d"), _diag=torch.ones((B, N), dtype=torch.float64),
+                               _flag=torch.zeros(B, dtype=torch.int32))
+    for name in ("_whitened_columns", "_nan_failed", "_shape_args"):
+        setattr(gp, name, getattr(G.GaussianProcess, name).__get__(gp))
+    y, normals = stack("y"), torch.from_numpy(np.random.default_rng(3).normal(size=(B, N, 12)))
+    trials, bank = tn(trials), sh.stack(sh.box())
+    assert tuple(bank.shape) == (1, 2) and bool((bank == 1.0).all())
+    zeroed = 0
+    for nm in ("standard", "chi2", "log_likelihood"):
+        for dips in (False, True):
+            for blocks in (dict(), dict(max_trials=10, max_draws=5)):
+                kw = dict(normalization=nm, dips_only=dips, normals=normals, **blocks)
+                a = G.GaussianProcess.search_significance(gp, "transit", y, trials, **kw)
+                b = G.GaussianProcess.shape_search_significance(gp, y, trials, bank, **kw)
+                for x, xo, what in zip(a, b, a._fields):
+                    assert x.shape == xo.shape and np.array_equal(npy(x), npy(xo), equal_nan=True), (nm, dips, blocks, what)
+                assert bool(torch.isnan(a.statistic[:, -3:]).all()) and bool(torch.isfinite(a.statistic[:, :-3]).all())
+                assert bool(torch.isfinite(a.null_maxima).all()) and bool(((a.fap[:, :-3] > 0) & (a.fap[:, :-3] <= 1)).all())
+                zeroed += int((a.statistic == 0).sum()) if dips else 0
+                assert dips or not bool((a.statistic == 0).any())
+    assert zeroed > 0                                                              # (dips_only did change something)
 
 
 def test_trapezoid_bank_meets_the_transit_trapezoid():
@@ -351,7 +415,7 @@ def test_shapes_header_is_exported_and_typed(lib):
     assert len(_lib.SYMBOLS) == 68
     assert not set(_lib.SHAPES_SYMBOLS) & set().union(*others)
     assert os.path.join(build.INCLUDE, "celerite2_amd_shapes.h") in build.HIP_HEADERS
-    assert "c2_shapes.hip" in build.HIP_SOURCES and "c2_shape_project.hip" in build.HIP_SOURCES
+    assert "c2_shapes.hip" in build.HIP_SOURCES and "c2_trial_project.hip" in build.HIP_SOURCES   # (both entry points' sources)
     assert all(n not in ops.__all__ for n in ("whitened_shapes", "shape_projections"))
     assert callable(ops.whitened_shapes) and callable(ops.shape_projections)
     defines = dict(re.findall(r"^#define\s+(C2_SHAPE_\w+)\s+(\d+)\s*$", text, flags=re.M))

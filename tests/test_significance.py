@@ -262,7 +262,7 @@ def tp_args(kind=0, B=1, N=4, K=3, R=2, p=None, P=None):
 
 
 def test_trials_header_is_exported_and_typed(lib):
-    from celerite2_amd import _lib, build, ops
+    from celerite2_amd import _lib, build, ops, significance as sg
 
     text = open(os.path.join(ROOT, "include", "celerite2_amd_trials.h")).read()
     header = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
@@ -278,16 +278,36 @@ def test_trials_header_is_exported_and_typed(lib):
     assert os.path.join(build.INCLUDE, "celerite2_amd_trials.h") in build.HIP_HEADERS
     assert "c2_trial_project.hip" in build.HIP_SOURCES
     assert "trial_projections" not in ops.__all__ and callable(ops.trial_projections)
-    # the op's table is the header's
+    # the op's tables are the headers': codes, draws a wavefront, doubles a trial, columns, the width of T
     defs = {k: int(v) for k, v in re.findall(r"^#define\s+(C2_TRIAL_\w+)\s+(\d+)", text, flags=re.M)}
+    shapes_h = open(os.path.join(ROOT, "include", "celerite2_amd_shapes.h")).read()
+    defs.update({k: int(v) for k, v in re.findall(r"^#define\s+(C2_SHAPE_\w+)\s+(\d+)", shapes_h, flags=re.M)})
+    assert set(ops.TRIAL_KINDS) == set(R.KINDS) and set(ops._TRIAL_TABLE) == set(sg.SEARCHES) == set(R.KINDS) | {"shape"}
+    assert sg.KINDS == R.KINDS
     for kind, name in (("periodogram", "SINUSOID"), ("transit", "TRANSIT"), ("keplerian", "KEPLERIAN")):
         code, words, C, RB = ops.TRIAL_KINDS[kind]
         assert (code, RB) == (defs["C2_TRIAL_" + name], defs["C2_TRIAL_%s_DRAWS" % name]) and RB % 16 == 0
         assert (words, C) == (R.WORDS[kind], R.NCOL[kind])
-    # the three sweeps and the projection share one statement of the columns
+        assert ops._TRIAL_TABLE[kind][:3] + (ops._TRIAL_TABLE[kind].draws, ops._TRIAL_TABLE[kind].bank) == (code, words, C, RB, False)
+    shape = ops._TRIAL_TABLE["shape"]
+    assert (shape.code, shape.words, shape.columns, shape.draws, shape.bank) == (None, 4, 1, defs["C2_SHAPE_DRAWS"], True)
+    assert ops.SHAPE_DRAWS == defs["C2_SHAPE_DRAWS"] and ops.SHAPE_MAX_NODES == defs["C2_SHAPE_MAX_NODES"]
+    # the width of T as the headers state it: 3 + 2 Q0 for a two-column kind, 1 + Q0 for a one-column kind
+    headers = {"periodogram": "periodogram", "transit": "transit", "keplerian": "kepler", "shape": "shapes"}
+    for kind, kd in ops._TRIAL_TABLE.items():
+        assert kd.width == ((3, 2) if kd.columns == 2 else (1, 1)), kind
+        h = open(os.path.join(ROOT, "include", "celerite2_amd_%s.h" % headers[kind])).read()
+        assert ("3 + 2 Q0" if kd.columns == 2 else "1 + Q0") in h, kind
+        assert (sg.SEARCHES[kind].domain is None) == (kind == "periodogram") and sg.SEARCHES[kind].dips == (kd.columns == 1)
+    # every source that forms a trial column includes the one statement of the columns, and no other file defines a rule
     csrc = os.path.join(ROOT, "celerite2_amd", "csrc")
-    for src in ("c2_periodogram.hip", "c2_transit.hip", "c2_kepler.hip", "c2_trial_project.hip"):
+    for src in ("c2_periodogram.hip", "c2_transit.hip", "c2_kepler.hip", "c2_shapes.hip", "c2_trial_sweep.hpp", "c2_trial_project.hip"):
         assert '#include "c2_trial_columns.hpp"' in open(os.path.join(csrc, src)).read(), src
+    rule = re.compile(r"\bcolumns\s*\(double t\b|struct (Sinusoid|Transit|Keplerian|Shape|Fold)\b|\b(danby|mean_anomaly|phase)\s*\(double\b")
+    for src in sorted(os.listdir(csrc)):
+        found = rule.search(open(os.path.join(csrc, src)).read())
+        assert (found is not None) == (src == "c2_trial_columns.hpp"), (src, found)
+    assert not os.path.exists(os.path.join(csrc, "c2_shape_column.hpp")) and not os.path.exists(os.path.join(csrc, "c2_shape_project.hip"))
 
 
 def test_bad_projection_calls_are_refused_before_c(lib):

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""numpy restatement of the whitened-transit sweep (celerite2_amd/csrc/c2_transit.hip) and of what it and the torch finish
+"""numpy restatement of the whitened-transit sweep (celerite2_amd/csrc/c2_transit.hip: trial::k_trial_sweep on trial::Transit) and of what it and the torch finish
 (celerite2_amd/transit.py) are checked against: dense algebra on the matrix the celerite matrices stand for, two dense
 generalized-least-squares fits per trial, and the classical weighted box-least-squares statistic in closed form.  Test
 infrastructure only -- nothing here is imported by the package.

@@ -28,7 +28,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from trial_static import MIX_HEAD, fp64_valu, kept_block, kernel_asm, mix_cells, register_table, row_loop_mix, with_block  # noqa: E402
+from trial_static import MIX_HEAD, alternate, fp64_valu, kept_block, mix_cells, row_loop_mix, sweep_asm, sweep_label, sweep_registers, sweep_symbol, with_block  # noqa: E402
 
 FP64_PEAK = 78.6e12 / 2.0   # fp64 VALU instructions per lane and second
 SHAPES = [(64, 4096, 8, 4096), (1, 4096, 8, 4096), (1024, 1024, 4, 1024), (64, 4096, 32, 512)]
@@ -44,14 +44,14 @@ def recurrence_fp64(jr, qr):
 
 
 def instruction_table():
-    asm = kernel_asm("c2_kepler.hip")
+    asm = sweep_asm("keplerian")
     if asm is None:
         return None
-    mix = lambda jr, qr: row_loop_mix(asm, "_ZN2c26kepler12k_keplerians" + "ILi%dELi%dEE" % (jr, qr))[0]
+    mix = lambda jr, qr: row_loop_mix(asm, sweep_symbol("keplerian", jr, qr))[0]
     lines = [MIX_HEAD + " solver's share of the fp64 VALU |", "|---|---|---|---|---|---|---|---|"]
     for jr, qr in INSTANCES:
         c = mix(jr, qr)
-        lines.append("| `k_keplerians<%d, %d>` | %s %.0f %% |" % (jr, qr, mix_cells(c), 100.0 * (1.0 - recurrence_fp64(jr, qr) / fp64_valu(c))))
+        lines.append("| `%s` | %s %.0f %% |" % (sweep_label("keplerian", jr, qr), mix_cells(c), 100.0 * (1.0 - recurrence_fp64(jr, qr) / fp64_valu(c))))
     lines += ["", "One row of one lane (one trial; at JR = 32 one of a trial's two columns): the solve has no branch, so this is the "
               "only path.  The solver's share: the row's fp64 VALU instructions less the recurrence's own (3 JR + 6 + QR a column, "
               "one for <z_c, z_s>).  fp64 VALU per lane-row, machine-readable: "
@@ -91,7 +91,7 @@ def main():
     a = ap.parse_args()
     old = open(a.out).read() if a.out and os.path.exists(a.out) else ""
     if a.static_only:
-        text = with_block(old, "registers", register_table("c2_kepler.o", "c2::kepler::", "k_keplerians"), TOOL)
+        text = with_block(old, "registers", sweep_registers("keplerian"), TOOL)
         text = with_block(text, "instructions", instruction_table(), TOOL)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -105,28 +105,6 @@ def main():
     assert torch.cuda.is_available(), "this measures the GPU: there is nothing to fall back to"
     dev = torch.device("cuda:0")
     per_row = dict((int(k), int(v)) for k, v in re.findall(r"JR(\d+)=(\d+)", kept_block(old, "instructions", TOOL) or ""))
-
-    def stats(ms):
-        ms = sorted(ms)
-        return ms[len(ms) // 2], ms[0], ms[-1]
-
-    def alternate(runs, steps):
-        """runs: name -> (fn, steps or None)."""
-        for k, (fn, n) in runs.items():
-            for _ in range(a.warmup if n is None else 1):
-                fn()
-        # events made beforehand and ONE synchronise at the end: the device never idles between steps
-        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n or steps)]
-              for k, (fn, n) in runs.items()}
-        torch.cuda.synchronize()
-        for i in range(steps):
-            for k, (fn, n) in runs.items():
-                if i < len(ev[k]):
-                    ev[k][i][0].record()
-                    fn()
-                    ev[k][i][1].record()
-        torch.cuda.synchronize()
-        return {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
 
     lines = ["# gp.keplerian_search's route beside ops.whitened_gram in chunks of 15 trials", "",
              "One process, steps alternating between the routes, %d timed steps each (composed: %d) after %d warm-up steps "
@@ -187,7 +165,7 @@ def main():
         worst = float(((p1 - p2).abs() / tol)[fin].max())
         assert bool(torch.equal(torch.isnan(p1), torch.isnan(p2))) and worst < 1e4, "the two routes disagree: %g" % worst
         agree.append("%d x %d x %d x %d: %.3g (%d series not factored)" % (B, N, J, K, worst, int((~ok).sum())))
-        out = alternate({"fused": (fused, None), "kernel": (kernel, None), "composed": (composed, a.composed_steps)}, a.steps)
+        out = alternate({"fused": (fused, None), "kernel": (kernel, None), "composed": (composed, a.composed_steps)}, a.steps, a.warmup)
         jr = 4 if J <= 4 else 8 if J <= 8 else 16 if J <= 16 else 32
         lane_rows = B * N * K * (2 if jr == 32 else 1)
         for op, st in out.items():

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""What the tabulated-shape search under correlated noise costs (csrc/c2_shapes.hip, csrc/c2_shape_project.hip) beside the
+"""What the tabulated-shape search under correlated noise costs (csrc/c2_shapes.hip, csrc/c2_trial_project.hip) beside the
 box sweep it is modelled on and beside the only route there was before it, on one device, in ONE fresh process:
 
     python tools/bench_shapes.py [--steps 10] [--out profiles/shape_search.md] [--quick]
@@ -25,7 +25,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from trial_static import MIX_HEAD, fp64_valu, kept_block, kernel_asm, mix_cells, register_table, row_loop_mix, with_block  # noqa: E402
+from trial_static import (MIX_HEAD, alternate, fp64_valu, kept_block, mix_cells, register_table, row_loop_mix, short_name, sorted_rows,  # noqa: E402
+                          sweep_asm, sweep_label, sweep_registers, sweep_symbol, with_block)
 
 SHAPES = [(64, 4096, 8, 4096), (1, 4096, 8, 4096), (1024, 1024, 4, 1024), (64, 4096, 32, 512)]
 DRAWS = (128, 1024)
@@ -36,24 +37,19 @@ BANK_PAIRS = 16 * 1024                              # a bank at the cap staged a
 
 
 def occupancy_table():
-    """Waves per SIMD that registers and LDS each allow for every k_shapes<JR, QR>, and what a bank staged in LDS would
-    have left: the figures behind reading the nodes through the vector cache."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from kernel_regs import kernel_rows
-    import re
-
-    rows = [r for r in kernel_rows("c2_shapes.o") if "k_shapes" in r[1]]
+    """Waves per SIMD that registers and LDS each allow for every k_trial_sweep<Shape, JR, QR>, and what a bank staged in
+    LDS would have left: the figures behind reading the nodes through the vector cache."""
+    rows = sorted_rows("c2_shapes.o", "k_trial_sweep")
     if not rows:
         return None
     lines = ["| kernel | registers | waves / SIMD by registers | LDS bytes | waves / SIMD by LDS | by LDS with a 16 KB bank staged |",
              "|---|---|---|---|---|---|"]
     hit = 0
-    for _, name, vg, ag, scratch, lds, spill, sg in sorted(rows, key=lambda r: [int(v) for v in re.findall(r"\d+", re.sub(r"\(.*", "", r[1]))[-2:]]):
+    for _, name, vg, ag, scratch, lds, spill, sg in rows:
         by_reg = min(WAVES_MAX, VGPRS // (8 * ((vg + ag + 7) // 8)))
         by_lds, by_bank = (LDS_CU // lds) / 4.0, (LDS_CU // (lds + BANK_PAIRS)) / 4.0      # one-wave blocks, four SIMDs
         hit += by_bank < min(by_reg, by_lds)
-        lines.append("| `%s` | %d | %d | %d | %.2f | %.2f |" % (re.sub(r"\(.*", "", name).replace("void c2::shape::", ""), vg + ag, by_reg, lds,
-                                                               min(WAVES_MAX, by_lds), by_bank))
+        lines.append("| `%s` | %d | %d | %d | %.2f | %.2f |" % (short_name(name), vg + ag, by_reg, lds, min(WAVES_MAX, by_lds), by_bank))
     lines += ["", "512 registers per lane and SIMD in steps of 8, 160 KiB of LDS per compute unit shared by its four SIMDs, blocks of one "
               "wavefront.  As shipped (the bank read through the vector cache) registers set the occupancy at every instantiation; a bank at "
               "the cap staged in LDS would have set it, lower, at %d of %d." % (hit, len(rows))]
@@ -61,31 +57,27 @@ def occupancy_table():
 
 
 def registers():
-    a = register_table("c2_shapes.o", "c2::shape::", "k_shapes")
-    b = register_table("c2_shape_project.o", "c2::shape::", "k_shape_project")
+    a = sweep_registers("shape")
+    b = register_table("c2_trial_project.o", " (`k_project<Shape, NQ>`: NQ = C2_SHAPE_DRAWS / 16 tiles of 16 draws a wavefront).", "Shape")
     occ = occupancy_table()
-    if a is None or b is None or occ is None:
-        return None
-    b = b.rsplit("\n\n", 1)[0] + "\n\n`k_shape_project<NQ>`: NQ = C2_SHAPE_DRAWS / 16 tiles of 16 draws a wavefront."
-    return a + "\n\n" + b + "\n\n" + occ
+    return None if a is None or b is None or occ is None else a + "\n\n" + b + "\n\n" + occ
 
 
 def instruction_table():
-    """The row loop's instruction mix per width beside k_transits'; the forward-skipped region that holds the gather (the
+    """The row loop's instruction mix per width beside the transit's; the forward-skipped region that holds the gather (the
     global loads of the two nodes) is counted apart."""
     lines = [MIX_HEAD + " the skipped block (all) |", "|---|---|---|---|---|---|---|---|"]
     per_row = {}
-    for source, mangled, label, skip in (("c2_shapes.hip", "_ZN2c25shape8k_shapesILi%dELi%dEE", "k_shapes", "global_load"),
-                                         ("c2_transit.hip", "_ZN2c27transit10k_transitsILi%dELi%dEE", "k_transits", "v_div_fmas_f64")):
-        asm = kernel_asm(source)
+    for search, skip in (("shape", "global_load"), ("transit", "v_div_fmas_f64")):
+        asm = sweep_asm(search)
         if asm is None:
             return None
         for jr, qr in ((4, 2), (8, 2), (16, 2), (32, 2)):
-            c, skipped = row_loop_mix(asm, mangled % (jr, qr), skip)
-            per_row[(label, jr)] = fp64_valu(c)
-            lines.append("| `%s<%d, %d>` | %s %d |" % (label, jr, qr, mix_cells(c), sum(skipped.values())))
-    lines += ["", "One row of one lane (one trial), the path a wavefront takes when no lane needs the skipped block: for `k_shapes` the "
-              "two node loads (entered when any lane is in an event), for `k_transits` the ramp's division.  fp64 VALU per lane-row, "
+            c, skipped = row_loop_mix(asm, sweep_symbol(search, jr, qr), skip)
+            per_row[(search, jr)] = fp64_valu(c)
+            lines.append("| `%s` | %s %d |" % (sweep_label(search, jr, qr), mix_cells(c), sum(skipped.values())))
+    lines += ["", "One row of one lane (one trial), the path a wavefront takes when no lane needs the skipped block: for the shape the "
+              "two node loads (entered when any lane is in an event), for the transit the ramp's division.  fp64 VALU per lane-row, "
               "machine-readable: " + " ".join("%s:JR%d=%d" % (k[0], k[1], v) for k, v in sorted(per_row.items()))]
     return "\n".join(lines)
 
@@ -122,28 +114,6 @@ def main():
 
         def get_celerite_matrices(self, t, diag):
             return self.m
-
-    def stats(ms):
-        ms = sorted(ms)
-        return ms[len(ms) // 2], ms[0], ms[-1]
-
-    def alternate(runs, steps):
-        """runs: name -> (fn, steps or None)."""
-        for k, (fn, n) in runs.items():
-            for _ in range(a.warmup if n is None else 1):
-                fn()
-        # events made beforehand and ONE synchronise at the end: the device never idles between steps
-        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n or steps)]
-              for k, (fn, n) in runs.items()}
-        torch.cuda.synchronize()
-        for i in range(steps):
-            for k, (fn, n) in runs.items():
-                if i < len(ev[k]):
-                    ev[k][i][0].record()
-                    fn()
-                    ev[k][i][1].record()
-        torch.cuda.synchronize()
-        return {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
 
     S = 65
     limb = sh.stack(sh.limb_darkened(0.1, 0.3, 0.4, 0.3, S)).to(dev)
@@ -224,7 +194,7 @@ def main():
         assert bool(torch.equal(torch.isnan(p1), torch.isnan(p2))) and worst < 1e4, "the two routes disagree: %g" % worst
         agree.append("%d x %d x %d x %d: %.3g (box bank bit-identical to whitened_transits: %s)" % (B, N, J, K, worst, bool(torch.equal(Tb, Tt))))
         out = alternate({"transits": (transits, None), "box": (box, None), "limb": (limb_, None), "composed": (composed, a.composed_steps)},
-                        a.steps)
+                        a.steps, a.warmup)
         for op, st in out.items():
             lines.append("| %d x %d x %d x %d | %s | %.3f (%.3f .. %.3f) | %s | %s |"
                          % (B, N, J, K, op, st[0], st[1], st[2], "%.3f" % (st[0] / out["transits"][0]) if op in ("box", "limb") else "",
@@ -261,7 +231,7 @@ def main():
                 worst = float(((q1 - q2).abs() / tol)[okk].max())
                 assert worst < 1e4, "the two routes disagree: %g" % worst
                 sig_agree.append("%d x %d: %.3g" % (B, draws, worst))
-                o2 = alternate({"projection": (projection, None), "significance": (significance, None), "loop": (loop, None)}, max(3, a.steps // 2))
+                o2 = alternate({"projection": (projection, None), "significance": (significance, None), "loop": (loop, None)}, max(3, a.steps // 2), a.warmup)
                 scaled = o2["loop"][0] * draws / a.loop_draws
                 sig_lines.append("| %d x %d x %d x %d | %d | %.3f (%.3f .. %.3f) | %.2f (%.2f .. %.2f) | %.1f | %.1f |"
                                  % (B, N, J, K, draws, *o2["projection"], *o2["significance"], scaled, scaled / o2["significance"][0]))

@@ -35,11 +35,11 @@ KINDS = ("periodogram", "transit", "keplerian")
 
 
 def registers():
-    table = register_table("c2_trial_project.o", "c2::project::", "k_project")
+    table = register_table("c2_trial_project.o")
     if table is None:
         return None
     # (register_table's closing line describes the sweeps' template parameters: this kernel has its own)
-    return table.rsplit("\n\n", 1)[0] + "\n\n`k_project<KIND, NQ>`: KIND 0 the sinusoid, 1 the transit, 2 the Keplerian; NQ = RB / 16 " \
+    return table.rsplit("\n\n", 1)[0] + "\n\n`k_project<Column, NQ>`: Column the kind's column source (csrc/c2_trial_columns.hpp); NQ = RB / 16 " \
         "tiles of 16 draws a wavefront.  No scratch and no spilled register at any instantiation."
 
 

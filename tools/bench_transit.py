@@ -27,7 +27,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from trial_static import MIX_HEAD, fp64_valu, kept_block, kernel_asm, mix_cells, register_table, row_loop_mix, with_block  # noqa: E402
+from trial_static import MIX_HEAD, alternate, fp64_valu, kept_block, mix_cells, row_loop_mix, sweep_asm, sweep_label, sweep_registers, sweep_symbol, with_block  # noqa: E402
 
 FP64_PEAK = 78.6e12 / 2.0   # fp64 VALU instructions per lane and second
 SHAPES = [(64, 4096, 8, 4096), (1, 4096, 8, 4096), (1024, 1024, 4, 1024), (64, 4096, 32, 512)]
@@ -38,16 +38,16 @@ TOOL = "tools/bench_transit.py --static-only"
 def instruction_table():
     """The row loop's instruction mix per width; the forward-skipped region that holds the ramp's division (v_div_fmas_f64)
     is counted apart."""
-    asm = kernel_asm("c2_transit.hip")
+    asm = sweep_asm("transit")
     if asm is None:
         return None
     lines = [MIX_HEAD + " the ramp's block (fp64 VALU / all) |", "|---|---|---|---|---|---|---|---|"]
     per_row = {}
     for jr, qr in ((4, 2), (8, 2), (16, 2), (32, 2), (8, 1), (8, 8)):
-        c, ramp = row_loop_mix(asm, "_ZN2c27transit10k_transitsILi%dELi%dEE" % (jr, qr), "v_div_fmas_f64")
+        c, ramp = row_loop_mix(asm, sweep_symbol("transit", jr, qr), "v_div_fmas_f64")
         if qr == 2:
             per_row[jr] = fp64_valu(c)
-        lines.append("| `k_transits<%d, %d>` | %s %d / %d |" % (jr, qr, mix_cells(c), fp64_valu(ramp), sum(ramp.values())))
+        lines.append("| `%s` | %s %d / %d |" % (sweep_label("transit", jr, qr), mix_cells(c), fp64_valu(ramp), sum(ramp.values())))
     lines += ["", "One row of one lane (one trial), the path a wavefront takes when no lane is on an ingress or egress (box trials "
               "always); the last column is the block with the ramp's division, entered by a wavefront with at least one such lane.  "
               "fp64 VALU per lane-row, machine-readable: " + " ".join("JR%d=%d" % kv for kv in sorted(per_row.items()))]
@@ -65,7 +65,7 @@ def main():
     a = ap.parse_args()
     old = open(a.out).read() if a.out and os.path.exists(a.out) else ""
     if a.static_only:
-        text = with_block(old, "registers", register_table("c2_transit.o", "c2::transit::", "k_transits"), TOOL)
+        text = with_block(old, "registers", sweep_registers("transit"), TOOL)
         text = with_block(text, "instructions", instruction_table(), TOOL)
         if a.out:
             open(a.out, "w").write(text)
@@ -78,28 +78,6 @@ def main():
     assert torch.cuda.is_available(), "this measures the GPU: there is nothing to fall back to"
     dev = torch.device("cuda:0")
     per_row = dict((int(k), int(v)) for k, v in re.findall(r"JR(\d+)=(\d+)", kept_block(old, "instructions", TOOL) or ""))
-
-    def stats(ms):
-        ms = sorted(ms)
-        return ms[len(ms) // 2], ms[0], ms[-1]
-
-    def alternate(runs, steps):
-        """runs: name -> (fn, steps or None)."""
-        for k, (fn, n) in runs.items():
-            for _ in range(a.warmup if n is None else 1):
-                fn()
-        # events made beforehand and ONE synchronise at the end: the device never idles between steps
-        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n or steps)]
-              for k, (fn, n) in runs.items()}
-        torch.cuda.synchronize()
-        for i in range(steps):
-            for k, (fn, n) in runs.items():
-                if i < len(ev[k]):
-                    ev[k][i][0].record()
-                    fn()
-                    ev[k][i][1].record()
-        torch.cuda.synchronize()
-        return {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
 
     lines = ["# gp.transit_search's route beside ops.whitened_gram in chunks of %d trials" % CHUNK, "",
              "One process, steps alternating between the routes, %d timed steps each (composed: %d) after %d warm-up steps "
@@ -174,7 +152,7 @@ def main():
             agree.append("%d x %d x %d x %d: %.3g (%d series not factored, %d trials NaN in each)"
                          % (B, N, J, K, worst, int((~ok).sum()), int(torch.isnan(p1[ok]).sum())))
             runs["composed"] = (composed, a.composed_steps)
-        out = alternate(runs, a.steps)
+        out = alternate(runs, a.steps, a.warmup)
         jr = 4 if J <= 4 else 8 if J <= 8 else 16 if J <= 16 else 32
         lane_rows = B * N * K
         for op, st in out.items():

@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
-"""The static tables of the one-lane-per-trial sweeps (csrc/c2_periodogram.hip, csrc/c2_transit.hip, csrc/c2_kepler.hip), shared
-by tools/bench_periodogram.py, tools/bench_transit.py and tools/bench_kepler.py: the register table from the built objects, the row loop's instruction
-mix from the compiler's assembly, and the marked blocks of a profile that hold them.  No GPU."""
+"""The static tables of the one-lane-per-trial sweep (trial::k_trial_sweep<Column, JR, QR>, csrc/c2_trial_sweep.hpp, instantiated
+by csrc/c2_periodogram.hip, c2_transit.hip, c2_kepler.hip and c2_shapes.hip), shared by tools/bench_periodogram.py,
+tools/bench_transit.py, tools/bench_kepler.py and tools/bench_shapes.py: the register table from the built objects, the row
+loop's instruction mix from the compiler's assembly, and the marked blocks of a profile that hold them.  No GPU."""
 import collections
 import os
 import re
@@ -12,6 +13,29 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 TITLES = {"registers": "Registers (gfx950, from the built objects)", "instructions": "The row loop (gfx950, from the compiler's assembly)"}
+
+
+# search -> (the source that instantiates the sweep for it, its column source of csrc/c2_trial_columns.hpp)
+SWEEPS = {"periodogram": ("c2_periodogram", "Sinusoid"), "transit": ("c2_transit", "Transit"), "keplerian": ("c2_kepler", "Keplerian"),
+          "shape": ("c2_shapes", "Shape")}
+
+
+def sweep_label(search, jr, qr):
+    return "k_trial_sweep<%s, %d, %d>" % (SWEEPS[search][1], jr, qr)
+
+
+def sweep_symbol(search, jr, qr):
+    """The mangled name of c2::trial::k_trial_sweep<c2::trial::<Column>, jr, qr>, up to its arguments."""
+    column = SWEEPS[search][1]
+    return "_ZN2c25trial13k_trial_sweepINS0_%d%sELi%dELi%dEE" % (len(column), column, jr, qr)
+
+
+def sweep_asm(search):
+    return kernel_asm(SWEEPS[search][0] + ".hip")
+
+
+def sweep_registers(search, note=""):
+    return register_table(SWEEPS[search][0] + ".o", " (`k_trial_sweep<Column, JR, QR>`: J rounded up to 4, 8, 16 or 32, Q0 to 1, 2, 4 or 8)." + note)
 
 
 def marks(key, tool):
@@ -34,21 +58,30 @@ def kept_block(text, key, tool):
     return text.split(begin, 1)[1].split(end, 1)[0].strip("\n") if begin in text and end in text else None
 
 
-def register_table(obj, namespace, kernel, note=""):
-    """The registers, LDS and scratch of every kernel of the built object `obj`, e.g. ("c2_transit.o", "c2::transit::",
-    "k_transits"); None where the objects are not on this machine."""
+def sorted_rows(obj, kernel=""):
+    """kernel_regs.kernel_rows of the built object `obj` whose name holds `kernel`, by their last two template arguments."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from kernel_regs import kernel_rows
 
-    rows = kernel_rows(obj)
+    return sorted((r for r in kernel_rows(obj) if kernel in r[1]), key=lambda r: [int(v) for v in re.findall(r"\d+", re.sub(r"\(.*", "", r[1]))[-2:]])
+
+
+def short_name(name):
+    """A demangled kernel name without its arguments, `void` and the project's namespaces."""
+    return re.sub(r"c2::\w+::", "", re.sub(r"\(.*", "", name).replace("void ", ""))
+
+
+def register_table(obj, note=".", kernel=""):
+    """The registers, LDS and scratch of every kernel of the built object `obj`, e.g. "c2_trial_project.o", whose name holds
+    `kernel`; None where the objects are not on this machine."""
+    rows = sorted_rows(obj, kernel)
     if not rows:
         return None
     lines = ["| kernel | registers (of them accumulation) | SGPRs | LDS bytes | scratch bytes | spilled registers |", "|---|---|---|---|---|---|"]
-    for _, name, vg, ag, scratch, lds, spill, sg in sorted(rows, key=lambda r: [int(v) for v in re.findall(r"\d+", re.sub(r"\(.*", "", r[1]))[-2:]]):
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace(namespace, "")
-        lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (name, vg, ag, sg, lds, scratch, spill))
-    lines += ["", "Largest scratch %d bytes, %d spilled registers over %d kernels (`%s<JR, QR>`: J rounded up to 4, 8, 16 "
-              "or 32, Q0 to 1, 2, 4 or 8).%s" % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows), kernel, note)]
+    for _, name, vg, ag, scratch, lds, spill, sg in rows:
+        lines.append("| `%s` | %d (%d) | %d | %d | %d | %d |" % (short_name(name), vg, ag, sg, lds, scratch, spill))
+    lines += ["", "Largest scratch %d bytes, %d spilled registers over %d kernels%s"
+              % (max(r[4] for r in rows), max(r[6] for r in rows), len(rows), note)]
     return "\n".join(lines)
 
 
@@ -113,3 +146,30 @@ def mix_cells(c):
         sum(c.values()), sum(f64.values()), fma, mul, add, sum(f64.values()) - fma - mul - add, valu - sum(f64.values()),
         c.get("ds_read_b128", 0), c.get("ds_read_b64", 0), lds - c.get("ds_read_b128", 0) - c.get("ds_read_b64", 0),
         sum(v for k, v in c.items() if k.startswith("s_")))
+
+
+def stats(ms):
+    ms = sorted(ms)
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
+def alternate(runs, steps, warmup):
+    """{name: (median, min, max) ms} of the functions `runs`: name -> (fn, its own number of steps or None for `steps`), step by
+    step in turn, every step timed by its own pair of HIP events after `warmup` calls (one for a run with its own count)."""
+    import torch
+
+    for k, (fn, n) in runs.items():
+        for _ in range(warmup if n is None else 1):
+            fn()
+    # events made beforehand and ONE synchronise at the end: the device never idles between steps
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n or steps)]
+          for k, (fn, n) in runs.items()}
+    torch.cuda.synchronize()
+    for i in range(steps):
+        for k, (fn, n) in runs.items():
+            if i < len(ev[k]):
+                ev[k][i][0].record()
+                fn()
+                ev[k][i][1].record()
+    torch.cuda.synchronize()
+    return {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
