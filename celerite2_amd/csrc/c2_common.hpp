@@ -11,7 +11,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <mutex>
 
 namespace c2 {
 
@@ -70,36 +69,6 @@ template <int G>
 __device__ __forceinline__ double gget(double x, int i) {
   if constexpr (G == 1) return x;
   return __shfl(x, i, G);
-}
-
-// Stream-ordered temporaries of the library.  They come from a memory pool the LIBRARY owns (one per device, created on
-// first use, release threshold 1 GiB so that up to that much stays cached between calls: the default pool hands its memory
-// back to the driver at every synchronisation and each call would pay a fresh allocation -- 0.2 ms for the 17 MB of a
-// 64 x 4096 x 64 many-rhs solve that itself takes 0.4 ms).  The device's DEFAULT pool, which the process shares with
-// everybody else, is left as it is; if the pool cannot be created the temporaries fall back to it, uncached.  Thread-safe
-// (std::call_once per device); hipFreeAsync releases either kind.
-inline hipError_t temp_alloc(void **p, size_t bytes, hipStream_t s) {
-  constexpr int kMaxDev = 64;
-  static std::once_flag once[kMaxDev];
-  static hipMemPool_t pools[kMaxDev] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return hipMallocAsync(p, bytes, s);
-  std::call_once(once[dev], [dev] {
-    hipMemPoolProps props = {};
-    props.allocType = hipMemAllocationTypePinned;
-    props.handleTypes = hipMemHandleTypeNone;
-    props.location.type = hipMemLocationTypeDevice;
-    props.location.id = dev;
-    hipMemPool_t pool = nullptr;
-    if (hipMemPoolCreate(&pool, &props) == hipSuccess && pool) {
-      uint64_t keep = 1ull << 30;
-      (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-      pools[dev] = pool;
-    }
-    (void)hipGetLastError();
-  });
-  if (pools[dev]) return hipMallocFromPoolAsync(p, bytes, pools[dev], s);
-  return hipMallocAsync(p, bytes, s);
 }
 
 // Group-size dispatch: G = next power of two >= J.

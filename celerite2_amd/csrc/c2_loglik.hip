@@ -28,6 +28,7 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
 #include "c2_launch.hpp"
+#include "c2_plan.hpp"
 
 #ifdef C2_REV_TIMING
 __device__ unsigned long long c2_dbg[8];
@@ -1264,8 +1265,6 @@ static bool use_lanes4(int64_t B, int64_t J, bool grad) {
 // wavefront on every SIMD.  Measured on MI355X at N = 4096 (profiles/r02_lane_mappings.md): the forward-only kernel
 // wins from 24576 series up (3.3 vs 4.1 ms; 6.7 vs 10.4 ms at 65536), the gradient pair from 24576 up as well (15.7 vs
 // 16.0 ms; 17.2 vs 21.6 ms at 32768; 28.2 vs 41.8 ms at 65536).  C2_LANES=1 forces it.
-// guard words in front of the records of the one-lane path: the head + one per wavefront, rounded to 16 bytes
-static size_t lanes1_gate_words(int64_t B) { return (size_t)((kGateHeadWords + (B + kWave - 1) / kWave + 1) & ~(int64_t)1); }
 // Two lanes per series (c2_loglik_k2.hip, J == 8): 32 series per wavefront -- the batches that
 // give the one-lane mapping half a chip.  C2_LANES=2 forces it.
 static bool use_lanes2(int64_t B, int64_t N, int64_t J, bool grad) {
@@ -1451,6 +1450,40 @@ static bool use_lanes1(int64_t B, int64_t J, bool grad) {
   return B >= opt::ival(grad ? opt::k_lanes1_min_batch_grad : opt::k_lanes1_min_batch_fwd);
 }
 
+// The backward-recursion form serves the group mappings up to eight lanes.  Sixteen lanes (C = 4) measured on the bench's
+// recipe at N = 4096: J = 16 every wavefront beyond the guard (the replay sweep answers: 8.0 ms either way), J = 12 re-anchored at
+// every segment 8.9 -> 13.7 ms, J = 10 8.9 -> 7.3 -- not a gain one can count on; left on the replay.  C2_LOGLIK_BACK=0 keeps the replay (A/B runs).
+static bool use_back(int64_t N, int64_t J) {
+  if (opt::off(opt::k_loglik_back)) return false;
+  return group_size(J) <= 8 && N >= 2;
+}
+
+// THE PLAN, first half: which kernel family serves a call (c2_plan.hpp).  The two precedences side by side; nothing else
+// asks use_lanes1 / 2 / 4.
+//   gradient: time-parallel (if the entry point allows it) > four lanes (arrays on 16-byte boundaries only: the pair moves U,
+//             V, bU, bV, bc and its records as double2, the C ABI promises 8 bytes) > two > one > group, its reverse sweep by
+//             the backward recursion > by replay
+//   forward:  two > one > four > time-parallel in one pass > Newton iterations (both take a stream-ordered temporary:
+//             allow_timepar = not while capturing) > group
+static Lanes lane_mapping(int64_t B, int64_t N, int64_t J, bool grad, bool aligned16, bool allow_timepar) {
+  if (J > C2_FAST_WIDTH) return Lanes::wide;
+  if (grad) {
+    if (allow_timepar && use_timepar_grad(B, N, J)) return Lanes::timepar;
+    if (aligned16 && use_lanes4(B, J, true)) return Lanes::four;
+    if (use_lanes2(B, N, J, true)) return Lanes::two;
+    if (use_lanes1(B, J, true)) return Lanes::one;
+    return use_back(N, J) ? Lanes::group : Lanes::replay;
+  }
+  if (use_lanes2(B, N, J, false)) return Lanes::two;
+  if (use_lanes1(B, J, false)) return Lanes::one;
+  if (use_lanes4(B, J, false)) return Lanes::four;
+  // widths 8, 4 and 2 in one pass (chunk elements combined in a tree: c2_timepar.hip) whatever the length; the Newton
+  // iterations are for the other widths
+  if (allow_timepar && use_timepar(B, N, J, true)) return Lanes::timepar;
+  if (allow_timepar && use_factor_iter(B, N, J)) return Lanes::newton;
+  return Lanes::group;
+}
+
 // wide models (c2_wide.hip; C2_FAST_WIDTH < J <= C2_MAX_WIDTH): the log-likelihood from factor + solve_lower + a reduction, its
 // gradient as the literal op chain of c2_fused.hip over the wide kernels, failed series filled with NaN afterwards
 
@@ -1462,47 +1495,36 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
   if (B < 1 || N < 1 || J < 1) return C2_ERR_INVALID;
   if (J > C2_MAX_WIDTH) return C2_ERR_UNSUPPORTED;
   if (!t || !c || !a || !U || !V || !y || !ll || !flag) return C2_ERR_INVALID;
-  if (J > C2_FAST_WIDTH) {   // a wide model: factor + solve_lower + reduction on the workgroup-per-series kernels
-    hipStream_t ws = (hipStream_t)stream;
-    hipStreamCaptureStatus wcap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(ws, &wcap);
-    if (wcap != hipStreamCaptureStatusNone) {   // its temporary is a stream-ordered allocation: not inside a graph capture
-      c2_internal_set_error("c2_loglik at J > 32 allocates a temporary and cannot be captured in a HIP graph; c2_loglik_grad takes a caller workspace");
-      return C2_ERR_UNSUPPORTED;
-    }
-    void *tmp = nullptr;
-    if (int e = hip_check(c2::temp_alloc(&tmp, c2_wide_loglik_doubles(B, N, J) * sizeof(double), ws))) return e;
-    int rc = c2_wide_loglik(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
-    rc = keep_first(rc, hipFreeAsync(tmp, ws));
-    return rc;
-  }
-  if (use_lanes2(B, N, J, false)) return c2_internal_loglik_k2(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
-  if (use_lanes1(B, J, false)) {
-    if (J == 8) return c2_internal_loglik_t8(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
-    if (J == 6) return c2_internal_loglik_t6(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
-    if (J == 4) return c2_internal_loglik_t4(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
-    return c2_internal_loglik_t2(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
-  }
-  if (use_lanes4(B, J, false)) return c2_internal_loglik4(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &capturing);   // (its temporary is a stream-ordered allocation: kept out of graph captures)
-  // widths 4 and 2 in one pass (chunk elements combined in a tree: c2_timepar.hip) whatever the length; the Newton
-  // iterations below are for the other widths
-  const bool onepass = (J == 8 || J == 4 || J == 2) && use_timepar(B, N, J, true);
-  if (capturing == hipStreamCaptureStatusNone && !onepass && use_factor_iter(B, N, J)) {
-    // d, W by Newton iterations on the chunk start states, z by the chunk-map solve, a reduction
-    const size_t nd = c2_internal_loglik_wide_doubles(B, N, J);
-    void *tmp = nullptr;
-    if (nd > 0 && c2::temp_alloc(&tmp, (nd + 1) * sizeof(double), s) == hipSuccess) {
+  // (the forms with a stream-ordered temporary stay out of graph captures: StreamTemp has no room there)
+  switch (lane_mapping(B, N, J, false, false, true)) {
+    case Lanes::wide: {   // factor + solve_lower + reduction on the workgroup-per-series kernels
+      StreamTemp tmp(s, c2_wide_loglik_doubles(B, N, J) * sizeof(double));
+      if (!tmp && tmp.error() == hipSuccess) {
+        c2_internal_set_error("c2_loglik at J > 32 allocates a temporary and cannot be captured in a HIP graph; c2_loglik_grad takes a caller workspace");
+        return C2_ERR_UNSUPPORTED;
+      }
+      if (!tmp) return hip_check(tmp.error());
+      return tmp.release(c2_wide_loglik(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, tmp.get(), stream));
+    }
+    case Lanes::two: return c2_internal_loglik_k2(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
+    case Lanes::one:
+      return (J == 8 ? c2_internal_loglik_t8 : J == 6 ? c2_internal_loglik_t6 : J == 4 ? c2_internal_loglik_t4 : c2_internal_loglik_t2)(
+          B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
+    case Lanes::four: return c2_internal_loglik4(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, flag, stream);
+    case Lanes::newton: {
+      // d, W by Newton iterations on the chunk start states, z by the chunk-map solve, a reduction
+      const size_t nd = c2_internal_loglik_wide_doubles(B, N, J);
+      StreamTemp tmp(s, nd ? (nd + 1) * sizeof(double) : 0);
+      if (!tmp) break;
       // That form composes c2_factor -- which hands a batch with a failed or NaN pivot to the row-by-row factor on its own --
       // with the chunk-map solve: its healthy series would then carry the bits of neither formulation.  Behind a series
       // that failed (flag != 0: an ordinary non positive definite matrix as much as a NaN -- c2_factor has fallen back for
       // the batch there already) or whose value is not finite, the row-by-row kernel recomputes the batch: k_ll_guard opens
       // its gate.  A healthy batch pays the two launches (the gated kernel returns at once).
-      unsigned long long *guard = (unsigned long long *)((double *)tmp + nd);
+      unsigned long long *guard = (unsigned long long *)(tmp.get() + nd);
       int rc = hip_check(hipMemsetAsync(guard, 0, sizeof(unsigned long long), s));
-      if (rc == C2_OK) rc = c2_internal_loglik_wide(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp, stream);
+      if (rc == C2_OK) rc = c2_internal_loglik_wide(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, tmp.get(), stream);
       if (rc == C2_OK && verify_fallback_enabled()) {
         hipLaunchKernelGGL(k_ll_guard, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const double *)ll,
                            (const int32_t *)flag, guard);
@@ -1510,26 +1532,22 @@ int c2_loglik(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, co
         if (rc == C2_OK)
           rc = launch_fwd<0>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, nullptr, 0, nullptr, nullptr, s, guard);
       }
-      rc = keep_first(rc, hipFreeAsync(tmp, s));
-      return rc;
+      return tmp.release(rc);
     }
-    (void)hipGetLastError();
-  }
-  if (capturing == hipStreamCaptureStatusNone && use_timepar(B, N, J, true)) {
-    // Small batch of long series: parallel along time (c2_timepar.hip), verified on the device; the ordinary kernel
-    // below runs behind the verification word and does nothing unless it failed.  Scratch is a stream-ordered
-    // temporary; without it (allocation refused) the ordinary kernel runs alone.
-    const size_t nd = c2_internal_loglik_timepar_doubles(B, N, J);
-    void *tmp = nullptr;
-    if (nd > 0 && c2::temp_alloc(&tmp, (nd + 2) * sizeof(double), s) == hipSuccess) {
-      unsigned long long *guard = (unsigned long long *)tmp;
-      int rc = c2_internal_loglik_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, (double *)tmp + 2, guard, stream);
+    case Lanes::timepar: {
+      // Small batch of long series: parallel along time (c2_timepar.hip), verified on the device; the ordinary kernel
+      // below runs behind the verification word and does nothing unless it failed.  Without room for its scratch the
+      // ordinary kernel runs alone.
+      const size_t nd = c2_internal_loglik_timepar_doubles(B, N, J);
+      StreamTemp tmp(s, nd ? (nd + 2) * sizeof(double) : 0);
+      if (!tmp) break;
+      unsigned long long *guard = (unsigned long long *)tmp.get();
+      int rc = c2_internal_loglik_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, tmp.get() + 2, guard, stream);
       if (rc == C2_OK)
         rc = launch_fwd<0>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, nullptr, 0, nullptr, nullptr, s, guard + 1);
-      rc = keep_first(rc, hipFreeAsync(tmp, s));
-      return rc;
+      return tmp.release(rc);
     }
-    (void)hipGetLastError();
+    default: break;
   }
   return launch_fwd<0>(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, flag, nullptr, 0, nullptr, nullptr, s);
 }
@@ -1556,9 +1574,6 @@ static inline GradWs grad_ws(int64_t B, int64_t N, int64_t J, bool back = false)
   g.total = g.ck + g.w + g.dz + g.guard;
   return g;
 }
-// The backward-recursion form serves the group mappings up to eight lanes.  Sixteen lanes (C = 4) measured on the bench's
-// recipe at N = 4096: J = 16 every wavefront beyond the guard (the replay sweep answers: 8.0 ms either way), J = 12 re-anchored at
-// every segment 8.9 -> 13.7 ms, J = 10 8.9 -> 7.3 -- not a gain one can count on; left on the replay.  C2_LOGLIK_BACK=0 keeps the replay (A/B runs).
 static int64_t simd_count() {
   static int64_t n = 0;
   if (n == 0) {
@@ -1569,10 +1584,6 @@ static int64_t simd_count() {
   }
   return n;
 }
-static bool use_back(int64_t N, int64_t J) {
-  if (opt::off(opt::k_loglik_back)) return false;
-  return group_size(J) <= 8 && N >= 2;
-}
 
 // core::factor without the S workspace (interface.hpp:37-48) on the fused forward kernel: d and W straight
 // into the caller's arrays (d == a and W == V allowed: every row is read blocks ahead of the row being written).
@@ -1580,7 +1591,7 @@ static bool use_back(int64_t N, int64_t J) {
 // scanned chunk elements at widths 4 / 2 (start states exact to rounding) and the Newton iterations at the other widths
 // (1 .. 8), the row-by-row kernel below that
 // `scratch` (nullable; c2_internal_factor_scratch_doubles): caller-provided room for the time-parallel forms -- without it
-// they use a stream-ordered temporary and stay out of graph captures.
+// they use a stream-ordered temporary and stay out of graph captures (StreamTemp); without room, row by row.
 size_t c2_internal_factor_scratch_doubles(int64_t B, int64_t N, int64_t J) {
   const size_t n1 = c2_internal_factor_iter_doubles(B, N, J), n2 = c2_internal_timepar_doubles(B, N, J) + 2;
   return ((n1 > n2 ? n1 : n2) + 1) & ~(size_t)1;
@@ -1589,17 +1600,6 @@ int c2_internal_factor_fused_ws(int64_t B, int64_t N, int64_t J, const double *t
                                 int64_t c_bs, const double *a, const double *U, const double *V, double *d, double *W,
                                 int32_t *flag, int allow_timepar, double *scratch, c2_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &capturing);
-  const bool may_alloc = capturing == hipStreamCaptureStatusNone;
-  auto room = [&](size_t nd, void **tmp) {   // the caller's scratch, else a stream-ordered temporary
-    if (scratch) { *tmp = scratch; return true; }
-    return may_alloc && c2::temp_alloc(tmp, nd * sizeof(double), s) == hipSuccess;
-  };
-  auto release = [&](void *tmp, int rc) {
-    if (!scratch) rc = keep_first(rc, hipFreeAsync(tmp, s));
-    return rc;
-  };
   // allow_timepar == 2 (the time-parallel gradient builds on d, W): the time-parallel forms from 2048 rows (Newton forced:
   // every length), the row-by-row kernel below that (0.15 us per row against several launches)
   const bool forced_iter = opt::has(opt::k_factor_iter) && opt::ival(opt::k_factor_iter) != 0;
@@ -1620,34 +1620,31 @@ int c2_internal_factor_fused_ws(int64_t B, int64_t N, int64_t J, const double *t
     newton = scan_ms < rows_ms;
   }
   if (allow_timepar && d != a && W != V && newton) {
-    const size_t nd = c2_internal_factor_iter_doubles(B, N, J);
-    void *tmp = nullptr;
-    if (nd > 0 && room(nd, &tmp)) {
+    StreamTemp tmp(s, c2_internal_factor_iter_doubles(B, N, J) * sizeof(double), scratch);
+    if (tmp) {
       const unsigned long long *last = nullptr;
-      int rc = c2_internal_factor_iter(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, (double *)tmp, &last, stream);
+      int rc = c2_internal_factor_iter(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, tmp.get(), &last, stream);
       if (rc == C2_OK && c2_internal_get_debug_sink())   // diagnostics: the iterations' / the scan's words (tools/e8_words.py)
-        (void)hipMemcpyAsync(c2_internal_get_debug_sink() + 8, tmp, 30 * sizeof(double), hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(c2_internal_get_debug_sink() + 8, tmp.get(), 30 * sizeof(double), hipMemcpyDeviceToDevice, s);
       if (rc == C2_OK)
         rc = launch_fwd<2>(B, N, J, t, t_bs, c, c_bs, a, U, V, a, nullptr, flag, nullptr, 0, W,
                            reinterpret_cast<double2 *>(d), s, last);
-      return release(tmp, rc);
+      return tmp.release(rc);
     }
-    (void)hipGetLastError();
   }
   // small batch of long series, out of place: parallel along time, verified, the row-by-row kernel gated behind it
   // (in place -- d == a or W == V -- stays row by row: the fallback would read what the time-parallel pass overwrote)
   if (allow_timepar && d != a && W != V && scan_widths && use_timepar(B, N, J)) {
     const size_t nd = c2_internal_timepar_doubles(B, N, J);
-    void *tmp = nullptr;
-    if (nd > 0 && room(nd + 2, &tmp)) {
-      unsigned long long *guard = (unsigned long long *)tmp;
-      int rc = c2_internal_factor_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, (double *)tmp + 2, guard, stream);
+    StreamTemp tmp(s, nd ? (nd + 2) * sizeof(double) : 0, scratch);
+    if (tmp) {
+      unsigned long long *guard = (unsigned long long *)tmp.get();
+      int rc = c2_internal_factor_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, tmp.get() + 2, guard, stream);
       if (rc == C2_OK)
         rc = launch_fwd<2>(B, N, J, t, t_bs, c, c_bs, a, U, V, a, nullptr, flag, nullptr, 0, W,
                            reinterpret_cast<double2 *>(d), s, guard);
-      return release(tmp, rc);
+      return tmp.release(rc);
     }
-    (void)hipGetLastError();
   }
   return launch_fwd<2>(B, N, J, t, t_bs, c, c_bs, a, U, V, /*y (unused: any readable (B,N) array)*/ a, nullptr, flag,
                        nullptr, 0, W, reinterpret_cast<double2 *>(d), (hipStream_t)stream);
@@ -1679,25 +1676,17 @@ extern "C" int c2_internal_factor_rev_long(int64_t B, int64_t N, int64_t J, cons
   if (J < 1 || J > 8 || !drop_in_long_shape(B, N)) return C2_ERR_UNSUPPORTED;
   if (opt::off(opt::k_timepar_grad)) return C2_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &capturing);
-  if (capturing != hipStreamCaptureStatusNone) return C2_ERR_UNSUPPORTED;   // a stream-ordered temporary below
-  const size_t nd = C2_TPG_PICK(c2_internal_factor_rev_timepar_doubles)(B, N, J);
-  void *tmp = nullptr;
-  if (nd == 0 || c2::temp_alloc(&tmp, nd * sizeof(double), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return C2_ERR_UNSUPPORTED;
-  }
+  StreamTemp tmp(s, C2_TPG_PICK(c2_internal_factor_rev_timepar_doubles)(B, N, J) * sizeof(double));
+  if (!tmp) return C2_ERR_UNSUPPORTED;   // (not this shape, inside a graph capture, allocation refused)
   int rc = C2_TPG_PICK(c2_internal_factor_rev_timepar)(B, N, J, t, t_bs, c, c_bs, U, U, d, W, bd, bW, bt, bc, ba, bU, bV,
-                                                       (double *)tmp, stream);
+                                                       tmp.get(), stream);
   // verified on the device (word 0 of the scratch, c2_timepar_grad.hip): should the chunk boundaries disagree, the
   // segment-replay kernel -- behind that word, empty otherwise -- recomputes the batch from the caller's S rows
   if (rc == C2_OK && verify_fallback_enabled())
     rc = c2_internal_factor_rev_replay(B, N, J, t, t_bs, c, c_bs, U, d, W, S, bd, bW, bt, bc, ba, bU, bV,
-                                       (const unsigned long long *)tmp, stream);
-  c2_internal_debug_capture((const double *)tmp, nullptr, s);
-  rc = keep_first(rc, hipFreeAsync(tmp, s));
-  return rc;
+                                       (const unsigned long long *)tmp.get(), stream);
+  c2_internal_debug_capture(tmp.get(), nullptr, s);
+  return tmp.release(rc);
 }
 // factor WITH the S workspace of the drop-in on a small batch of long series (widths 1 .. 8): d, W by the Newton iterations
 // on the chunk start states, then the S rows -- a linear recurrence once d, W are known -- by chunks (k_s_rows of
@@ -1708,21 +1697,12 @@ extern "C" int c2_internal_factor_states_timepar(int64_t B, int64_t N, int64_t J
                                                  c2_stream_t stream) {
   if (J < 1 || J > 8 || !drop_in_long_shape(B, N) || d == a || W == V) return C2_ERR_UNSUPPORTED;
   if (opt::off(opt::k_factor_iter)) return C2_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &capturing);
-  if (capturing != hipStreamCaptureStatusNone) return C2_ERR_UNSUPPORTED;   // stream-ordered temporaries below
-  const size_t nd = C2_TPG_PICK(c2_internal_s_rows_doubles)(B, N, J);
-  void *tmp = nullptr;
-  if (nd == 0 || c2::temp_alloc(&tmp, nd * sizeof(double), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return C2_ERR_UNSUPPORTED;
-  }
+  StreamTemp tmp((hipStream_t)stream, C2_TPG_PICK(c2_internal_s_rows_doubles)(B, N, J) * sizeof(double));
+  if (!tmp) return C2_ERR_UNSUPPORTED;   // (not this shape, inside a graph capture, allocation refused)
   int rc = c2_internal_factor_fused_ws(B, N, J, t, t_bs, c, c_bs, a, U, V, d, W, flag, /*Newton iterations*/ 2, nullptr, stream);
   if (rc == C2_OK)
-    rc = C2_TPG_PICK(c2_internal_s_rows)(B, N, J, t, t_bs, c, c_bs, d, W, flag, S, (double *)tmp, stream);
-  rc = keep_first(rc, hipFreeAsync(tmp, s));
-  return rc;
+    rc = C2_TPG_PICK(c2_internal_s_rows)(B, N, J, t, t_bs, c, c_bs, d, W, flag, S, tmp.get(), stream);
+  return tmp.release(rc);
 }
 
 
@@ -1736,33 +1716,53 @@ int c2_internal_anchor_spans(int64_t B, int64_t N, int64_t J, int C, int spw, co
   return launch_ok();
 }
 
-// what the row-by-row forms of loglik_grad_impl take (doubles; J <= C2_FAST_WIDTH)
-static size_t grad_rows_doubles(int64_t B, int64_t N, int64_t J) {
-  size_t n = grad_ws(B, N, J, use_back(N, J)).total;
-  if (use_lanes4(B, J, true)) {   // [guard words] [records of the four-lane pair | workspace of the replay fallback]
-    const size_t r = c2_internal_loglik_q4_record_doubles(B, N), f = grad_ws(B, N, J).total;
-    const size_t n4 = lanes1_gate_words(B) + (r > f ? r : f);
-    n = n4 > n ? n4 : n;   // (arrays off a 16-byte boundary take the eight-lane pair on the same workspace)
+// THE PLAN, second half: where a mapping of the gradient keeps what in the caller's workspace (offsets in doubles).
+//   one / two / four lanes   [gate words][records of the pair | workspace of the replay pair, gated per group of 64 series]
+//   time-parallel            [verification words ... its scratch | 8 words, then the workspace of the gated replay pair]
+//   group, replay            [grad_ws(back) / grad_ws(): checkpoints, W records, (d, z), span words]
+//   wide                     [the op chain's d, W, S, z, F, seeds]
+// `|`: overlaid -- nobody reads the records any more when the fallback writes.  need: the end of the last region the
+// mapping or its gated fallback can write.
+struct GradLayout {
+  size_t words;      // gate / verification words: where (always in front) ...
+  size_t n_words;    // ... and how many
+  size_t records;    // what the mapping's own kernels write
+  size_t fallback;   // workspace of the gated replay pair
+  size_t need;
+};
+static GradLayout grad_layout(Lanes m, int64_t B, int64_t N, int64_t J) {
+  GradLayout L{};
+  size_t r = 0;
+  switch (m) {
+    case Lanes::wide: L.need = c2_loglik_grad_composite_workspace_bytes(B, N, J) / sizeof(double); return L;
+    case Lanes::group: L.need = grad_ws(B, N, J, true).total; return L;
+    case Lanes::replay: L.need = grad_ws(B, N, J).total; return L;
+    case Lanes::timepar: L.n_words = kTimeparVerifyWords; L.records = 0; r = c2_internal_timepar_grad_doubles(B, N, J); break;
+    case Lanes::four: L.n_words = gate_words(B); L.records = L.n_words; r = c2_internal_loglik_q4_record_doubles(B, N); break;
+    case Lanes::two: L.n_words = gate_words(B); L.records = L.n_words; r = c2_internal_loglik_k2_record_doubles(B, N); break;
+    default: L.n_words = gate_words(B); L.records = L.n_words; r = lanes1_record_doubles(B, N, J); break;   // Lanes::one
   }
-  if (use_lanes1(B, J, true)) {  // [guard words: head + one per wavefront] [records of the one-lane path | workspace of the replay fallback]
-    const size_t r = lanes1_record_doubles(B, N, J), f = grad_ws(B, N, J).total;
-    n = lanes1_gate_words(B) + (r > f ? r : f);
-  }
-  if (use_lanes2(B, N, J, true)) {  // the same layout with the records of the two-lane path
-    const size_t f = grad_ws(B, N, J).total, r = c2_internal_loglik_k2_record_doubles(B, N);
-    n = lanes1_gate_words(B) + (r > f ? r : f);
-  }
-  return n;
+  L.fallback = L.n_words;
+  L.need = max2(L.records + r, L.fallback + grad_ws(B, N, J).total);
+  return L;
+}
+// the largest need over the mappings the dispatcher can reach for this shape under the current options: either alignment
+static size_t grad_need(int64_t B, int64_t N, int64_t J, bool allow_timepar) {
+  return max2(grad_layout(lane_mapping(B, N, J, true, false, allow_timepar), B, N, J).need,
+              grad_layout(lane_mapping(B, N, J, true, true, allow_timepar), B, N, J).need);
 }
 size_t c2_loglik_grad_workspace_bytes(int64_t B, int64_t N, int64_t J) {
   if (B < 1 || N < 1 || J < 1 || J > C2_MAX_WIDTH) return 0;
-  if (J > C2_FAST_WIDTH) return c2_loglik_grad_composite_workspace_bytes(B, N, J);   // (d, W, S, z, F, seeds: the op chain)
-  size_t n = grad_rows_doubles(B, N, J);
-  if (use_timepar_grad(B, N, J)) {   // [verification words | its scratch, or the workspace of the gated row-by-row pair]
-    const size_t r = c2_internal_timepar_grad_doubles(B, N, J), f = grad_ws(B, N, J).total + kTimeparVerifyWords;
-    n = r > f ? r : f;
-  }
-  return n * sizeof(double);
+  return grad_need(B, N, J, true) * sizeof(double);
+}
+// test hook (loaded by name): the mapping of one call and what it needs
+int c2_internal_loglik_grad_plan(int64_t B, int64_t N, int64_t J, int allow_timepar, int aligned16, int *mapping,
+                                 size_t *need_doubles) {
+  if (B < 1 || N < 1 || J < 1 || J > C2_MAX_WIDTH || !mapping || !need_doubles) return C2_ERR_INVALID;
+  const Lanes m = lane_mapping(B, N, J, true, aligned16 != 0, allow_timepar != 0);
+  *mapping = (int)m;
+  *need_doubles = grad_layout(m, B, N, J).need;
+  return C2_OK;
 }
 
 static int loglik_grad_impl(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c, int64_t c_bs,
@@ -1786,10 +1786,8 @@ int c2_loglik_grad(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_b
 // can be less than the row-by-row forms write (2 x 12000 x 4: 651268 doubles against 1248290 with the W records of the
 // backward recursion).
 size_t c2_internal_loglik_grad_rows_workspace_bytes(int64_t B, int64_t N, int64_t J) {
-  const size_t n = c2_loglik_grad_workspace_bytes(B, N, J);
-  if (n == 0 || J > C2_FAST_WIDTH) return n;
-  const size_t rows = grad_rows_doubles(B, N, J) * sizeof(double);
-  return rows > n ? rows : n;
+  if (B < 1 || N < 1 || J < 1 || J > C2_MAX_WIDTH) return 0;
+  return max2(grad_need(B, N, J, false), grad_need(B, N, J, true)) * sizeof(double);   // (never below the public size)
 }
 int c2_internal_loglik_grad_rows(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs, const double *c,
                                  int64_t c_bs, const double *a, const double *U, const double *V, const double *y,
@@ -1808,71 +1806,67 @@ static int loglik_grad_impl(int64_t B, int64_t N, int64_t J, const double *t, in
     return C2_ERR_INVALID;
   if (work_bytes < (allow_timepar ? c2_loglik_grad_workspace_bytes(B, N, J) : c2_internal_loglik_grad_rows_workspace_bytes(B, N, J)))
     return C2_ERR_INVALID;
-  if (J > C2_FAST_WIDTH) {
-    if (int e = c2_loglik_grad_composite(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work,
-                                         work_bytes, stream))
-      return e;
-    return c2_wide_nan_failed(B, N, J, flag, bt, bc, ba, bU, bV, by, stream);
-  }
-  if (allow_timepar && use_timepar_grad(B, N, J)) {   // small batch of long series: parallel along time
-    if (int e = c2_internal_loglik_grad_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
-                                                (double *)work, stream))
-      return e;
-    // ... verified on the device: word 0 of the workspace holds the worst disagreement at the chunk boundaries in units of
-    // half its tolerance (c2_timepar_grad.hip, k_verify_combine).  Beyond it the row-by-row pair below -- launched behind
-    // the word, empty otherwise -- recomputes the batch (the same outputs; its workspace overlays the scratch).
-    c2_internal_debug_capture((const double *)work, nullptr, (hipStream_t)stream);
-    if (!verify_fallback_enabled()) return C2_OK;
-    return c2_internal_loglik_grad_replay(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
-                                          (double *)work + kTimeparVerifyWords, (const unsigned long long *)work, stream);
-  }
-  const unsigned long long *gate = nullptr;
-  // (the four-lane pair moves U, V, bU, bV, bc and its records as double2: the C ABI promises 8-byte alignment only, so
-  // arrays off a 16-byte boundary -- a view starting at an odd element -- take the eight-lane pair instead)
+  hipStream_t s = (hipStream_t)stream;
   const bool aligned16 = ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(bU) |
                            reinterpret_cast<uintptr_t>(bV) | reinterpret_cast<uintptr_t>(bc) | reinterpret_cast<uintptr_t>(work)) & 15) == 0;
-  if (use_lanes4(B, J, true) && aligned16) {
-    // Four lanes per series, scaled frame.  Groups of 64 series whose anchor intervals are beyond the guard (gaps in time)
-    // are left to the replay pair below, gated per group by the words k_q4_gate leaves (decided on the device).
-    unsigned long long *guard = (unsigned long long *)work;
-    work = (double *)work + lanes1_gate_words(B);
-    if (int e = c2_internal_loglik_q4_grad(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
-                                           (double *)work, guard, stream))
-      return e;
-    gate = gate_per_wave(guard + kGateHeadWords);
-  } else if (use_lanes2(B, N, J, true)) {
-    // Two lanes per series: as below, the two wavefronts of a group of 64 series raising its guard word together
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long *guard = (unsigned long long *)work;
-    if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * lanes1_gate_words(B), s))) return e;
-    work = (double *)work + lanes1_gate_words(B);
-    if (int e = c2_internal_loglik_k2_grad(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
-                                           (double *)work, guard, stream))
-      return e;
-    gate = gate_per_wave(guard + kGateHeadWords);
-  } else if (use_lanes1(B, J, true)) {
-    hipStream_t s = (hipStream_t)stream;
-    // One lane per series: forward with records, then the backward-recursion reverse sweep.  The forward pass leaves
-    // the stability measure of every WAVEFRONT in its own guard word; where it exceeds kBackwardGuard that wavefront's
-    // reverse sweep returns at once and the replay pair below -- gated per group of 64 series by the same words --
-    // produces the gradients of those series (same outputs; its workspace overlays the records, which nobody reads any
-    // more by then; decided on the device).
-    unsigned long long *guard = (unsigned long long *)work;
-    if (int e = hip_check(hipMemsetAsync(guard, 0, 8 * kGateHeadWords, s))) return e;
-    work = (double *)work + lanes1_gate_words(B);
-    auto one_lane = J == 8 ? c2_internal_loglik_t_grad8
-                  : J == 6 ? c2_internal_loglik_t_grad6
-                  : J == 4 ? c2_internal_loglik_t_grad4 : c2_internal_loglik_t_grad2;
-    if (int e = one_lane(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, (double *)work, guard,
-                         stream))
-      return e;
-    gate = gate_per_wave(guard + kGateHeadWords);   // per group of 64 series: only the wavefronts that fell back are replayed
+  const Lanes m = lane_mapping(B, N, J, true, aligned16, allow_timepar);
+  const GradLayout L = grad_layout(m, B, N, J);
+  double *w = (double *)work, *records = w + L.records, *fallback = w + L.fallback;
+  unsigned long long *words = (unsigned long long *)(w + L.words);
+  switch (m) {
+    case Lanes::wide:
+      if (int e = c2_loglik_grad_composite(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work,
+                                           work_bytes, stream))
+        return e;
+      return c2_wide_nan_failed(B, N, J, flag, bt, bc, ba, bU, bV, by, stream);
+    case Lanes::group:   // the primary path of this batch: reverse sweep by the backward recursion
+      return loglik_grad_group(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, w, nullptr, true, stream);
+    case Lanes::replay:
+      return c2_internal_loglik_grad_replay(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, w, nullptr,
+                                            stream);
+    case Lanes::timepar:   // small batch of long series: parallel along time
+      if (int e = c2_internal_loglik_grad_timepar(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag,
+                                                  records, stream))
+        return e;
+      // ... verified on the device: word 0 of the workspace holds the worst disagreement at the chunk boundaries in units of
+      // half its tolerance (c2_timepar_grad.hip, k_verify_combine).  Beyond it the row-by-row pair -- launched behind
+      // the word, empty otherwise -- recomputes the batch (the same outputs; its workspace overlays the scratch).
+      c2_internal_debug_capture((const double *)words, nullptr, s);
+      if (!verify_fallback_enabled()) return C2_OK;
+      return c2_internal_loglik_grad_replay(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, fallback,
+                                            words, stream);
+    case Lanes::four:
+      // Four lanes per series, scaled frame.  Groups of 64 series whose anchor intervals are beyond the guard (gaps in time)
+      // are left to the replay pair below, gated per group by the words k_q4_gate leaves (decided on the device).
+      if (int e = c2_internal_loglik_q4_grad(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, records,
+                                             words, stream))
+        return e;
+      break;
+    case Lanes::two:
+      // Two lanes per series: as below, the two wavefronts of a group of 64 series raising its guard word together
+      if (int e = hip_check(hipMemsetAsync(words, 0, 8 * L.n_words, s))) return e;
+      if (int e = c2_internal_loglik_k2_grad(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, records,
+                                             words, stream))
+        return e;
+      break;
+    default: {   // Lanes::one
+      // One lane per series: forward with records, then the backward-recursion reverse sweep.  The forward pass leaves
+      // the stability measure of every WAVEFRONT in its own guard word; where it exceeds kBackwardGuard that wavefront's
+      // reverse sweep returns at once and the replay pair below -- gated per group of 64 series by the same words --
+      // produces the gradients of those series (same outputs; its workspace overlays the records, which nobody reads any
+      // more by then; decided on the device).
+      if (int e = hip_check(hipMemsetAsync(words, 0, 8 * kGateHeadWords, s))) return e;
+      auto one_lane = J == 8 ? c2_internal_loglik_t_grad8
+                    : J == 6 ? c2_internal_loglik_t_grad6
+                    : J == 4 ? c2_internal_loglik_t_grad4 : c2_internal_loglik_t_grad2;
+      if (int e = one_lane(B, N, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, records, words, stream))
+        return e;
+      break;
+    }
   }
-  if (gate == nullptr && use_back(N, J))   // the primary path of this batch: reverse sweep by the backward recursion
-    return loglik_grad_group(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work, nullptr, true,
-                             stream);
-  return c2_internal_loglik_grad_replay(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, work, gate,
-                                        stream);
+  // per group of 64 series: only the wavefronts that fell back are replayed
+  return c2_internal_loglik_grad_replay(B, N, J, t, t_bs, c, c_bs, a, U, V, y, ll, bt, bc, ba, bU, bV, by, flag, fallback,
+                                        gate_per_wave(words + kGateHeadWords), stream);
 }
 
 // The checkpoint / replay pair (lanes of a series share its state), every kernel behind `gate` (gate_closed; nullptr: run).

@@ -292,11 +292,10 @@ int run(int64_t B, int64_t N, int64_t nrhs, const double *t, int64_t t_bs, const
   const size_t n_carry = (size_t)B * nchunk * NT * 4 * kWave, n_dc = (size_t)B * nchunk * J,
                n_rs = (size_t)B * kScanRanges * NT * 4 * 3 * kWave;
   const size_t bytes = sizeof(double) * (n_carry + n_dc + n_rs);
-  double *carry = nullptr;
-  bool async = true;
-  if (c2::temp_alloc((void **)&carry, bytes, s) != hipSuccess) {
-    (void)hipGetLastError();
-    async = false;
+  // (without the pool -- allocation refused -- a plain allocation, freed behind a synchronisation below)
+  StreamTemp tmp(s, bytes, nullptr, StreamTemp::kAlsoInCaptures);
+  double *carry = tmp.get();
+  if (!tmp) {
     if (int e = hip_check(hipMalloc((void **)&carry, bytes))) return e;
   }
   const dim3 grid((unsigned)(B * nchunk));
@@ -311,12 +310,9 @@ int run(int64_t B, int64_t N, int64_t nrhs, const double *t, int64_t t_bs, const
   hipLaunchKernelGGL((k_mm_mfma<NT, true, SCALE>), grid, dim3(kWave), 0, s, B, N, nrhs, Lc, nchunk, t, t_bs, c, c_bs, U,
                      V, d, Y, Z, carry, Dc, zero_z);
   int rc = launch_ok();
-  if (async) {
-    rc = keep_first(rc, hipFreeAsync(carry, s));
-  } else {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(carry);
-  }
+  if (tmp) return tmp.release(rc);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(carry);
   return rc;
 }
 

@@ -1472,55 +1472,30 @@ static int launch_sweep(int64_t B, int64_t N, int64_t J, int64_t nrhs, const dou
     // many right-hand sides on a small batch (apply_inverse on an N x M matrix, core.py:56-60): chunk maps with lanes over
     // the columns, every column in the same three launches (c2_solve_cols.hip).  Scratch is a stream-ordered temporary;
     // not inside graph captures.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &capturing);
-    if (capturing == hipStreamCaptureStatusNone) {
-      const size_t nd = c2_internal_solve_cols_doubles(B, N, J, nrhs);
-      void *tmp = nullptr;
-      if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
-        int rc = c2_internal_solve_cols(LOWER ? 1 : 0, B, N, J, nrhs, t, t_bs, c, c_bs, U, V, Y, Z, (double *)tmp, stream);
-        rc = keep_first(rc, hipFreeAsync(tmp, s));
-        if (rc != C2_ERR_UNSUPPORTED) return rc;
-      }
-      (void)hipGetLastError();
+    StreamTemp tmp(s, c2_internal_solve_cols_doubles(B, N, J, nrhs) * sizeof(double));
+    if (tmp) {
+      const int rc = tmp.release(c2_internal_solve_cols(LOWER ? 1 : 0, B, N, J, nrhs, t, t_bs, c, c_bs, U, V, Y, Z, tmp.get(), stream));
+      if (rc != C2_ERR_UNSUPPORTED) return rc;
     }
   }
   if (SOLVE && solve_chunks_shape(B, N, J, nrhs) && solve_chunks_enabled()) {
     // a small batch of series of 512 rows and more: chunk maps, from 8192 rows with the chain over the chunks in two levels
     // (c2_timepar_grad.hip; every width up to 8), right-hand side by right-hand side, the workspace written on the way if asked for (one series of 1e5
     // rows, 8 right-hand sides: 31 ms row by row).  Scratch is a stream-ordered temporary; not inside graph captures.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &capturing);
-    if (capturing == hipStreamCaptureStatusNone) {
-      const int sh = c2_internal_tpg_short_chunks(B, N);
-      const size_t nd = sh == 2 ? c2_internal_solve_chunks_doubles16(B, N, J)
-                                : (sh == 1 ? c2_internal_solve_chunks_doubles32(B, N, J) : c2_internal_solve_chunks_doubles64(B, N, J));
-      void *tmp = nullptr;
-      if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
-        int rc = (sh == 2 ? c2_internal_solve_chunks16 : (sh == 1 ? c2_internal_solve_chunks32 : c2_internal_solve_chunks64))(LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V,
-                                                                               Y, Z, (double *)tmp, stream, nrhs, F);
-        rc = keep_first(rc, hipFreeAsync(tmp, s));
-        return rc;
-      }
-      (void)hipGetLastError();
-    }
+    const int sh = c2_internal_tpg_short_chunks(B, N);
+    const size_t nd = sh == 2 ? c2_internal_solve_chunks_doubles16(B, N, J)
+                              : (sh == 1 ? c2_internal_solve_chunks_doubles32(B, N, J) : c2_internal_solve_chunks_doubles64(B, N, J));
+    StreamTemp tmp(s, nd * sizeof(double));
+    if (tmp)
+      return tmp.release((sh == 2 ? c2_internal_solve_chunks16 : (sh == 1 ? c2_internal_solve_chunks32 : c2_internal_solve_chunks64))(
+          LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, tmp.get(), stream, nrhs, F));
   }
   if (SOLVE && nrhs == 1 && !F && c2_internal_use_timepar_solve(B, N, J)) {
     // a small batch of long series and one right-hand side: the solve recursion is affine in its state -- chunks of 64
     // rows in parallel, chained, applied (c2_timepar.hip).  Scratch (series longer than 4096 rows only) is a
     // stream-ordered temporary; not inside graph captures.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &capturing);
-    if (capturing == hipStreamCaptureStatusNone) {
-      const size_t nd = c2_internal_timepar_solve_doubles(B, N, J);
-      void *tmp = nullptr;
-      if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
-        int rc = c2_internal_solve_timepar(LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, (double *)tmp, stream);
-        rc = keep_first(rc, hipFreeAsync(tmp, s));
-        return rc;
-      }
-      (void)hipGetLastError();
-    }
+    StreamTemp tmp(s, c2_internal_timepar_solve_doubles(B, N, J) * sizeof(double));
+    if (tmp) return tmp.release(c2_internal_solve_timepar(LOWER ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, tmp.get(), stream));
   }
   if (nrhs == 1)  // a vector: the tuned single-rhs kernel (c2_sweep.hip)
     return c2_internal_sweep1(LOWER ? 1 : 0, SOLVE ? 1 : 0, B, N, J, t, t_bs, c, c_bs, U, V, Y, Z, F, zero_z, stream);
@@ -1587,36 +1562,19 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
   if (!F && nrhs >= 33 && M >= 2 && use_generalK()) {
     int64_t Lc = c2_internal_general_chunks_plan(B, M, nrhs);
     if (opt::has(opt::k_general_rhs_chunks)) Lc = opt::ival(opt::k_general_rhs_chunks) >= 8 ? opt::ival(opt::k_general_rhs_chunks) : 0;
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &capturing);
-    if (Lc > 0 && capturing == hipStreamCaptureStatusNone) {
-      const size_t nd = c2_internal_general_chunks_doubles(B, M, J, nrhs, Lc);
-      void *tmp = nullptr;
-      if (nd > 0 && c2::temp_alloc(&tmp, nd * sizeof(double), s) == hipSuccess) {
-        int rc = c2_internal_general_chunks(LOWER ? 1 : 0, B, N, M, J, nrhs, Lc, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, (double *)tmp,
-                                            stream);
-        rc = keep_first(rc, hipFreeAsync(tmp, s));
-        if (rc != C2_ERR_UNSUPPORTED) return rc;
-      }
-      (void)hipGetLastError();
+    StreamTemp tmp(s, Lc > 0 ? c2_internal_general_chunks_doubles(B, M, J, nrhs, Lc) * sizeof(double) : 0);
+    if (tmp) {
+      const int rc = tmp.release(c2_internal_general_chunks(LOWER ? 1 : 0, B, N, M, J, nrhs, Lc, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y,
+                                                            Z, tmp.get(), stream));
+      if (rc != C2_ERR_UNSUPPORTED) return rc;
     }
   }
   if (use_general_tile() && !(nrhs == 3 && B >= 512 && use_generalK())) {
     // small batches of long series are cut into chunks along time: a stream-ordered temporary for the chunk maps (not
     // inside a graph capture, and one wavefront per series if the allocation fails)
-    void *tmp = nullptr;
-    const size_t nd = c2_internal_general_tile_doubles(B, M, J, nrhs);
-    if (nd > 0) {
-      hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(s, &capturing);
-      if (capturing != hipStreamCaptureStatusNone || c2::temp_alloc(&tmp, nd * sizeof(double), s) != hipSuccess) {
-        (void)hipGetLastError();
-        tmp = nullptr;
-      }
-    }
-    int e = c2_internal_general_tile(LOWER ? 1 : 0, B, N, M, J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F,
-                                     (double *)tmp, stream);
-    if (tmp) e = keep_first(e, hipFreeAsync(tmp, s));
+    StreamTemp tmp(s, c2_internal_general_tile_doubles(B, M, J, nrhs) * sizeof(double));   // (no room: get() is nullptr)
+    const int e = tmp.release(c2_internal_general_tile(LOWER ? 1 : 0, B, N, M, J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F,
+                                                       tmp.get(), stream));
     if (e != C2_ERR_UNSUPPORTED) return e;
   }
   // three or more right-hand sides: lanes over the right-hand sides, one merge event per iteration (c2_general.hip)
@@ -1631,19 +1589,19 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
   // temporary the sequential merge kernel runs instead (no scratch memory at all).
   constexpr size_t kGeneralTempMax = (size_t)32 << 30;
   const size_t fbytes = sizeof(double) * (size_t)B * M * J * nrhs;
-  double *Fw = F;
-  if (!Fw) {
-    // without a caller workspace the state rows are pure overhead (2 x 8 J nrhs bytes per row): two phases pay off
-    // for one or two right-hand sides (prediction); beyond that they only draw level with the sequential merge
-    // (22.5 against 24 ms at nrhs = 8, measured with -DC2_GM_TWO_PHASE_MAX_NRHS=64), which needs no scratch memory
-    if (nrhs > C2_GM_TWO_PHASE_MAX_NRHS || fbytes > kGeneralTempMax || c2::temp_alloc((void **)&Fw, fbytes, s) != hipSuccess) {
-      (void)hipGetLastError();
-      C2_DISPATCH_G(group_size(J),
-                    hipLaunchKernelGGL((k_general<G, KT, LOWER>), grid_for(B, G, (nrhs + KT - 1) / KT), dim3(kWave), 0,
-                                       s, B, N, M, (int)J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F));
-      return launch_ok();
-    }
+  // without a caller workspace the state rows are pure overhead (2 x 8 J nrhs bytes per row): two phases pay off
+  // for one or two right-hand sides (prediction); beyond that they only draw level with the sequential merge
+  // (22.5 against 24 ms at nrhs = 8, measured with -DC2_GM_TWO_PHASE_MAX_NRHS=64), which needs no scratch memory
+  // (this temporary is taken inside a graph capture as well, as it always was)
+  const bool two_phase = F || (nrhs <= C2_GM_TWO_PHASE_MAX_NRHS && fbytes <= kGeneralTempMax);
+  StreamTemp tmp(s, two_phase ? fbytes : 0, F, StreamTemp::kAlsoInCaptures);
+  if (!tmp) {
+    C2_DISPATCH_G(group_size(J),
+                  hipLaunchKernelGGL((k_general<G, KT, LOWER>), grid_for(B, G, (nrhs + KT - 1) / KT), dim3(kWave), 0,
+                                     s, B, N, M, (int)J, nrhs, t1, t1_bs, t2, t2_bs, c, c_bs, U, V, Y, Z, F));
+    return launch_ok();
   }
+  double *Fw = tmp.get();
   C2_DISPATCH_G(group_size(J), {
     if (nrhs == 1)
       hipLaunchKernelGGL((k_gm_state<G, 1, LOWER>), grid_for(B, G), dim3(kWave), 0, s, B, N, M, (int)J, nrhs, t1, t1_bs,
@@ -1654,11 +1612,7 @@ static int launch_general(int64_t B, int64_t N, int64_t M, int64_t J, int64_t nr
     hipLaunchKernelGGL((k_gm_emit<G, LOWER>), grid_for(B * N, G), dim3(kWave), 0, s, B, N, M, (int)J, nrhs, t1, t1_bs,
                        t2, t2_bs, c, c_bs, U, V, Y, (const double *)Fw, Z);
   });
-  int rc = launch_ok();
-  if (!F) {
-    rc = keep_first(rc, hipFreeAsync(Fw, s));
-  }
-  return rc;
+  return tmp.release(launch_ok());
 }
 template <bool LOWER, bool SOLVE>
 static int launch_sweep_rev(int64_t B, int64_t N, int64_t J, int64_t nrhs, const double *t, int64_t t_bs,
@@ -1978,12 +1932,9 @@ int c2_condition(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
   if (!t || !c || !a || !U || !V || !kappa || !flag) return C2_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const int64_t slice = B < 4096 ? B : 4096;
-  double *tmp = nullptr;
-  if (int e = hip_check(temp_alloc((void **)&tmp, sizeof(double) * (size_t)slice * (size_t)N * (size_t)(J + 1), s))) {
-    (void)hipGetLastError();
-    return e;
-  }
-  double *d = tmp, *W = tmp + (size_t)slice * (size_t)N;
+  StreamTemp tmp(s, sizeof(double) * (size_t)slice * (size_t)N * (size_t)(J + 1), nullptr, StreamTemp::kAlsoInCaptures);
+  if (!tmp) return hip_check(tmp.error());
+  double *d = tmp.get(), *W = d + (size_t)slice * (size_t)N;
   int rc = C2_OK;
   for (int64_t b0 = 0; b0 < B && rc == C2_OK; b0 += slice) {
     const int64_t nb = B - b0 < slice ? B - b0 : slice;
@@ -1994,7 +1945,7 @@ int c2_condition(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
                        (const int32_t *)(flag + b0), kappa + b0);
     rc = launch_ok();
   }
-  return keep_first(rc, hipFreeAsync(tmp, s));
+  return tmp.release(rc);
 }
 
 }  // extern "C"

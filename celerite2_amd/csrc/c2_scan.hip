@@ -186,11 +186,10 @@ int run_chunked(int64_t B, int64_t N, int64_t J, int64_t nrhs, int64_t Lc, const
                 int zero_z, hipStream_t s) {
   const int64_t nchunk = (N + Lc - 1) / Lc;
   const size_t bytes = sizeof(double) * (size_t)B * nchunk * J * nrhs;
-  double *carry = nullptr;
-  bool async = true;
-  if (c2::temp_alloc((void **)&carry, bytes, s) != hipSuccess) {
-    (void)hipGetLastError();
-    async = false;
+  // (without the pool -- allocation refused -- a plain allocation, freed behind a synchronisation below)
+  StreamTemp tmp(s, bytes, nullptr, StreamTemp::kAlsoInCaptures);
+  double *carry = tmp.get();
+  if (!tmp) {
     if (int e = hip_check(hipMalloc((void **)&carry, bytes))) return e;
   }
   const int G_ = group_size(J);
@@ -234,12 +233,9 @@ int run_chunked(int64_t B, int64_t N, int64_t J, int64_t nrhs, int64_t Lc, const
                      nchunk, t, t_bs, c, c_bs, carry);
   pass(std::true_type{});
   int rc = launch_ok();
-  if (async) {
-    rc = keep_first(rc, hipFreeAsync(carry, s));
-  } else {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(carry);
-  }
+  if (tmp) return tmp.release(rc);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(carry);
   return rc;
 }
 }  // namespace

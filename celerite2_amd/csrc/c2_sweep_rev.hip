@@ -639,20 +639,14 @@ extern "C" int c2_internal_sweep_rev_long(int lower, int solve, int64_t B, int64
                                           c2_stream_t stream) {
   using namespace c2rl;
   hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &capturing);
-  if (capturing != hipStreamCaptureStatusNone || (!solve && bY == bZ)) return C2_ERR_UNSUPPORTED;
-  if (J > 32) return C2_ERR_UNSUPPORTED;
+  if ((!solve && bY == bZ) || J > 32) return C2_ERR_UNSUPPORTED;
   int JL = 1;
   while (JL < J) JL *= 2;
   const int64_t nblk = (N + kRowsPerBlock / JL - 1) / (kRowsPerBlock / JL);
   const size_t nws = (size_t)B * N * J * nrhs, npart = (size_t)B * nblk * J;
-  void *tmp = nullptr;
-  if (c2::temp_alloc(&tmp, (nws + npart) * sizeof(double), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return C2_ERR_UNSUPPORTED;
-  }
-  double *Fa = (double *)tmp, *part = Fa + nws;
+  StreamTemp tmp(s, (nws + npart) * sizeof(double));
+  if (!tmp) return C2_ERR_UNSUPPORTED;   // (inside a graph capture, allocation refused)
+  double *Fa = tmp.get(), *part = Fa + nws;
   int rc;
   if (solve) rc = lower ? c2_solve_upper(B, N, J, nrhs, t, t_bs, c, c_bs, U, V, bZ, bY, Fa, stream)
                         : c2_solve_lower(B, N, J, nrhs, t, t_bs, c, c_bs, U, V, bZ, bY, Fa, stream);
@@ -683,5 +677,5 @@ extern "C" int c2_internal_sweep_rev_long(int lower, int solve, int64_t B, int64
     hipLaunchKernelGGL(k_rev_bc, dim3((unsigned)(B * J)), dim3(kWave), 0, s, (int)J, nblk, (const double *)part, bc);
     rc = launch_ok();
   }
-  return keep_first(rc, hipFreeAsync(tmp, s));
+  return tmp.release(rc);
 }

@@ -27,6 +27,7 @@
 #include "../../include/celerite2_amd.h"
 #include "c2_internal.hpp"
 #include "c2_launch.hpp"
+#include "c2_plan.hpp"
 
 namespace c2terms {
 
@@ -159,7 +160,7 @@ __global__ void k_terms_rev_finish(int Jr, int Jc, int nsplit, const double *__r
   }
 }
 
-inline size_t al2(size_t n) { return (n + 1) & ~(size_t)1; }
+using c2::al2;
 
 struct Plan {
   size_t c, a, U, V, bt, bc, ba, bU, bV, one_d, total;  // doubles
@@ -203,20 +204,6 @@ using namespace c2terms;
 // wavefront per SIMD
 // ... and with four (c2_loglik_q4.hip: k_q4_fwd / k_q4_rev<..., TT>): the batches between the eight-lane and the two-lane range
 static bool fused_width(int64_t J) { return J == 8 || J == 4 || J == 2; }
-// guard words in front of the fused kernels' records: the head + one per wavefront of 64 series, rounded to 16 bytes
-static size_t fused_gate_words(int64_t B) { return (size_t)((c2::kGateHeadWords + (B + 63) / 64 + 1) & ~(int64_t)1); }
-static size_t fused_record_doubles(int64_t B, int64_t N, int64_t J) {
-  const size_t r3 = al2((size_t)B * J) + c2_internal_loglik_g8_tt_doubles(B, N, J);   // (the rates in front: Plan::c)
-  if (J == 8) {   // any lane mapping
-    const size_t r1 = c2_internal_loglik_t_record_doubles8(B, N), r2 = c2_internal_loglik_k2_record_doubles(B, N);
-    const size_t r4 = al2((size_t)B * 8) + c2_internal_loglik_q4_record_doubles(B, N);
-    size_t r = r1 > r2 ? r1 : r2;
-    r = r > r3 ? r : r3;
-    return r > r4 ? r : r4;
-  }
-  const size_t r1 = J == 4 ? c2_internal_loglik_t_record_doubles4(B, N) : c2_internal_loglik_t_record_doubles2(B, N);
-  return r1 > r3 ? r1 : r3;
-}
 // Two lanes per series (J == 8) between the composed chain and the one-lane kernels: C2_TERMS_TWO_LANES=1 forces them, =0
 // disables them; otherwise by batch size (a forced C2_TERMS_FUSED decides first)
 static bool use_two_lanes(int64_t B, int64_t J, bool grad) {
@@ -262,6 +249,57 @@ static bool use_four_lanes(int64_t B, int64_t J, bool grad = true) {
   return B >= c2::opt::ival(c2::opt::k_terms_four_lanes_min_batch_grad) && B < c2::opt::ival(c2::opt::k_terms_four_lanes_max_batch_grad);
 }
 
+// THE PLAN of the coefficient-level pair (c2_plan.hpp), first half: one precedence for c2_loglik_terms and
+// c2_loglik_terms_grad -- four lanes > the group of J lanes > two > one > the composed chain (matrices in memory, then
+// c2_loglik / c2_loglik_grad).  Nothing else asks the use_* predicates.
+using c2::Lanes;
+static Lanes terms_mapping(int64_t B, int64_t N, int64_t J, bool grad) {
+  if (use_four_lanes(B, J, grad)) return Lanes::four;
+  if (use_eight_lanes(B, N, J, grad)) return Lanes::group;
+  if (use_two_lanes(B, J, grad)) return Lanes::two;
+  if (use_fused(B, J, grad)) return Lanes::one;
+  return Lanes::composed;
+}
+static bool terms_mapping_exists(Lanes m, int64_t J) {   // whatever the options: the widths a family is compiled for
+  return m == Lanes::composed || (fused_width(J) && (J == 8 || m == Lanes::group || m == Lanes::one));
+}
+// Second half: the layout (offsets in doubles).
+//   gradient, a lane mapping   [gate words][rates | records of the pair behind them]
+//                              [          ][plan of the composed chain, gated per group of 64 series   ]
+//   forward, four / J lanes    [gate words][plan of the composed chain, gated][span words of the four-lane form]
+//   forward, two / one lane    nothing
+//   composed                   [plan]
+// The rates are Plan::c, the first array of the plan: the lane kernels and the gated chain read the same copy.
+struct TermsLayout {
+  size_t n_words;   // gate words, in front
+  size_t plan;      // where the Plan of the composed chain starts (the rates with it)
+  size_t records;   // gradient: the records of the lane mapping, behind the rates
+  size_t spans;     // forward, four lanes: k_anchor_spans' words, behind the plan
+  size_t need;
+};
+static TermsLayout terms_layout(Lanes m, int64_t B, int64_t N, int64_t J, int grad) {
+  TermsLayout L{};
+  const size_t total = plan(B, N, J, grad).total;
+  if (m == Lanes::composed) { L.need = total; return L; }
+  if (!grad && (m == Lanes::two || m == Lanes::one)) return L;
+  L.n_words = L.plan = c2::gate_words(B);
+  if (!grad) {
+    L.spans = L.plan + total;
+    L.need = L.spans + (m == Lanes::four ? al2(c2_internal_loglik_q4_span_words(B, N)) : 0);
+    return L;
+  }
+  const bool rates_in_front = m == Lanes::four || m == Lanes::group;   // (the others compute the rates in the lane)
+  L.records = L.plan + (rates_in_front ? al2((size_t)B * J) : 0);
+  const size_t r = m == Lanes::four    ? c2_internal_loglik_q4_record_doubles(B, N)
+                   : m == Lanes::group ? c2_internal_loglik_g8_tt_doubles(B, N, J)
+                   : m == Lanes::two   ? c2_internal_loglik_k2_record_doubles(B, N)
+                   : J == 8            ? c2_internal_loglik_t_record_doubles8(B, N)
+                   : J == 4            ? c2_internal_loglik_t_record_doubles4(B, N)
+                                       : c2_internal_loglik_t_record_doubles2(B, N);
+  L.need = c2::max2(L.records + r, L.plan + total);
+  return L;
+}
+
 static int matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ar, const double *cr, const double *ac,
                     const double *bc, const double *cc, const double *dc, int coef_batched, const double *x,
                     int64_t x_bs, const double *diag, double *w, const Plan &p, const unsigned long long *gate,
@@ -276,20 +314,23 @@ static int matrices(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *
 
 extern "C" {
 
-// Either variant fits: [guard word, 16 bytes] [records of the fused kernels | plan of the composed chain]; the choice
-// between them is made per call (batch size, C2_TERMS_FUSED), the size does not depend on it.
+// Every mapping fits: the choice among them is made per call (batch size, the C2_TERMS_* options), the size does not
+// depend on it -- the largest need over the mappings that exist at this width.
 size_t c2_loglik_terms_workspace_bytes(int64_t B, int64_t N, int64_t Jr, int64_t Jc, int grad) {
   if (check(B, N, Jr, Jc)) return 0;
   const int64_t J = Jr + 2 * Jc;
-  size_t n = plan(B, N, J, grad).total;
-  if (grad && fused_width(J)) {
-    const size_t r = fused_record_doubles(B, N, J);
-    n = fused_gate_words(B) + (r > n ? r : n);
-  } else if (!grad && fused_width(J)) {
-    n += fused_gate_words(B);   // the group-mapping forward form: one word per group of 64 series in front of the plan
-    if (J == 8) n += al2(c2_internal_loglik_q4_span_words(B, N));   // ... and the four-lane form's span words behind it
-  }
+  size_t n = 0;
+  for (Lanes m : {Lanes::four, Lanes::group, Lanes::two, Lanes::one, Lanes::composed})
+    if (terms_mapping_exists(m, J)) n = c2::max2(n, terms_layout(m, B, N, J, grad).need);
   return n * sizeof(double);
+}
+// test hook (loaded by name): the mapping of one call and what it needs
+int c2_internal_loglik_terms_plan(int64_t B, int64_t N, int64_t Jr, int64_t Jc, int grad, int *mapping, size_t *need_doubles) {
+  if (check(B, N, Jr, Jc) || !mapping || !need_doubles) return C2_ERR_INVALID;
+  const Lanes m = terms_mapping(B, N, Jr + 2 * Jc, grad != 0);
+  *mapping = (int)m;
+  *need_doubles = terms_layout(m, B, N, Jr + 2 * Jc, grad).need;
+  return C2_OK;
 }
 
 int c2_loglik_terms(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ar, const double *cr, const double *ac,
@@ -301,38 +342,37 @@ int c2_loglik_terms(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *
     return C2_ERR_INVALID;
   const int64_t J = Jr + 2 * Jc;
   if (work_bytes < c2_loglik_terms_workspace_bytes(B, N, Jr, Jc, 0)) return C2_ERR_INVALID;
-  const bool four_f = use_four_lanes(B, J, false), eight_f = !four_f && use_eight_lanes(B, N, J, false);
-  if (four_f || eight_f) {
-    // every lane forms its column of U, V (k_loglik_fwd<..., TT>); a group of 64 series with a phase beyond the branch-free
-    // sincos is closed in the gate words and goes through matrices in memory, every kernel of that chain behind the same words
-    unsigned long long *guard = (unsigned long long *)work;
-    double *w = (double *)work + fused_gate_words(B);
-    hipStream_t s = (hipStream_t)stream;
-    const Plan p = plan(B, N, J, 0);
-    hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
-                       w + p.c, (const unsigned long long *)nullptr);
-    if (int e = c2::launch_ok()) return e;
-    if (four_f) {
-      unsigned long long *words = (unsigned long long *)(w + p.total);   // (behind the plan: k_anchor_spans' scratch)
-      if (int e = c2_internal_loglik_q4_tt(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, flag, words, guard, stream))
-        return e;
-    } else if (int e = c2_internal_loglik_g8_tt(B, N, J, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, flag, guard,
-                                                stream))
-      return e;
-    const unsigned long long *gate = c2::gate_per_wave(guard + c2::kGateHeadWords);
-    if (int e = matrices(B, N, Jr, Jc, ar, cr, ac, bc, cc, dc, coef_batched, x, x_bs, diag, w, p, gate, s)) return e;
-    return c2_internal_loglik_g8_gated(B, N, J, x, x_bs, w + p.c, J, w + p.a, w + p.U, w + p.V, y, ll, flag, gate, stream);
-  }
-  if (use_two_lanes(B, J, false))
-    return c2_internal_loglik_k2_tt(B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, flag, stream);
-  if (use_fused(B, J, false))
-    return (J == 8 ? c2_internal_loglik_tt8 : (J == 4 ? c2_internal_loglik_tt4 : c2_internal_loglik_tt2))(
-        B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, flag, stream);
-  const Plan p = plan(B, N, J, 0);
-  double *w = (double *)work;
   hipStream_t s = (hipStream_t)stream;
-  if (int e = matrices(B, N, Jr, Jc, ar, cr, ac, bc, cc, dc, coef_batched, x, x_bs, diag, w, p, nullptr, s)) return e;
-  return c2_loglik(B, N, J, x, x_bs, w + p.c, J, w + p.a, w + p.U, w + p.V, y, ll, flag, stream);
+  const Lanes m = terms_mapping(B, N, J, false);
+  const TermsLayout L = terms_layout(m, B, N, J, 0);
+  const Plan p = plan(B, N, J, 0);
+  double *w = (double *)work + L.plan;
+  switch (m) {
+    case Lanes::two:
+      return c2_internal_loglik_k2_tt(B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, flag, stream);
+    case Lanes::one:
+      return (J == 8 ? c2_internal_loglik_tt8 : (J == 4 ? c2_internal_loglik_tt4 : c2_internal_loglik_tt2))(
+          B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, flag, stream);
+    case Lanes::composed:
+      if (int e = matrices(B, N, Jr, Jc, ar, cr, ac, bc, cc, dc, coef_batched, x, x_bs, diag, w, p, nullptr, s)) return e;
+      return c2_loglik(B, N, J, x, x_bs, w + p.c, J, w + p.a, w + p.U, w + p.V, y, ll, flag, stream);
+    default: break;   // Lanes::four, Lanes::group
+  }
+  // every lane forms its column of U, V (k_loglik_fwd<..., TT>); a group of 64 series with a phase beyond the branch-free
+  // sincos is closed in the gate words and goes through matrices in memory, every kernel of that chain behind the same words
+  unsigned long long *guard = (unsigned long long *)work;
+  hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
+                     w + p.c, (const unsigned long long *)nullptr);
+  if (int e = c2::launch_ok()) return e;
+  if (int e = m == Lanes::four
+                  ? c2_internal_loglik_q4_tt(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, flag,
+                                             (unsigned long long *)((double *)work + L.spans), guard, stream)
+                  : c2_internal_loglik_g8_tt(B, N, J, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, flag, guard,
+                                             stream))
+    return e;
+  const unsigned long long *gate = c2::gate_per_wave(guard + c2::kGateHeadWords);
+  if (int e = matrices(B, N, Jr, Jc, ar, cr, ac, bc, cc, dc, coef_batched, x, x_bs, diag, w, p, gate, s)) return e;
+  return c2_internal_loglik_g8_gated(B, N, J, x, x_bs, w + p.c, J, w + p.a, w + p.U, w + p.V, y, ll, flag, gate, stream);
 }
 
 int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const double *ar, const double *cr,
@@ -346,42 +386,44 @@ int c2_loglik_terms_grad(int64_t B, int64_t N, int64_t Jr, int64_t Jc, const dou
     return C2_ERR_INVALID;
   const int64_t J = Jr + 2 * Jc;
   if (work_bytes < c2_loglik_terms_workspace_bytes(B, N, Jr, Jc, 1)) return C2_ERR_INVALID;
-  const Plan p = plan(B, N, J, 1);
-  double *w = (double *)work;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned long long *gate = nullptr;
-  const bool four = use_four_lanes(B, J);
-  const bool eight = !four && use_eight_lanes(B, N, J, true);
-  const bool two = !four && !eight && use_two_lanes(B, J, true);
-  if (eight || four) {
-    // the eight-lane pair with the rows formed in the lanes; its gate words (written by the launch) send a group of 64 series
-    // it declines -- a span beyond the backward guard, a phase beyond the branch-free sincos -- to the composed chain below
-    unsigned long long *guard = (unsigned long long *)work;
-    w += fused_gate_words(B);
-    hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
-                       w + p.c, (const unsigned long long *)nullptr);
-    if (int e = c2::launch_ok()) return e;
-    if (int e = four ? c2_internal_loglik_q4_tt_grad(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar, bcr,
-                                                     bac, bbc, bcc, bdc, bx, bdiag, by, flag, w + al2((size_t)B * 8), guard, stream)
-                     : c2_internal_loglik_g8_tt_grad(B, N, J, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar,
-                                                     bcr, bac, bbc, bcc, bdc, bx, bdiag, by, flag, w + al2((size_t)B * J), guard,
-                                                     stream))
-      return e;
-    gate = c2::gate_per_wave(guard + c2::kGateHeadWords);
-  } else if (two || use_fused(B, J, true)) {
-    // Forward with records + reverse sweep, both forming the rows in the lane.  As in c2_loglik_grad, the forward pass
-    // leaves its stability measure in `guard`; if it exceeds kBackwardGuard the reverse sweep returns at once and the
-    // composed chain below -- every kernel of it behind the same word -- produces the gradients instead.
-    unsigned long long *guard = (unsigned long long *)work;
-    // (two lanes per series: the two wavefronts of a group of 64 series raise its word together -- every word starts at zero)
-    if (int e = c2::hip_check(hipMemsetAsync(guard, 0, 8 * (two ? fused_gate_words(B) : (size_t)c2::kGateHeadWords), s))) return e;
-    w += fused_gate_words(B);
-    auto fused = two ? c2_internal_loglik_k2_tt_grad
-                     : (J == 8 ? c2_internal_loglik_tt_grad8 : (J == 4 ? c2_internal_loglik_tt_grad4 : c2_internal_loglik_tt_grad2));
-    if (int e = fused(B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, bar, bcr, bac, bbc, bcc, bdc,
-                      bx, bdiag, by, flag, w, guard, stream))
-      return e;
-    gate = c2::gate_per_wave(guard + c2::kGateHeadWords);   // per group of 64 series (c2_loglik_helpers.hpp)
+  const Lanes m = terms_mapping(B, N, J, true);
+  const TermsLayout L = terms_layout(m, B, N, J, 1);
+  const Plan p = plan(B, N, J, 1);
+  double *w = (double *)work + L.plan, *records = (double *)work + L.records;
+  unsigned long long *guard = (unsigned long long *)work;
+  const unsigned long long *gate = m == Lanes::composed ? nullptr : c2::gate_per_wave(guard + c2::kGateHeadWords);
+  switch (m) {
+    case Lanes::composed: break;
+    case Lanes::four:
+    case Lanes::group:
+      // four or J lanes per series with the rows formed in the lanes; the gate words (written by the launch) send a group of
+      // 64 series it declines -- a span beyond the backward guard, a phase beyond the branch-free sincos -- to the composed
+      // chain below
+      hipLaunchKernelGGL(k_rates, dim3((unsigned)((B * J + 255) / 256)), dim3(256), 0, s, B, (int)Jr, (int)Jc, cr, cc, coef_batched,
+                         w + p.c, (const unsigned long long *)nullptr);
+      if (int e = c2::launch_ok()) return e;
+      if (int e = m == Lanes::four
+                      ? c2_internal_loglik_q4_tt_grad(B, N, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar, bcr,
+                                                      bac, bbc, bcc, bdc, bx, bdiag, by, flag, records, guard, stream)
+                      : c2_internal_loglik_g8_tt_grad(B, N, J, Jc, coef_batched, ar, ac, bc, dc, w + p.c, x, x_bs, diag, y, ll, bar,
+                                                      bcr, bac, bbc, bcc, bdc, bx, bdiag, by, flag, records, guard, stream))
+        return e;
+      break;
+    default: {   // Lanes::two, Lanes::one
+      // Forward with records + reverse sweep, both forming the rows in the lane.  As in c2_loglik_grad, the forward pass
+      // leaves its stability measure in `guard`; if it exceeds kBackwardGuard the reverse sweep returns at once and the
+      // composed chain below -- every kernel of it behind the same word -- produces the gradients instead.
+      // (two lanes per series: the two wavefronts of a group of 64 series raise its word together -- every word starts at zero)
+      const bool two = m == Lanes::two;
+      if (int e = c2::hip_check(hipMemsetAsync(guard, 0, 8 * (two ? L.n_words : (size_t)c2::kGateHeadWords), s))) return e;
+      auto fused = two ? c2_internal_loglik_k2_tt_grad
+                       : (J == 8 ? c2_internal_loglik_tt_grad8 : (J == 4 ? c2_internal_loglik_tt_grad4 : c2_internal_loglik_tt_grad2));
+      if (int e = fused(B, N, Jc, coef_batched, ar, cr, ac, bc, cc, dc, x, x_bs, diag, y, ll, bar, bcr, bac, bbc, bcc, bdc,
+                        bx, bdiag, by, flag, records, guard, stream))
+        return e;
+      break;
+    }
   }
   if (int e = matrices(B, N, Jr, Jc, ar, cr, ac, bc, cc, dc, coef_batched, x, x_bs, diag, w, p, gate, s)) return e;
   if (gate) {

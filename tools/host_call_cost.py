@@ -1,8 +1,42 @@
 """Per-call cost of the host-pointer drop-in modules (celerite2_amd.driver / backprop over c2h_*): one PCIe round trip,
-one hipMalloc / hipMemcpy / hipFree per argument and a device sync per call (c2_host.hip)."""
+one hipMalloc / hipMemcpy / hipFree per argument and a device sync per call (c2_host.hip).
+--loglik: the host cost of c2_loglik_grad / c2_loglik_terms_grad on device arrays instead (below)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+
+if "--loglik" in sys.argv:
+    # python tools/host_call_cost.py --loglik: what the HOST spends per call of the fused entry points on device arrays --
+    # dispatch plan, argument checks, launches -- at a shape whose kernels take less than that (8 series of 16 rows,
+    # J = 8): n calls enqueued back to back, one synchronisation at the end, the median of five rounds
+    import torch
+    from celerite2_amd import ops, synth
+    dev = torch.device("cuda:0")
+    B, N, J = 8, 16, 8
+    t, c, a, U, V, y = synth.device_batch(0, B, N, J, dev)
+    rng = np.random.default_rng(3)
+    ac = rng.uniform(0.5, 2.0, (B, 4)); cc = rng.uniform(0.02, 0.3, (B, 4)); dc = rng.uniform(0.2, 3.0, (B, 4))
+    co = [torch.zeros((B, 0), dtype=torch.float64, device=dev)] * 2 + [torch.from_numpy(v).to(dev) for v in (ac, 0.5 * ac * cc / dc, cc, dc)]
+    diag = torch.full((B, N), 0.2, dtype=torch.float64, device=dev)
+    work = ops.loglik_grad_workspace(B, N, J, dev)
+    out = ops.loglik_grad(t, c, a, U, V, y, work=work)[1]
+    twork = ops.loglik_terms_workspace(B, N, 0, 4, dev)
+    tout = ops.loglik_terms_grad(*co, t, diag, y, work=twork)[1]
+    calls = {"c2_loglik_grad": lambda: ops.loglik_grad(t, c, a, U, V, y, work=work, out=out),
+             "c2_loglik_terms_grad": lambda: ops.loglik_terms_grad(*co, t, diag, y, work=twork, out=tout)}
+    n = 2000
+    for name, call in calls.items():
+        rounds = []
+        for _ in range(6):   # (the first round warms up and is dropped)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n): call()
+            torch.cuda.synchronize()
+            rounds.append((time.perf_counter() - t0) / n * 1e6)
+        print("%s (through ops, B=%d N=%d J=%d): %.2f us per call (rounds: %s)" % (name, B, N, J, float(np.median(rounds[1:])),
+                                                                               " ".join("%.2f" % r for r in rounds[1:])), flush=True)
+    sys.exit(0)
+
 from celerite2_amd import driver
 from oracle import dense
 for (N, J) in [(1000, 2), (4096, 8), (100000, 8)]:
