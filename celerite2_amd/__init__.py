@@ -7,6 +7,7 @@ semiseparable GP linear algebra.
     celerite2_amd.gp                                thin batched GaussianProcess frontend
     celerite2_amd.terms                             kernel terms -> (c, a, U, V)
     celerite2_amd.periodogram                       the periodogram under correlated noise: the torch part
+    celerite2_amd.harmonics                         the multi-harmonic periodogram (nterms > 1): the torch part
     celerite2_amd.transit                           the transit search under correlated noise: the torch part
     celerite2_amd.kepler                            the Keplerian search under correlated noise: the torch part
     celerite2_amd.shapes                            the tabulated-shape search under correlated noise: builders, the torch part

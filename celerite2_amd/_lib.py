@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
-celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h and celerite2_amd_shapes.h).
+celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h, celerite2_amd_shapes.h and
+celerite2_amd_harmonics.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -19,6 +20,7 @@ TRANSIT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_
 KEPLER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_kepler.h")   # the Keplerian search
 TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_trials.h")   # projections on trial columns
 SHAPES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_shapes.h")   # the tabulated-shape search
+HARMONICS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_harmonics.h")   # the multi-harmonic periodogram
 
 
 class BackendError(RuntimeError):
@@ -115,6 +117,9 @@ TRIALS_SYMBOLS = ["c2_trial_projections"]
 # Every symbol include/celerite2_amd_shapes.h declares (checked by tests/test_shapes.py).
 SHAPES_SYMBOLS = ["c2_whitened_shapes", "c2_shape_projections"]
 
+# Every symbol include/celerite2_amd_harmonics.h declares (checked by tests/test_harmonics.py).
+HARMONICS_SYMBOLS = ["c2_whitened_harmonics"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -184,6 +189,7 @@ def load():
     protos.update(_prototypes(_header(KEPLER_HEADER)))
     protos.update(_prototypes(_header(TRIALS_HEADER)))
     protos.update(_prototypes(_header(SHAPES_HEADER)))
+    protos.update(_prototypes(_header(HARMONICS_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

@@ -135,6 +135,8 @@ struct Sinusoid {
   struct Params { double t_ref; };
   double om, t_ref;
   __device__ __forceinline__ Sinusoid(const double *tr, bool live, int64_t, const Params &p) : om(live ? tr[0] : 0.0), t_ref(p.t_ref) {}
+  // (a frequency the lane formed itself: harmonic h's fl(h * w) of c2_harmonics.hip)
+  __device__ __forceinline__ Sinusoid(double om_, const Params &p) : om(om_), t_ref(p.t_ref) {}
   __device__ __forceinline__ void columns(double t, double (&a)[2]) const { sincos_cw(pgram::phase(om, t, t_ref), a[1], a[0]); }
 };
 

@@ -390,7 +390,7 @@ class GaussianProcess:
         return type(fit)(*[self._nan_failed(x.reshape(B, -1))[0].reshape(x.shape) for x in fit])
 
     # -- the periodogram under the factored covariance (ops.whitened_sinusoids; no counterpart in the reference) -------
-    def periodogram(self, y, freq, *, A="mean", normalization="standard", t_ref=0.0, return_fit=False):
+    def periodogram(self, y, freq, *, A="mean", normalization="standard", t_ref=0.0, return_fit=False, nterms=1):
         """The generalized Lomb-Scargle periodogram of `y` (B, N) under the factored covariance, (B, F): for each ANGULAR trial
         frequency of `freq` ((F,) shared | (B, F)) the model y = mean + A beta0 + alpha cos w(t - t_ref) + beta sin w(t - t_ref)
         + GP is fitted by generalized least squares and compared with the fit without the sinusoid (chi2_null - chi2 = dchi2).
@@ -402,8 +402,17 @@ class GaussianProcess:
         (B, F, .) arrays (celerite2_amd/periodogram.py has the formulas).  Not differentiable and never raising under
         compute(..., quiet=True): a frequency at which the sinusoid is not identifiable (w = 0 beside a constant column),
         a series whose factorisation failed or whose A is rank-deficient, and every frequency when N < P0 + 3 hold NaN.
-        Times with a large offset keep their phase accuracy with `t_ref` at the offset.  J <= 32."""
-        from . import periodogram as pg, significance as sg
+        Times with a large offset keep their phase accuracy with `t_ref` at the offset.  J <= 32.
+        `nterms` = H in 2 .. 4: the MULTI-HARMONIC periodogram -- the model carries alpha_h cos x_h + beta_h sin x_h for
+        h = 1 .. H, harmonic h at the frequency h w, fitted jointly (ops.whitened_harmonics, one sweep with H lanes per
+        frequency; celerite2_amd/harmonics.py has the formulas) -- and `return_fit=True` gives harmonics.Harmonics(power
+        (B, F), amplitude (B, F, 2 H) = (alpha_1, beta_1, ..., alpha_H, beta_H), chi2_null (B,)); a frequency at which a
+        harmonic aliases onto the constant or onto another harmonic, and every frequency when N < P0 + 2 H + 1, hold NaN;
+        harmonics.waveform evaluates the fitted periodic part.  nterms = 1 is the one-term path, untouched."""
+        from . import harmonics as hm, periodogram as pg, significance as sg
+
+        if isinstance(nterms, bool) or not isinstance(nterms, int) or not 1 <= nterms <= ops.HARMONICS_MAX:
+            raise ValueError("nterms must be an integer from 1 to %d (got %r)" % (ops.HARMONICS_MAX, nterms))
 
         self._need()
         self._check_vector(y)
@@ -412,6 +421,10 @@ class GaussianProcess:
             raise ValueError("normalization must be one of %s" % (pg.NORMALIZATIONS,))
         freq = sg.check_trials("periodogram", freq, B, "freq", "F")
         Z0 = self._whitened_columns(y, A)
+        if nterms > 1:
+            T = ops.whitened_harmonics(self._t, self._c, self._U, self._W, self._d, Z0, freq, nterms, t_ref=t_ref)
+            fit = self._nan_failed_fit(hm.finish(hm.null_products(Z0, self._d), T, N, nterms, normalization, ok=self._flag == 0))
+            return fit if return_fit else fit.power
         T = ops.whitened_sinusoids(self._t, self._c, self._U, self._W, self._d, Z0, freq, t_ref=t_ref)
         fit = self._nan_failed_fit(pg.finish(pg.null_products(Z0, self._d), T, N, normalization, ok=self._flag == 0))
         return fit if return_fit else fit.power

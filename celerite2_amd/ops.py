@@ -10,6 +10,7 @@ streams); the arithmetic is in the gfx950 kernels.
 """
 import collections
 import ctypes
+import re
 
 import torch
 
@@ -28,7 +29,8 @@ __all__ = [
 ]
 # (`whitened_gram`, `whitened_sinusoids`, `whitened_transits`, `whitened_keplerians` and `trial_projections`, the ops of
 # include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h, celerite2_amd_kepler.h and
-# celerite2_amd_trials.h, are public as well; they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
+# celerite2_amd_trials.h, are public as well, and so is `whitened_harmonics` of celerite2_amd_harmonics.h
+# (_lib.HARMONICS_SYMBOLS); they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
 # _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
 # include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS)
 
@@ -473,9 +475,10 @@ def _bank(shapes, B):
     return NS, S, 0 if shapes.dim() == 2 else NS * S
 
 
-def _whitened(op, kind, t, c, U, W, d, Z0, trials, out, *, t_ref=None, shapes=None, name="trials", k="K"):
-    """The sweep c2_<op> of one kind of _TRIAL_TABLE: T (B, K, width).  `t_ref` goes before T in the call, the bank after it."""
-    kd = _TRIAL_TABLE[kind]
+def _whitened(op, kind, t, c, U, W, d, Z0, trials, out, *, t_ref=None, shapes=None, name="trials", k="K", count=()):
+    """The sweep c2_<op> of one kind of _TRIAL_TABLE (or a _TrialKind outside it): T (B, K, width).  `count`: integers that
+    follow K in the call; `t_ref` goes before T, the bank after it."""
+    kd = _TRIAL_TABLE[kind] if isinstance(kind, str) else kind
     B, N, J = _dims(U)
     if Z0.dim() != 3:
         raise ValueError("Invalid shape: Z0 (must be (B, N, Q0))")
@@ -492,7 +495,7 @@ def _whitened(op, kind, t, c, U, W, d, Z0, trials, out, *, t_ref=None, shapes=No
     if out is None:
         out, = _empty(U.device, dims, "BKR")
     _args(dims, ins, [("out", out, "BKR")])
-    rc = getattr(_lib.load(), "c2_" + op)(B, N, J, Q0, K, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials, tr_bs,
+    rc = getattr(_lib.load(), "c2_" + op)(B, N, J, Q0, K, *count, t, _bs(t, N), c, _bs(c, J), U, W, d, Z0, trials, tr_bs,
                                           *(() if t_ref is None else (float(t_ref),)), out, *bank, _stream())
     _lib.check(rc, op)
     return out
@@ -534,6 +537,29 @@ def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
     accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  J <= 32 and 1 <= Q0 <= 8.
     No atomics: two calls give identical bits."""
     return _whitened("whitened_sinusoids", "periodogram", t, c, U, W, d, Z0, freq, out, t_ref=t_ref, name="freq", k="F")
+
+
+# C2_HARMONICS_MAX of include/celerite2_amd_harmonics.h
+HARMONICS_MAX = int(re.search(r"^#define\s+C2_HARMONICS_MAX\s+(\d+)", open(_lib.HARMONICS_HEADER).read(), flags=re.M).group(1))
+
+
+def whitened_harmonics(t, c, U, W, d, Z0, freq, nterms, *, t_ref=0.0, out=None):
+    """T (B, F, H (2 H + 1) + 2 H Q0) for H = `nterms` harmonics of every ANGULAR trial frequency freq ((F,) shared by the batch
+    or (B, F)): with the 2 H columns ordered (c_1, s_1, ..., c_H, s_H), c_h = cos x_h, s_h = sin x_h at the phase of
+    `whitened_sinusoids` for the frequency fl(h w), z_i = L^-1 (column i) and <a, b> = sum_n a_n b_n / d_n,
+
+        T[b, f] = [<z_i, z_j> for 0 <= i <= j < 2 H (row-major over the upper triangle), <z_i, Z0[:, k]> for i < 2 H, k < Q0]
+
+    from the factors (d, W) of `factor` and Z0 (B, N, Q0) = solve_lower of [A0 | y - mean], in one forward sweep that forms
+    the columns in registers, H neighbouring lanes per frequency (c2_whitened_harmonics, csrc/c2_harmonics.hip; the header has
+    the column rule).  nterms = 1 is `whitened_sinusoids` to the bit, and what T holds about harmonic h alone is
+    `whitened_sinusoids` at h * freq to the bit.  What the multi-harmonic periodogram reads (celerite2_amd/harmonics.py).
+    Caller-owned `out` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.
+    1 <= nterms <= 4, J <= 32 and 1 <= Q0 <= 8.  No atomics: two calls give identical bits."""
+    if isinstance(nterms, bool) or not isinstance(nterms, int) or not 1 <= nterms <= HARMONICS_MAX:
+        raise ValueError("nterms must be an integer from 1 to %d (got %r)" % (HARMONICS_MAX, nterms))
+    kind = _TrialKind(None, 1, 2 * nterms, (nterms * (2 * nterms + 1), 2 * nterms), None, False)
+    return _whitened("whitened_harmonics", kind, t, c, U, W, d, Z0, freq, out, t_ref=t_ref, name="freq", k="F", count=(nterms,))
 
 
 def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
