@@ -44,13 +44,6 @@ namespace harmonics {
 // lanes of a trial
 constexpr int group_lanes(int GH, int JR) { return JR >= 32 ? 2 * GH : GH; }
 
-// w_h = fl(h * w): one rounding
-__device__ __forceinline__ double harmonic(int h, double w) {
-#pragma clang fp contract(off)
-  const double wh = (double)h * w;
-  return wh;
-}
-
 // x of the lane at XOR distance D in the group; hm = the half-mirrored x (D >= 4)
 template <int D>
 __device__ __forceinline__ double xchg(double x, double hm) {
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(kWave) void k_harmonic_sweep(int64_t N, int J, int 
   const int g = SPLIT ? m >> 1 : m;                // this lane's harmonic, from 0
   const bool odd = SPLIT && (m & 1);
   const bool live = k < F && g < H;
-  const trial::Sinusoid col(live ? harmonic(g + 1, freq[b * f_bs + k]) : 0.0, {t_ref});
+  const trial::Sinusoid col(live ? pgram::harmonic(g + 1, freq[b * f_bs + k]) : 0.0, {t_ref});   // w_h = fl(h * w)
 
   double Fst[NL][JR], T0[NL][QR], Tsq[NL], z[NL], T01 = 0.0, X[NX];
 #pragma unroll

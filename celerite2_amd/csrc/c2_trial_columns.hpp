@@ -5,11 +5,14 @@
 // bit.  The public headers (celerite2_amd_periodogram.h, _transit.h, _kepler.h, _shapes.h) state the rules line by line;
 // tests/periodogram_ref.py, tests/transit_ref.py, tests/kepler_ref.py and tests/shapes_ref.py restate them.
 //
-// A source states NC (its columns, 1 or 2), WORDS (doubles per trial) and Params (what a launch hands every lane beside the
-// trials); it is built from (this lane's trial -- trial 0 when the lane is beyond K --, live, the series, Params), a lane
-// that is not live taking the INERT trial (all zeros) without reading; columns(t, a[NC]) gives the column values at a time.
+// A source states NC (its columns: 1 or 2; 2 H for H harmonics), WORDS (doubles per trial) and Params (what a launch hands
+// every lane beside the trials); it is built from (this lane's trial -- trial 0 when the lane is beyond K --, live, the
+// series, Params), a lane that is not live taking the INERT trial (all zeros) without reading; columns(t, a[NC]) gives the
+// column values at a time.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #include "c2_common.hpp"
 #include "c2_loglik_helpers.hpp"
@@ -23,6 +26,13 @@ __device__ __forceinline__ double phase(double w, double t, double t_ref) {
   const double dt = t - t_ref;
   const double x = w * dt;
   return x;
+}
+
+// w_h = fl(h * w): harmonic h's frequency (celerite2_amd_harmonics.h), one rounding
+__device__ __forceinline__ double harmonic(int h, double w) {
+#pragma clang fp contract(off)
+  const double wh = (double)h * w;
+  return wh;
 }
 
 }  // namespace pgram
@@ -138,6 +148,29 @@ struct Sinusoid {
   // (a frequency the lane formed itself: harmonic h's fl(h * w) of c2_harmonics.hip)
   __device__ __forceinline__ Sinusoid(double om_, const Params &p) : om(om_), t_ref(p.t_ref) {}
   __device__ __forceinline__ void columns(double t, double (&a)[2]) const { sincos_cw(pgram::phase(om, t, t_ref), a[1], a[0]); }
+};
+
+// (w) and H harmonics: the 2 H columns (c_1, s_1, ..., c_H, s_H) of celerite2_amd_harmonics.h -- H Sinusoids at the
+// frequencies fl(h w), so harmonic h's pair is, bit for bit, the Sinusoid's pair of a trial that holds fl(h w)
+template <int H>
+struct Harmonics {
+  static constexpr int NC = 2 * H, WORDS = 1;
+  typedef Sinusoid::Params Params;
+  Sinusoid s[H];
+  template <int... I>
+  __device__ __forceinline__ Harmonics(double w, const Params &p, std::integer_sequence<int, I...>)
+      : s{Sinusoid(pgram::harmonic(I + 1, w), p)...} {}
+  __device__ __forceinline__ Harmonics(const double *tr, bool live, int64_t, const Params &p)
+      : Harmonics(live ? tr[0] : 0.0, p, std::make_integer_sequence<int, H>{}) {}
+  __device__ __forceinline__ void columns(double t, double (&a)[2 * H]) const {
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      double pair[2];
+      s[h].columns(t, pair);
+      a[2 * h] = pair[0];
+      a[2 * h + 1] = pair[1];
+    }
+  }
 };
 
 // (P, t0, w, tau): b_n of celerite2_amd_transit.h.  The ramp's division is met only by a wavefront with a lane on an

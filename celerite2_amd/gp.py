@@ -25,10 +25,11 @@ class LinAlgError(Exception):
 
 
 def _significance(self, kind, y, trials, shapes, draws, A, normalization, t_ref, dips_only, generator, normals, max_trials,
-                  max_draws):
+                  max_draws, nterms=1):
     """search_significance and shape_search_significance (`shapes`: its bank, None for the kinds named): what differs
-    between the searches comes from significance.SEARCHES."""
-    from . import _trial_fit, periodogram as pg, significance as sg
+    between the searches comes from significance.SEARCHES.  `nterms` = H > 1 (the periodogram): the multi-harmonic search,
+    whose sweep and finish are harmonics.py's and whose per-draw statistic ops.harmonic_null_chi2 finishes in registers."""
+    from . import _trial_fit, harmonics as hm, periodogram as pg, significance as sg
 
     self._need()
     self._check_vector(y)
@@ -58,8 +59,13 @@ def _significance(self, kind, y, trials, shapes, draws, A, normalization, t_ref,
     ok = self._flag == 0
     Z0 = self._whitened_columns(y, A)
     S0 = _trial_fit.null_products(Z0, self._d)
-    T = search.sweep(self._t, self._c, self._U, self._W, self._d, Z0, trials, t_ref=t_ref, shapes=shapes)
-    statistic, = self._nan_failed(sg.observed_statistic(kind, S0, T, N, normalization, trials, NS, dips_only, ok))
+    if nterms > 1:
+        T = ops.whitened_harmonics(self._t, self._c, self._U, self._W, self._d, Z0, trials, nterms, t_ref=t_ref)
+        statistic, = self._nan_failed(hm.finish(S0, T, N, nterms, normalization, ok=ok).power)
+        factors = hm.null_factors(S0, T, N, nterms, ok)                      # (what no draw changes: once)
+    else:
+        T = search.sweep(self._t, self._c, self._U, self._W, self._d, Z0, trials, t_ref=t_ref, shapes=shapes)
+        statistic, = self._nan_failed(sg.observed_statistic(kind, S0, T, N, normalization, trials, NS, dips_only, ok))
     if normals is None:
         normals = torch.randn((B, N, draws), dtype=torch.float64, device=dev, generator=generator)
     rsd = torch.rsqrt(self._d)[..., None]
@@ -71,10 +77,18 @@ def _significance(self, kind, y, trials, shapes, draws, A, normalization, t_ref,
         s_yy, G0Y = (n * n).sum(dim=1), torch.matmul(ZA, scaled)
         alpha = ops.solve_upper(self._t, self._c, self._U, self._W, scaled)
         best = torch.full((B, n.shape[-1]), -math.inf, dtype=torch.float64, device=dev)
+        if nterms > 1:
+            V, chi2_0 = hm.null_draws(factors, G0Y, s_yy)
         for k0 in range(0, K, kstep):
             tk = (trials[:, k0:k0 + kstep] if per_series else trials[k0:k0 + kstep]).contiguous()
-            P = search.project(self._t, alpha, tk, t_ref=t_ref, shapes=shapes)
-            stat = sg._null_statistics(kind, S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization, tk, NS, dips_only, ok)
+            if nterms > 1:
+                Xt = None if factors.Xt is None else factors.Xt[:, k0:k0 + kstep].contiguous()
+                dchi2 = ops.harmonic_null_chi2(self._t, alpha, tk, nterms, factors.Lm[:, k0:k0 + kstep].contiguous(), Xt, V,
+                                               t_ref=t_ref)
+                stat = hm.normalize(dchi2, chi2_0, normalization)
+            else:
+                P = search.project(self._t, alpha, tk, t_ref=t_ref, shapes=shapes)
+                stat = sg._null_statistics(kind, S0, T[:, k0:k0 + kstep], G0Y, s_yy, P, N, normalization, tk, NS, dips_only, ok)
             best = torch.maximum(best, torch.where(torch.isnan(stat), best[:, None, :], stat).amax(dim=1))
         maxima.append(torch.where(torch.isinf(best) & (best < 0), torch.full_like(best, math.nan), best))
     null_maxima, = self._nan_failed(torch.cat(maxima, dim=1))
@@ -520,7 +534,7 @@ class GaussianProcess:
 
     # -- false-alarm probabilities of the three searches (ops.trial_projections; no counterpart in the reference) -------
     def search_significance(self, kind, y, trials, *, draws=1000, A="mean", normalization="standard", t_ref=0.0,
-                            dips_only=False, generator=None, normals=None, max_trials=None, max_draws=None):
+                            dips_only=False, generator=None, normals=None, max_trials=None, max_draws=None, nterms=1):
         """The search `kind` ("periodogram", "transit" or "keplerian") on `y` (B, N) with the Monte-Carlo false-alarm
         probability of every trial: significance.Significance(statistic (B, K), fap (B, K), null_maxima (B, draws)).
         `trials`: what the search takes -- ANGULAR frequencies (F,) | (B, F) for the periodogram, (K, 4) | (B, K, 4) for the
@@ -544,9 +558,17 @@ class GaussianProcess:
         `max_draws`: take the trials / draws in blocks of at most that many, which bounds the (B, K, C, draws) and
         (B, K, draws) arrays; the result does not depend on `max_trials`, to the bit, and on `max_draws` to rounding (the
         solve may take another kernel at another column count).  `A`, `t_ref`: as for the searches.  Not differentiable
-        and never raising under compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32."""
+        and never raising under compute(..., quiet=True): a series whose factorisation failed holds NaN.  J <= 32.
+        `nterms` = H in 2 .. 4 (the periodogram only): the MULTI-HARMONIC periodogram's significance -- `statistic` is
+        `periodogram(..., nterms=H)`'s power, and the statistic of every (frequency, draw) is finished in the registers of
+        the pass that projects the draws on the 2 H columns (ops.harmonic_null_chi2; harmonics.null_statistics is its
+        torch form), so a draw costs (B, F) values, not (B, F, 2 H).  nterms = 1 is the route above, untouched."""
+        if isinstance(nterms, bool) or not isinstance(nterms, int) or not 1 <= nterms <= ops.HARMONICS_MAX:
+            raise ValueError("nterms must be an integer from 1 to %d (got %r)" % (ops.HARMONICS_MAX, nterms))
+        if nterms > 1 and kind != "periodogram":
+            raise ValueError("nterms = %d needs kind = \"periodogram\" (got %r): the other searches have one term" % (nterms, kind))
         return _significance(self, kind, y, trials, None, draws, A, normalization, t_ref, dips_only, generator, normals, max_trials,
-                                  max_draws)
+                                  max_draws, nterms)
 
     # -- the tabulated-shape search under the factored covariance (ops.whitened_shapes; no counterpart in the reference) --
     def _shape_args(self, trials, shapes):

@@ -32,36 +32,32 @@ from ._trial_fit import null_fit, null_products
 from .autograd import _RANK_TOL
 from .periodogram import NORMALIZATIONS
 
-__all__ = ["Harmonics", "NORMALIZATIONS", "null_products", "finish", "waveform"]
+__all__ = ["Harmonics", "NullFactors", "NORMALIZATIONS", "null_products", "finish", "null_factors", "null_statistics", "waveform"]
 
 Harmonics = collections.namedtuple("Harmonics", "power amplitude chi2_null")
+NullFactors = collections.namedtuple("NullFactors", "Lm Xt L0 singular bad")
 
 
-def finish(S0, T, N, nterms, normalization="standard", ok=None):
-    """Harmonics(power (B, F), amplitude (B, F, 2 H), chi2_null (B,)) from S0 (B, Q0, Q0), T (B, F, H (2 H + 1) + 2 H Q0),
-    the series length N and H = nterms (the module docstring has the formulas).  power: dchi2 / chi2_0 ("standard", in
-    [0, 1]), dchi2 ("chi2") or dchi2 / 2 ("log_likelihood"); amplitude = (alpha_1, beta_1, ..., alpha_H, beta_H).
-    `ok` (B,) | None: series to take at all (the others hold NaN; their S0, T are not read)."""
-    if normalization not in NORMALIZATIONS:
-        raise ValueError("normalization must be one of %s" % (NORMALIZATIONS,))
+def _check_nterms(nterms):
     if isinstance(nterms, bool) or not isinstance(nterms, int) or nterms < 1:
         raise ValueError("nterms must be a positive integer (got %r)" % (nterms,))
-    H, Q0 = nterms, S0.shape[-1]
+
+
+def _factors(S0, T, ok, H):
+    """What `finish` and `null_statistics` share, from S0 (B, Q0, Q0) and T (B, F, H (2 H + 1) + 2 H Q0) alone: (S0, T, bad,
+    chi2_0, v, Xi, L0, L, sing) -- null_fit's S0, T, bad (B,), chi2_0 (B,), v (B, P0) and L0 (B, P0, P0); Xi[i] (B, P0, F) =
+    column i's L0^-1 Gt0^T (None when P0 = 0); L[i][j] (B, F), j <= i, the Cholesky factor of M = Gtt - X^T X, and sing (B, F):
+    a pivot below _RANK_TOL of Gtt's own diagonal entry (that pivot is taken as 1: L stays finite)."""
+    Q0 = S0.shape[-1]
     NC, HEAD = 2 * H, H * (2 * H + 1)
-    S0, T, bad, chi2_0, v, X, _ = null_fit(S0, T, ok, ("F", "H (2 H + 1) + 2 H Q0", HEAD + NC * Q0),
-                                           tuple(HEAD + i * Q0 for i in range(NC)))     # X (B, P0, NC F), column-major
+    S0, T, bad, chi2_0, v, X, L0 = null_fit(S0, T, ok, ("F", "H (2 H + 1) + 2 H Q0", HEAD + NC * Q0),
+                                            tuple(HEAD + i * Q0 for i in range(NC)))    # X (B, P0, NC F), column-major
     P0, F = Q0 - 1, T.shape[1]
-    nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
     one = torch.ones((), dtype=S0.dtype, device=S0.device)
     tri = lambda i, j: i * NC - (i * (i - 1)) // 2 + (j - i)             # (i <= j) of the row-major upper triangle
     Xi = [X[..., i * F:(i + 1) * F] for i in range(NC)] if P0 else None   # (B, P0, F) each
-    # M's lower triangle and r, (B, F) each
-    M = [[None] * NC for _ in range(NC)]
-    r = [None] * NC
+    M = [[None] * NC for _ in range(NC)]                                 # M's lower triangle, (B, F) each
     for i in range(NC):
-        r[i] = T[..., HEAD + i * Q0 + P0]
-        if P0:
-            r[i] = r[i] - (Xi[i] * v[:, :, None]).sum(dim=1)
         for j in range(i + 1):
             M[i][j] = T[..., tri(j, i)]
             if P0:
@@ -80,6 +76,27 @@ def finish(S0, T, N, nterms, normalization="standard", ok=None):
             for k in range(j):
                 x = x - L[i][k] * L[j][k]
             L[i][j] = x / L[j][j]
+    return S0, T, bad, chi2_0, v, Xi, L0, L, sing
+
+
+def finish(S0, T, N, nterms, normalization="standard", ok=None):
+    """Harmonics(power (B, F), amplitude (B, F, 2 H), chi2_null (B,)) from S0 (B, Q0, Q0), T (B, F, H (2 H + 1) + 2 H Q0),
+    the series length N and H = nterms (the module docstring has the formulas).  power: dchi2 / chi2_0 ("standard", in
+    [0, 1]), dchi2 ("chi2") or dchi2 / 2 ("log_likelihood"); amplitude = (alpha_1, beta_1, ..., alpha_H, beta_H).
+    `ok` (B,) | None: series to take at all (the others hold NaN; their S0, T are not read)."""
+    if normalization not in NORMALIZATIONS:
+        raise ValueError("normalization must be one of %s" % (NORMALIZATIONS,))
+    _check_nterms(nterms)
+    H, Q0 = nterms, S0.shape[-1]
+    NC, HEAD = 2 * H, H * (2 * H + 1)
+    S0, T, bad, chi2_0, v, Xi, _, L, sing = _factors(S0, T, ok, H)
+    P0 = Q0 - 1
+    nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
+    r = [None] * NC                                                    # (B, F) each
+    for i in range(NC):
+        r[i] = T[..., HEAD + i * Q0 + P0]
+        if P0:
+            r[i] = r[i] - (Xi[i] * v[:, :, None]).sum(dim=1)
     w = [None] * NC                                                    # L w = r
     dchi2 = torch.zeros_like(r[0])
     for i in range(NC):
@@ -106,6 +123,82 @@ def finish(S0, T, N, nterms, normalization="standard", ok=None):
     power = torch.where(sing, nan, power)
     amplitude = torch.where(sing[..., None], nan, torch.stack(amp, dim=-1))
     return Harmonics(power, amplitude, torch.where(bad, nan, chi2_0))
+
+
+def null_factors(S0, T, N, nterms, ok=None):
+    """NullFactors(Lm, Xt, L0, singular, bad): what does not depend on the draw of the statistic of many series y_r, from the
+    observed call's S0 (B, Q0, Q0) and T (B, F, H (2 H + 1) + 2 H Q0) (only the entries without y are read), in the layout
+    ops.harmonic_null_chi2 takes.  Lm (B, F, H (2 H + 1)): the factor of M = Gtt - X^T X, its lower triangle row-major, NaN
+    throughout at a frequency or in a series that holds NaN (`singular`).  Xt (B, F, 2 H, P0): X = L0^-1 Gt0^T by column, None
+    when P0 = 0.  L0 (B, P0, P0) the factor of G00 (the identity in a bad series; None when P0 = 0).  singular (B, F): M not
+    positive definite, N < P0 + 2 H + 1, or a bad series.  bad (B,): as null_fit has it."""
+    _check_nterms(nterms)
+    H, P0 = nterms, S0.shape[-1] - 1
+    NC = 2 * H
+    S0, T, bad, _, _, Xi, L0, L, sing = _factors(S0, T, ok, H)
+    if N < P0 + NC + 1:
+        sing = torch.ones_like(sing)
+    sing = sing | bad[:, None]
+    nan = torch.full((), math.nan, dtype=S0.dtype, device=S0.device)
+    Lm = torch.stack([L[i][j] for i in range(NC) for j in range(i + 1)], dim=-1)
+    Lm = torch.where(sing[..., None], nan, Lm).contiguous()
+    Xt = torch.stack([x.transpose(1, 2) for x in Xi], dim=2).contiguous() if P0 else None     # (B, F, NC, P0)
+    return NullFactors(Lm, Xt, L0, sing, bad)
+
+
+def null_draws(factors, G0Y, s_yy):
+    """(V (B, P0, R) = L0^-1 g0y_r -- None when P0 = 0 --, chi2_0 (B, R) = s_yy_r - |v_r|^2) of R series from their
+    G0Y (B, P0, R) and s_yy (B, R): the fit without the harmonics, per draw (significance.null_statistics' statements)."""
+    if factors.L0 is None:
+        return None, s_yy
+    G0Y = torch.where(factors.bad[:, None, None], torch.zeros((), dtype=G0Y.dtype, device=G0Y.device), G0Y)
+    V = torch.linalg.solve_triangular(factors.L0, G0Y, upper=False).contiguous()   # (the solver may hand back another layout)
+    return V, s_yy - (V * V).sum(dim=1)
+
+
+def normalize(dchi2, chi2_0, normalization):
+    """dchi2 (B, F, R) of R series in `normalization`, chi2_0 (B, R) their fits without the harmonics."""
+    if normalization == "standard":
+        return dchi2 / chi2_0[:, None, :]
+    return dchi2 if normalization == "chi2" else 0.5 * dchi2
+
+
+def null_statistics(S0, T, G0Y, s_yy, P, N, nterms, *, normalization="standard", ok=None):
+    """The multi-harmonic statistic of R series at once, (B, F, R), in plain torch: the many-y form of `finish`, with its
+    statements.  S0 (B, Q0, Q0) and T (B, F, H (2 H + 1) + 2 H Q0) of the observed call (only S0's A0 block and T's entries
+    without y are read); G0Y (B, P0, R) = g0y_r and s_yy (B, R) of the R series; P (B, F, 2 H, R) = gty_r
+    (ops.harmonic_projections); N the series length; H = nterms.  Per draw r and frequency, for i = 0 .. 2 H - 1 ascending,
+
+        v_r = L0^-1 g0y_r,   chi2_0_r = s_yy_r - |v_r|^2,   r_i = gty_i - sum_p X[p, i] v_r[p]  (p ascending),
+        w_i = (r_i - sum_{k < i} L_ik w_k) / L_ii,           dchi2 = sum_i w_i^2
+
+    then the normalisation: what ops.harmonic_null_chi2 finishes in registers without P in memory.  NaN as `finish` has it:
+    a frequency whose M is not positive definite, every frequency when N < P0 + 2 H + 1, a bad series.  With R = 1 and the
+    series' own products this is `finish`'s power; nterms = 1 is significance.null_statistics("periodogram", ...)."""
+    if normalization not in NORMALIZATIONS:
+        raise ValueError("normalization must be one of %s" % (NORMALIZATIONS,))
+    fac = null_factors(S0, T, N, nterms, ok)
+    NC, (B, F), P0 = 2 * nterms, fac.Lm.shape[:2], S0.shape[-1] - 1
+    if P.dim() != 4 or tuple(P.shape[:3]) != (B, F, NC):
+        raise ValueError("Invalid shape: P (must be (B, F, 2 H, R) = (%d, %d, %d, R))" % (B, F, NC))
+    R = P.shape[-1]
+    if tuple(s_yy.shape) != (B, R) or tuple(G0Y.shape) != (B, P0, R):
+        raise ValueError("Invalid shape: s_yy, G0Y (must be (B, R) and (B, P0, R) = (%d, %d) and (%d, %d, %d))" % (B, R, B, P0, R))
+    V, chi2_0 = null_draws(fac, G0Y, s_yy)
+    w = [None] * NC
+    dchi2 = torch.zeros_like(P[:, :, 0])
+    for i in range(NC):
+        x = P[:, :, i]
+        if P0:                                                         # (one term after the other: significance._xtv)
+            xv = fac.Xt[:, :, i, 0, None] * V[:, 0, None, :]
+            for p in range(1, P0):
+                xv = xv + fac.Xt[:, :, i, p, None] * V[:, p, None, :]
+            x = x - xv
+        for k in range(i):
+            x = x - fac.Lm[..., i * (i + 1) // 2 + k, None] * w[k]
+        w[i] = x / fac.Lm[..., i * (i + 1) // 2 + i, None]
+        dchi2 = dchi2 + w[i] * w[i]
+    return normalize(dchi2, chi2_0, normalization)
 
 
 def waveform(amplitude, freq, t, *, t_ref=0.0):

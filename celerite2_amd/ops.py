@@ -562,6 +562,67 @@ def whitened_harmonics(t, c, U, W, d, Z0, freq, nterms, *, t_ref=0.0, out=None):
     return _whitened("whitened_harmonics", kind, t, c, U, W, d, Z0, freq, out, t_ref=t_ref, name="freq", k="F", count=(nterms,))
 
 
+# H -> C2_HARMONIC_DRAWS_H of include/celerite2_amd_harmonic_trials.h: the draws a wavefront takes
+HARMONIC_DRAWS = {int(h): int(v) for h, v in re.findall(r"^#define\s+C2_HARMONIC_DRAWS_(\d+)\s+(\d+)",
+                                                         open(_lib.HARMONIC_TRIALS_HEADER).read(), flags=re.M)}
+_HARMONIC_MAX_P0 = 7
+
+
+def _harmonic_trials(t, alpha, freq, nterms):
+    """(dims, the entries of t, alpha, freq, freq's batch stride) of the two ops of celerite2_amd_harmonic_trials.h."""
+    if isinstance(nterms, bool) or not isinstance(nterms, int) or not 1 <= nterms <= HARMONICS_MAX:
+        raise ValueError("nterms must be an integer from 1 to %d (got %r)" % (HARMONICS_MAX, nterms))
+    if alpha.dim() != 3:
+        raise ValueError("Invalid shape: alpha (must be (B, N, R))")
+    B, N, R = alpha.shape
+    K, spec, f_bs = _trial_grid(_TRIAL_TABLE["periodogram"], freq, "freq", "F")
+    dims = dict(B=B, N=N, R=R, K=K, C=2 * nterms, L=nterms * (2 * nterms + 1))
+    return dims, [("t", t, _T), ("alpha", alpha, "BNR"), ("freq", freq, spec)], f_bs
+
+
+def harmonic_projections(t, alpha, freq, nterms, *, t_ref=0.0, out=None):
+    """P (B, F, 2 H, R): P[b, f, i, r] = sum_n col_i(f; t[b, n]) alpha[b, n, r] for alpha (B, N, R), t (N,) shared by the
+    batch or (B, N), the ANGULAR frequencies freq (F,) | (B, F) and H = `nterms` harmonics, the columns ordered
+    (c_1, s_1, ..., c_H, s_H) as `whitened_harmonics` has them: `trial_projections("periodogram", ...)` at every h * freq in
+    one pass over alpha (c2_harmonic_projections, csrc/c2_harmonic_trials.hip), and P[:, :, 2 h - 2:2 h] is that call's result
+    to the bit.  Caller-owned `out` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an
+    input.  1 <= nterms <= 4.  No atomics: two calls give identical bits."""
+    dims, ins, f_bs = _harmonic_trials(t, alpha, freq, nterms)
+    if out is None:
+        out, = _empty(alpha.device, dims, "BKCR")
+    _args(dims, ins, [("out", out, "BKCR")])
+    B, N, R, F = dims["B"], dims["N"], dims["R"], dims["K"]
+    rc = _lib.load().c2_harmonic_projections(B, N, F, nterms, R, t, _bs(t, N), freq, f_bs, float(t_ref), alpha, out, _stream())
+    _lib.check(rc, "harmonic_projections")
+    return out
+
+
+def harmonic_null_chi2(t, alpha, freq, nterms, Lm, Xt=None, V=None, *, t_ref=0.0, out=None):
+    """D (B, F, R): the multi-harmonic dchi2 of R series at every frequency, finished in registers from the projections of
+    `harmonic_projections` without writing them (c2_harmonic_null_chi2, csrc/c2_harmonic_trials.hip; the header has the
+    rule line by line).  alpha (B, N, R), t, freq, nterms as there; Lm (B, F, H (2 H + 1)), Xt (B, F, 2 H, P0) and V (B, P0, R)
+    as harmonics.null_factors and harmonics.null_draws give them (Xt and V None when P0 = 0; P0 <= 7).  NaN in Lm at a
+    frequency gives NaN at every draw of that frequency and nowhere else.  What gp.search_significance(..., nterms=H) reads.
+    Caller-owned `out` is accepted (nothing is allocated then: capturable in a HIP graph); it must not alias an input.  No
+    atomics: two calls give identical bits."""
+    dims, ins, f_bs = _harmonic_trials(t, alpha, freq, nterms)
+    if (Xt is None) != (V is None):
+        raise ValueError("Invalid shape: Xt, V (both None when P0 = 0, else (B, F, 2 H, P0) and (B, P0, R))")
+    P0 = 0 if V is None else (V.shape[1] if V.dim() == 3 else -1)
+    if not 0 <= P0 <= _HARMONIC_MAX_P0:
+        raise ValueError("Invalid shape: V (must be (B, P0, R) with P0 <= %d)" % _HARMONIC_MAX_P0)
+    dims["P"] = P0
+    ins += [("Lm", Lm, "BKL"), ("Xt", Xt, "BKCP"), ("V", V, "BPR")]
+    if out is None:
+        out, = _empty(alpha.device, dims, "BKR")
+    _args(dims, ins, [("out", out, "BKR")])
+    B, N, R, F = dims["B"], dims["N"], dims["R"], dims["K"]
+    rc = _lib.load().c2_harmonic_null_chi2(B, N, F, nterms, R, P0, t, _bs(t, N), freq, f_bs, float(t_ref), alpha, Lm, Xt, V, out,
+                                           _stream())
+    _lib.check(rc, "harmonic_null_chi2")
+    return out
+
+
 def whitened_transits(t, c, U, W, d, Z0, trials, *, out=None):
     """T (B, K, 1 + Q0): for every series and every trial (period P, epoch t0, duration w, ingress tau) of `trials` ((K, 4)
     shared by the batch or (B, K, 4)), with z = L^-1 b_k(t) and <a, b> = sum_n a_n b_n / d_n,
