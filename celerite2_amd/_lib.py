@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
 celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h, celerite2_amd_shapes.h,
-celerite2_amd_harmonics.h and celerite2_amd_harmonic_trials.h).
+celerite2_amd_harmonics.h, celerite2_amd_harmonic_trials.h and celerite2_amd_filter.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -22,6 +22,7 @@ TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_t
 SHAPES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_shapes.h")   # the tabulated-shape search
 HARMONICS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_harmonics.h")   # the multi-harmonic periodogram
 HARMONIC_TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_harmonic_trials.h")   # ... and its null draws
+FILTER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter.h")   # streaming updates
 
 
 class BackendError(RuntimeError):
@@ -124,6 +125,9 @@ HARMONICS_SYMBOLS = ["c2_whitened_harmonics"]
 # Every symbol include/celerite2_amd_harmonic_trials.h declares (checked by tests/test_harmonic_significance.py).
 HARMONIC_TRIALS_SYMBOLS = ["c2_harmonic_projections", "c2_harmonic_null_chi2"]
 
+# Every symbol include/celerite2_amd_filter.h declares (checked by tests/test_filter.py).
+FILTER_SYMBOLS = ["c2_filter_state_words", "c2_filter_append", "c2_filter_absorb", "c2_filter_forecast"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -195,6 +199,7 @@ def load():
     protos.update(_prototypes(_header(SHAPES_HEADER)))
     protos.update(_prototypes(_header(HARMONICS_HEADER)))
     protos.update(_prototypes(_header(HARMONIC_TRIALS_HEADER)))
+    protos.update(_prototypes(_header(FILTER_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

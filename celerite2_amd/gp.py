@@ -297,6 +297,21 @@ class GaussianProcess:
         r = ops.explained_variance(self._t, ts, self._c, self._U, self._W, self._d, Us, Vs)
         return self._nan_failed(cond.mean, cond._k0() - r)
 
+    # -- streaming updates (stream.Filter; no counterpart in the reference) ------------------------------------------------
+    def filter(self, y):
+        """A stream.Filter that has absorbed the computed series and the data `y` (B, N): one solve_lower and one absorb
+        of the d, W already factored -- nothing is refactored.  Rows are then appended in O(M J^2) each
+        (Filter.append).  A series whose factorisation failed gets a NaN state."""
+        from .stream import Filter
+
+        self._need()
+        self._check_vector(y)
+        z = ops.solve_lower(self._t, self._c, self._U, self._W, (y - self.mean)[..., None].contiguous())[..., 0].contiguous()
+        state = ops.filter_init(self._diag.shape[0], self._U.shape[-1], self._diag.device)
+        ops.filter_absorb(state, self._t, self._c, self._W, self._d, z, out=state)
+        state.masked_fill_((self._flag != 0)[:, None], math.nan)
+        return Filter(self.kernel, state, mean=self.mean)
+
     def predict_kernel(self, y, t, *, jitter=None):
         """The conditional mean (B, M) at the sorted times `t` ((M,) shared or (B, M)), mean included, as a differentiable
         function of the kernel's tensor hyper-parameters, of `jitter`, of a tensor `mean`, of `y` and of the times:

@@ -32,7 +32,9 @@ __all__ = [
 # celerite2_amd_trials.h, are public as well, and so is `whitened_harmonics` of celerite2_amd_harmonics.h
 # (_lib.HARMONICS_SYMBOLS); they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
 # _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
-# include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS)
+# include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS, and
+# `filter_state_words`, `filter_init`, `filter_append`, `filter_absorb` and `filter_forecast` of celerite2_amd_filter.h,
+# _lib.FILTER_SYMBOLS)
 
 
 def _p(x):
@@ -1447,3 +1449,101 @@ def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=Tr
     term_coefficients_rev(program, P, work["cots"], tflag=tflag, lflag=flag, ll=ll, out=bP)
     noise_mean_rev(jitter, bdiag, by, flag=flag, out=(bj, bm))
     return ll, (bP, bj, bm, bx, bdiag, by), flag
+
+
+# ---- streaming updates (include/celerite2_amd_filter.h, csrc/c2_filter.hip; _lib.FILTER_SYMBOLS) ----------------------------
+_FILTER_ROWS = dict(t="M|BM", c=_C)   # the new rows' times and the rates; everything else of a row is per series
+
+
+def filter_state_words(J):
+    """Doubles per series of a filter state, 4 + J + J^2 (t_last, n, sum log d, sum z^2 / d, F, S); 0 beyond J = 32."""
+    return int(_lib.load().c2_filter_state_words(int(J)))
+
+
+def filter_init(B, J, device):
+    """The empty state of B series of width J: zeros (B, SW), n = 0."""
+    SW = filter_state_words(J)
+    if SW == 0:
+        raise ValueError("celerite2_amd.filter_init: width not supported (1 <= J <= %d)" % _lib.C2_FAST_WIDTH)
+    return torch.zeros((int(B), SW), dtype=torch.float64, device=device)
+
+
+def _filter_dims(X, name):
+    if X.dim() != 3:
+        raise ValueError("Invalid shape: %s (must be (B, M, J))" % name)
+    B, M, J = X.shape
+    return dict(B=B, M=M, J=J, S=4 + J + J * J)
+
+
+def _filter_count(count, dims, dev):
+    if count is None:
+        return
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.device == dev):
+        raise ValueError("celerite2_amd filter ops need `count` as a contiguous int32 tensor on the same device")
+    if tuple(count.shape) != (dims["B"],):
+        raise ValueError("Invalid shape: count (got %s, expected %s)" % (tuple(count.shape), (dims["B"],)))
+
+
+def _filter_out(state, out):
+    """The output state: `state` itself (in place), or a tensor of its own."""
+    if out is None:
+        return torch.empty_like(state)
+    if out is not state and out.data_ptr() == state.data_ptr():
+        raise ValueError("Invalid argument: out must be state itself or must not overlap it")
+    return out
+
+
+def filter_append(state, t, c, a, U, V, y, *, count=None, out=None, d=None, W=None, z=None):
+    """Append up to M rows per series to a filter state in O(M J^2) (c2_filter_append): t (M,) | (B, M), c (J,) | (B, J),
+    a, y (B, M), U, V (B, M, J) -> (state, d, W, z, flag) with the d, W, z rows that `factor` and `solve_lower` of the whole
+    series would give -- d the one-step-ahead predictive variance, z the innovation.  `count` (B,) int32: rows m >= count[b]
+    are not read and their outputs are not written; a series with count 0 keeps its state bit for bit.  flag (B,) int32:
+    the 1-based row of this call whose d <= 0 (the rows before it are written, the series' state stays as on entry), else 0.
+    `out` may be `state` (in place); caller-owned `d`, `W`, `z` are accepted and must not alias an input.  J <= 32.
+    The times must be sorted and not before the state's t_last: not checked here (celerite2_amd.stream.Filter does)."""
+    dims = _filter_dims(U, "U")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    out = _filter_out(state, out)
+    d = torch.empty_like(a) if d is None else d
+    W = torch.empty_like(V) if W is None else W
+    z = torch.empty_like(y) if z is None else z
+    ins = [("state", state, "BS"), ("out", out, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("a", a, "BM"), ("U", U, "BMJ"),
+           ("V", V, "BMJ"), ("y", y, "BM")]
+    _args(dims, ins, [("d", d, "BM"), ("W", W, "BMJ"), ("z", z, "BM")])
+    _filter_count(count, dims, U.device)
+    flag = _flag(B, U.device)
+    rc = _lib.load().c2_filter_append(B, M, J, state, out, t, _bs(t, M), c, _bs(c, J), a, U, V, y, count, d, W, z, flag, _stream())
+    _lib.check(rc, "filter_append")
+    return out, d, W, z, flag
+
+
+def filter_absorb(state, t, c, W, d, z, *, count=None, out=None):
+    """Absorb rows of an existing factorisation -- W (B, M, J), d (B, M) of `factor`, z (B, M) of `solve_lower` -- into a
+    filter state without refactoring (c2_filter_absorb): only the decay and the update of the state are applied.  Returns the
+    new state; `out` may be `state`; `count` as in filter_append."""
+    dims = _filter_dims(W, "W")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    out = _filter_out(state, out)
+    _args(dims, [("state", state, "BS"), ("out", out, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("W", W, "BMJ"),
+                 ("d", d, "BM"), ("z", z, "BM")])
+    _filter_count(count, dims, W.device)
+    rc = _lib.load().c2_filter_absorb(B, M, J, state, out, t, _bs(t, M), c, _bs(c, J), W, d, z, count, _stream())
+    _lib.check(rc, "filter_absorb")
+    return out
+
+
+def filter_forecast(state, t, c, a, U, *, count=None, mu=None, var=None):
+    """(mu, var) (B, M) at M query rows per series, each independently from the same unchanged state (c2_filter_forecast):
+    mu = u^T (p o F), var = a - u^T ((p p^T) o S) u, p = exp(-c (t - t_last)).  For t >= t_last this is the full conditional
+    given all absorbed rows (earlier times are not checked and give no conditional).  Rows m >= count[b] are not read and
+    not written."""
+    dims = _filter_dims(U, "U")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    mu = torch.empty_like(a) if mu is None else mu
+    var = torch.empty_like(a) if var is None else var
+    _args(dims, [("state", state, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("a", a, "BM"), ("U", U, "BMJ")],
+          [("mu", mu, "BM"), ("var", var, "BM")])
+    _filter_count(count, dims, U.device)
+    rc = _lib.load().c2_filter_forecast(B, M, J, state, t, _bs(t, M), c, _bs(c, J), a, U, count, mu, var, _stream())
+    _lib.check(rc, "filter_forecast")
+    return mu, var
