@@ -16,6 +16,10 @@ through `general_matmul_lower` / `general_matmul_upper` and their reverse sweep 
 Gram matrix [A | y]^T (K + D)^-1 [A | y] in one forward sweep (csrc/c2_gram.hip), generalized least squares on it, and the
 likelihood with the linear coefficients profiled or marginalised out.
 
+`filter_append[_kernel]` is a streaming append (csrc/c2_filter.hip) with its reverse (csrc/c2_filter_rev.hip): the cotangent of
+a filter state is carried from one call to the previous one, so the predictive log density of each night's rows trains the
+hyper-parameters without revisiting the old rows.
+
 `factor`, `solve_lower`, `solve_upper`, `matmul_lower`, `matmul_upper` are the reference's five differentiable ops
 (python/celerite2/pymc/ops.py:61-141, jax/ops.py:33-172: forward = `backprop.<op>_fwd` with its workspace, gradient =
 `backprop.<op>_rev`), batched, on the device kernels -- for models that compose the ops themselves."""
@@ -26,7 +30,7 @@ import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "whitened_gram", "gls", "marginal_log_likelihood_kernel", "LinearFit", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "whitened_gram", "gls", "marginal_log_likelihood_kernel", "filter_append", "filter_append_kernel", "LinearFit", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -764,3 +768,63 @@ def marginal_log_likelihood_kernel(kernel, x, y, A, *, yerr=None, diag=None, jit
     a, U, V = get_celerite_matrices(ar, ac, bc, dc, x, D)
     fit = gls(x, c, a, U, V, A, r, prior_mean=prior_mean, prior_precision=prior_precision)
     return fit.log_likelihood if profiled else fit.marginal_log_likelihood
+
+
+# ---- streaming updates (csrc/c2_filter.hip forward, csrc/c2_filter_rev.hip backward) -------------------------------------------
+class _FilterAppend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, t, c, a, U, V, y, count):
+        args = [x.detach().contiguous() for x in (state, t, c, a, U, V, y)]
+        out, d, W, z, flag = ops.filter_append(*args, count=count)   # out of place: the entry state is what backward reads
+        ctx.count = count
+        ctx.save_for_backward(args[0], args[1], args[2], args[4], W, d, z, flag)
+        ctx.mark_non_differentiable(flag)
+        return out, d, W, z, flag
+
+    @staticmethod
+    def backward(ctx, bstate, bd, bW, bz, _bflag=None):
+        state, t, c, U, W, d, z, flag = ctx.saved_tensors
+        bsi, bt, bc, ba, bU, bV, by = ops.filter_append_rev(state, t, c, U, W, d, z, flag, bstate.contiguous(), bd.contiguous(),
+                                                            bW.contiguous(), bz.contiguous(), count=ctx.count)
+        return bsi, _reduce(bt, t), _reduce(bc, c), ba, bU, bV, by, None
+
+
+def filter_append(state, t, c, a, U, V, y, *, count=None):
+    """ops.filter_append out of place, -> (state_out, d, W, z, flag), differentiable in state, t, c, a, U, V, y
+    (c2_filter_append_rev; shared t / c receive the batch sum).  The cotangent of a state is carried from one call to the
+    previous one, so a loss on a later state -- -(1/2) ([3] + [2] + n log 2 pi) of its words is the log-likelihood of every
+    row absorbed -- or on the d and z of any call flows back through as many calls as states were kept; `state.detach()`
+    cuts it.  The rows m >= count[b] of d, W, z are uninitialised and receive no gradient.  flag (B,) int32 is not
+    differentiable and nothing is raised: a series whose call failed (flag != 0) keeps its state, passes its state
+    cotangent through and gives zero row gradients; the others are untouched.  J <= 32."""
+    return _FilterAppend.apply(state, t, c, a, U, V, y, count)
+
+
+def filter_append_kernel(kernel, state, t_new, y_new, *, yerr=None, diag=None, jitter=None, mean=None, count=None):
+    """`filter_append` as a differentiable function of the HYPER-PARAMETERS, with `log_likelihood_kernel`'s conventions
+    (tensor parameters of `kernel`, TermExpr kernels with their diagonal shift, `jitter` in quadrature, `mean` subtracted):
+    the rows t_new (M,) | (B, M), y_new (B, M) with noise yerr | diag (B, M) appended to `state` -> (state_out, d, W, z, flag).
+    Differentiable in the parameters, jitter, mean, the state, t_new, y_new and the noise.  The chain term_coefficients ->
+    get_celerite_matrices -> `filter_append`, c built in torch.  A kernel with a TermConvolution anywhere in it is refused.
+    J <= 32."""
+    if (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, M) is required")
+    if y_new.dim() != 2:
+        raise ValueError("Invalid shape: y_new (must be (B, M))")
+    if t_new.dim() not in (1, 2) or (t_new.dim() == 2 and t_new.shape[0] != y_new.shape[0]):
+        raise ValueError("Invalid shape: t_new (must be (M,) or (B, M))")
+    if _has_convolution(kernel):
+        raise ValueError("filter_append_kernel does not take a kernel with a TermConvolution in it (not semiseparable inside "
+                         "the exposure window): use predict(y, t, return_var=True)")
+    B = y_new.shape[0]
+    if not kernel._has_tensors():
+        raise TypeError("filter_append_kernel: the kernel has no tensor parameter (give its parameters as device tensors)")
+    ar, cr, ac, bc, cc, dc, shift = term_coefficients(kernel.program, kernel.parameter_matrix(B), B, with_shift=True)
+    D = (yerr * yerr if diag is None else diag) + shift[:, None]
+    jitter, mean = _per_series(jitter, B, y_new), _per_series(mean, B, y_new)
+    if jitter is not None:
+        D = D + (jitter * jitter)[:, None]
+    r = y_new if mean is None else y_new - mean[:, None]
+    c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
+    a, U, V = get_celerite_matrices(ar, ac, bc, dc, t_new, D)
+    return filter_append(state, t_new, c, a, U, V, r, count=count)

@@ -304,6 +304,8 @@ class GaussianProcess:
         (Filter.append).  A series whose factorisation failed gets a NaN state."""
         from .stream import Filter
 
+        if self.kernel._has_tensors():
+            raise ValueError("gp.filter does not take a kernel with tensor hyper-parameters (use stream.Filter.empty)")
         self._need()
         self._check_vector(y)
         z = ops.solve_lower(self._t, self._c, self._U, self._W, (y - self.mean)[..., None].contiguous())[..., 0].contiguous()

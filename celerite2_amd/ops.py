@@ -34,7 +34,8 @@ __all__ = [
 # _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
 # include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS, and
 # `filter_state_words`, `filter_init`, `filter_append`, `filter_absorb` and `filter_forecast` of celerite2_amd_filter.h,
-# _lib.FILTER_SYMBOLS)
+# _lib.FILTER_SYMBOLS, and `filter_rev_workspace_words` and `filter_append_rev` of celerite2_amd_filter_rev.h,
+# _lib.FILTER_REV_SYMBOLS)
 
 
 def _p(x):
@@ -1547,3 +1548,39 @@ def filter_forecast(state, t, c, a, U, *, count=None, mu=None, var=None):
     rc = _lib.load().c2_filter_forecast(B, M, J, state, t, _bs(t, M), c, _bs(c, J), a, U, count, mu, var, _stream())
     _lib.check(rc, "filter_forecast")
     return mu, var
+
+
+# ---- reverse of the append (include/celerite2_amd_filter_rev.h, csrc/c2_filter_rev.hip; _lib.FILTER_REV_SYMBOLS) -----------
+_FILTER_REV_OUT = dict(bstate_in="BS", bt="BM", bc="BJ", ba="BM", bU="BMJ", bV="BMJ", by="BM")   # bt, bc: per series always
+
+
+def filter_rev_workspace_words(J):
+    """Doubles of scratch per row of filter_append_rev, J + J^2 (the F and S the row starts from); 0 beyond J = 32."""
+    return int(_lib.load().c2_filter_rev_workspace_words(int(J)))
+
+
+def filter_append_rev(state, t, c, U, W, d, z, flag, bstate, bd=None, bW=None, bz=None, *, count=None, ws=None, out=None):
+    """Reverse of filter_append (c2_filter_append_rev): `state` (B, SW) the state the forward call STARTED from, t, c, U,
+    count as given to it, W, d, z, flag as it returned them; cotangents bstate (B, SW) of the state it left and bd, bz (B, M),
+    bW (B, M, J) of its rows (None = 0) -> (bstate_in (B, SW), bt (B, M), bc (B, J), ba (B, M), bU, bV (B, M, J), by (B, M)).
+    bt and bc come out PER SERIES also when t or c are shared.  The S block of a state cotangent is the symmetric
+    representative: the incoming one is replaced by (B + B^T) / 2.  Word [0] of bstate is added to bt of the last taken row;
+    rows m >= count[b] get zeros; a series with count 0 or flag != 0 gets bstate_in = bstate and zeros.  `ws`
+    (B, M, J + J^2): scratch of this call (allocated when None); `out`: the seven outputs, caller-owned (they may be
+    uninitialised, and must not alias an input).  J <= 32."""
+    dims = _filter_dims(U, "U")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    dims["X"] = J + J * J
+    ws = _empty(U.device, dims, "BMX")[0] if ws is None else ws
+    out = _empty(U.device, dims, *_FILTER_REV_OUT.values()) if out is None else tuple(out)
+    if len(out) != len(_FILTER_REV_OUT):
+        raise ValueError("Invalid argument: out must be (bstate_in, bt, bc, ba, bU, bV, by)")
+    ins = [("state", state, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("U", U, "BMJ"), ("W", W, "BMJ"), ("d", d, "BM"),
+           ("z", z, "BM"), ("bstate", bstate, "BS"), ("bd", bd, "BM"), ("bW", bW, "BMJ"), ("bz", bz, "BM")]
+    _args(dims, ins, [("ws", ws, "BMX")] + _named(_FILTER_REV_OUT, out))
+    _filter_count(count, dims, U.device)
+    _filter_count(flag, dims, U.device)
+    rc = _lib.load().c2_filter_append_rev(B, M, J, state, t, _bs(t, M), c, _bs(c, J), U, W, d, z, count, flag, bstate, bd, bW, bz,
+                                          ws, *out, _stream())
+    _lib.check(rc, "filter_append_rev")
+    return out

@@ -11,7 +11,20 @@ its one-step-ahead predictive variance and its innovation: z / sqrt(d) is the an
     mu, var = flt.forecast(t_query)
     flt.log_likelihood                        # (B,), that of every row absorbed so far
 
-No gradients, and no kernels with tensor hyper-parameters: both are out of scope here."""
+A kernel with TENSOR hyper-parameters (and a tensor `mean`, a `jitter`) makes the filter differentiable: `append` then goes
+through autograd.filter_append_kernel (reverse: csrc/c2_filter_rev.hip) and REBINDS `flt.state` instead of writing it in
+place, the Update it returns and `flt.log_likelihood` carry a graph, and the gradient flows back through as many appends as
+the graph holds -- `flt.detach()` cuts it at the present state, for truncated back-propagation night by night:
+
+    flt = Filter.empty(kernel, B, mean=mean, jitter=jitter)   # kernel = terms.SHOTerm(S0=S0, ...) with device tensors
+    for t_new, y_new, e_new in nights:
+        before = flt.log_likelihood
+        flt.append(t_new, y_new, yerr=e_new)
+        (before - flt.log_likelihood).sum().backward()        # minus tonight's predictive log density
+        optimiser.step(); optimiser.zero_grad(); flt.detach()
+
+`forecast` works on such a filter but returns detached values (its reverse is not written).  A filter on a plain kernel
+behaves as before: in place, no graph."""
 import collections
 import math
 
@@ -23,23 +36,29 @@ Update = collections.namedtuple("Update", "innovation variance score flag")
 
 
 class Filter:
-    def __init__(self, kernel, state, *, mean=0.0):
+    def __init__(self, kernel, state, *, mean=0.0, jitter=None):
+        from .autograd import _has_convolution
         from .terms import TermConvolution
 
         if isinstance(kernel, TermConvolution):
             raise ValueError("a Filter does not take a TermConvolution kernel (not semiseparable inside the exposure window)")
-        if kernel._has_tensors():
-            raise ValueError("a Filter does not take a kernel with tensor hyper-parameters")
+        self.differentiable = kernel._has_tensors()
+        if self.differentiable and _has_convolution(kernel):
+            raise ValueError("a Filter does not take a kernel with a TermConvolution in it (not semiseparable inside the "
+                             "exposure window)")
+        if jitter is not None and not self.differentiable:
+            raise ValueError("'jitter' goes with a kernel of tensor hyper-parameters (else add it to yerr)")
         if state.dim() != 2 or state.shape[1] != ops.filter_state_words(kernel.width):
             raise ValueError("Invalid shape: state %s, expected (B, %d)" % (tuple(state.shape), ops.filter_state_words(kernel.width)))
         self.kernel = kernel
         self.mean = mean if torch.is_tensor(mean) else float(mean)
+        self.jitter = jitter
         self.state = state
 
     @classmethod
-    def empty(cls, kernel, B, *, mean=0.0, device="cuda"):
+    def empty(cls, kernel, B, *, mean=0.0, jitter=None, device="cuda"):
         """A filter of B series that has seen nothing."""
-        return cls(kernel, ops.filter_init(B, kernel.width, device), mean=mean)
+        return cls(kernel, ops.filter_init(B, kernel.width, device), mean=mean, jitter=jitter)
 
     # -- what the state holds ------------------------------------------------------------------------------------------
     @property
@@ -58,7 +77,12 @@ class Filter:
         return -0.5 * (self.state[:, 3] + self.state[:, 2] + self.state[:, 1] * math.log(2 * math.pi))
 
     def clone(self):
-        return Filter(self.kernel, self.state.clone(), mean=self.mean)
+        return Filter(self.kernel, self.state.clone(), mean=self.mean, jitter=self.jitter)
+
+    def detach(self):
+        """Cut the graph at the present state: later appends send no gradient into the earlier ones.  Returns self."""
+        self.state = self.state.detach()
+        return self
 
     def _rows(self, t, diag, name):
         B = self.state.shape[0]
@@ -72,7 +96,9 @@ class Filter:
     def append(self, t_new, y_new, *, yerr=None, diag=None, count=None, check_sorted=True):
         """Append the rows (t_new (M,) | (B, M), y_new (B, M)) with white noise `yerr` or `diag` (B, M); `count` (B,) int32
         says how many of the M rows each series takes (rows beyond it are not read, a series with 0 keeps its state).
-        The state advances in place.  Returns Update(innovation z, variance d, score z / sqrt(d), flag): (B, M) each, NaN
+        The state advances in place -- under a kernel with tensor hyper-parameters `self.state` is rebound to a new tensor
+        instead, and everything returned is differentiable in the hyper-parameters, jitter, mean, t_new, y_new, the noise
+        and the state before.  Returns Update(innovation z, variance d, score z / sqrt(d), flag): (B, M) each, NaN
         in the rows that were not taken, and flag (B,) int32 -- the 1-based row whose predictive variance came out <= 0
         (the rows before it are returned, the series' state is left as it was), else 0."""
         if yerr is not None and diag is not None:
@@ -86,12 +112,33 @@ class Filter:
             raise ValueError("Invalid shape: y_new %s, expected %s" % (tuple(y_new.shape), (B, M)))
         if check_sorted:
             self._check_sorted(t_new, count)
+        if self.differentiable:
+            return self._append_graph(t_new, y_new, diag, count)
         c, a, U, V = self._rows(t_new, diag, "t_new")
         r = (y_new - self.mean).contiguous()
         d, z = (torch.full((B, M), math.nan, dtype=torch.float64, device=self.state.device) for _ in range(2))
         W = torch.full((B, M, U.shape[-1]), math.nan, dtype=torch.float64, device=self.state.device)
         _, d, W, z, flag = ops.filter_append(self.state, t_new.contiguous(), c, a, U, V, r, count=count, out=self.state,
                                              d=d, W=W, z=z)
+        return Update(z, d, z / torch.sqrt(d), flag)
+
+    def _append_graph(self, t_new, y_new, diag, count):
+        from . import autograd
+
+        B, M = y_new.shape
+        if t_new.dim() not in (1, 2) or (t_new.dim() == 2 and t_new.shape[0] != B):
+            raise ValueError("Invalid shape: t_new %s, expected (M,) or (%d, M)" % (tuple(t_new.shape), B))
+        if tuple(diag.shape) != (B, M):
+            raise ValueError("Invalid shape: diag %s, expected %s" % (tuple(diag.shape), (B, M)))
+        mean = self.mean if torch.is_tensor(self.mean) or self.mean != 0.0 else None
+        self.state, d, _, z, flag = autograd.filter_append_kernel(self.kernel, self.state, t_new, y_new, diag=diag,
+                                                                  jitter=self.jitter, mean=mean, count=count)
+        # the rows that were not taken: NaN, as in place (of a failed series: every row from the failing one on)
+        taken = torch.arange(M, device=d.device)[None, :] < (torch.full_like(flag, M) if count is None else count)[:, None]
+        at = torch.arange(1, M + 1, device=d.device)[None, :]
+        nan = torch.full_like(d, math.nan)
+        d = torch.where(taken & ((flag[:, None] == 0) | (at <= flag[:, None])), d, nan)
+        z = torch.where(taken & ((flag[:, None] == 0) | (at < flag[:, None])), z, nan)
         return Update(z, d, z / torch.sqrt(d), flag)
 
     def _check_sorted(self, t_new, count):
@@ -118,6 +165,11 @@ class Filter:
         tq = t if t.dim() == 2 else t[None, :]
         if bool(((tq < self.t_last[:, None]) & (self.state[:, 1:2] > 0)).any()):
             raise ValueError("The forecast coordinates must not be before the last absorbed time")
+        state, mean = self.state, self.mean
+        if self.differentiable:   # detached values: the reverse of forecast is not written
+            t, diag, state = t.detach(), diag.detach(), state.detach()
+            if torch.is_tensor(mean):
+                mean = mean.detach()[:, None] if mean.dim() == 1 else mean.detach()
         c, a, U, _ = self._rows(t, diag, "t")
-        mu, var = ops.filter_forecast(self.state, t.contiguous(), c, a, U)
-        return (mu + self.mean if include_mean else mu), var
+        mu, var = ops.filter_forecast(state, t.contiguous(), c, a, U)
+        return (mu + mean if include_mean else mu), var
