@@ -90,36 +90,37 @@ __global__ __launch_bounds__(kThreads) void k_kron_expand_rev(
     double *__restrict__ bt, double *__restrict__ ba, double *__restrict__ bU, double *__restrict__ bV,
     double *__restrict__ bdiag, double *__restrict__ part /* (B, nch, M) */, int nch) {
   __shared__ double red[kThreads / 64];
-  const int64_t b = blockIdx.y;
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool ok = n < N;
-  const int64_t bn = b * N + (ok ? n : N - 1);
-  const double *al = alpha + b * alpha_bs;
-  double sbt = 0.0, sba = 0.0;
-  for (int m = 0; m < M; ++m) {
-    const double g = ba2[bn * M + m];
-    sbt += bt2[bn * M + m];
-    sba = fma(al[m] * al[m], g, sba);
-    if (ok) bdiag[bn * M + m] = g;
-  }
-  if (ok) { bt[bn] = sbt; ba[bn] = sba; }
-  for (int j = 0; j < J; ++j) {
-    double su = 0.0, sv = 0.0;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (gridDim.y = min(B, 65535): one trip up to 65535 series)
+    const int64_t bn = b * N + (ok ? n : N - 1);
+    const double *al = alpha + b * alpha_bs;
+    double sbt = 0.0, sba = 0.0;
     for (int m = 0; m < M; ++m) {
-      su = fma(al[m], bU2[(bn * M + m) * J + j], su);
-      sv = fma(al[m], bV2[(bn * M + m) * J + j], sv);
+      const double g = ba2[bn * M + m];
+      sbt += bt2[bn * M + m];
+      sba = fma(al[m] * al[m], g, sba);
+      if (ok) bdiag[bn * M + m] = g;
     }
-    if (ok) { bU[bn * J + j] = su; bV[bn * J + j] = sv; }
-  }
-  const double an = a[bn];
-  for (int m = 0; m < M; ++m) {
-    double s = 2.0 * al[m] * an * ba2[bn * M + m];
+    if (ok) { bt[bn] = sbt; ba[bn] = sba; }
     for (int j = 0; j < J; ++j) {
-      s = fma(bU2[(bn * M + m) * J + j], U[bn * J + j], s);
-      s = fma(bV2[(bn * M + m) * J + j], V[bn * J + j], s);
+      double su = 0.0, sv = 0.0;
+      for (int m = 0; m < M; ++m) {
+        su = fma(al[m], bU2[(bn * M + m) * J + j], su);
+        sv = fma(al[m], bV2[(bn * M + m) * J + j], sv);
+      }
+      if (ok) { bU[bn * J + j] = su; bV[bn * J + j] = sv; }
     }
-    const double tot = block_sum(ok ? s : 0.0, red);
-    if (threadIdx.x == 0) part[(b * nch + blockIdx.x) * M + m] = tot;
+    const double an = a[bn];
+    for (int m = 0; m < M; ++m) {
+      double s = 2.0 * al[m] * an * ba2[bn * M + m];
+      for (int j = 0; j < J; ++j) {
+        s = fma(bU2[(bn * M + m) * J + j], U[bn * J + j], s);
+        s = fma(bV2[(bn * M + m) * J + j], V[bn * J + j], s);
+      }
+      const double tot = block_sum(ok ? s : 0.0, red);
+      if (threadIdx.x == 0) part[(b * nch + blockIdx.x) * M + m] = tot;
+    }
   }
 }
 
@@ -157,25 +158,26 @@ __global__ __launch_bounds__(kThreads) void k_kron_collapse(int64_t B, int64_t N
                                                             double *__restrict__ y_eff, double *__restrict__ part,
                                                             int32_t *__restrict__ badflag, int nch) {
   __shared__ double red[kThreads / 64];
-  const int64_t b = blockIdx.y;
-  const double *al = alpha + b * alpha_bs;
-  double corr = 0.0;
-  int32_t bad = 0;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (one trip up to 65535 series)
+    const double *al = alpha + b * alpha_bs;
+    double corr = 0.0;
+    int32_t bad = 0;
 #pragma unroll
-  for (int e = 0; e < kEpt; ++e) {
-    const int64_t n = (int64_t)blockIdx.x * kEpb + e * kThreads + threadIdx.x;
-    if (n < N) {
-      const int64_t bn = b * N + n;
-      const Epoch s = epoch_sums(al, diag + bn * M, y + bn * M, M);
-      a_eff[bn] = a[bn] + 1.0 / s.A;
-      y_eff[bn] = s.yt;
-      corr += -0.5 * ((double)(M - 1) * kLog2Pi + s.ld + log(s.A) + s.R);
-      if (s.bad || !(s.A > 0.0)) bad = 1;
+    for (int e = 0; e < kEpt; ++e) {
+      const int64_t n = (int64_t)blockIdx.x * kEpb + e * kThreads + threadIdx.x;
+      if (n < N) {
+        const int64_t bn = b * N + n;
+        const Epoch s = epoch_sums(al, diag + bn * M, y + bn * M, M);
+        a_eff[bn] = a[bn] + 1.0 / s.A;
+        y_eff[bn] = s.yt;
+        corr += -0.5 * ((double)(M - 1) * kLog2Pi + s.ld + log(s.A) + s.R);
+        if (s.bad || !(s.A > 0.0)) bad = 1;
+      }
     }
+    const double tot = block_sum(corr, red);
+    if (threadIdx.x == 0) part[b * nch + blockIdx.x] = tot;
+    if (bad) atomicOr(reinterpret_cast<int *>(badflag + b), 1);
   }
-  const double tot = block_sum(corr, red);
-  if (threadIdx.x == 0) part[b * nch + blockIdx.x] = tot;
-  if (bad) atomicOr(reinterpret_cast<int *>(badflag + b), 1);
 }
 
 // ll[b] = ll_1D[b] + sum of the partials (fixed order -> deterministic); a non-positive diag makes the series invalid.
@@ -204,40 +206,41 @@ __global__ __launch_bounds__(kThreads) void k_kron_collapse_rev(
     const int32_t *__restrict__ badflag, double *__restrict__ bdiag, double *__restrict__ by,
     double *__restrict__ part /* (B, nch, M) */, int nch) {
   __shared__ double red[kThreads / 64];
-  const int64_t b = blockIdx.y;
-  const double *al = alpha + b * alpha_bs;
-  const bool invalid = badflag[b] != 0;  // a band variance <= 0: every gradient of the series is NaN
-  double rA[kEpt], yt[kEpt], gs[kEpt], gy[kEpt];
-  int64_t row[kEpt];
-#pragma unroll
-  for (int e = 0; e < kEpt; ++e) {
-    const int64_t n = (int64_t)blockIdx.x * kEpb + e * kThreads + threadIdx.x;
-    row[e] = -1;
-    rA[e] = yt[e] = gs[e] = gy[e] = 0.0;
-    if (n < N) {
-      const int64_t bn = b * N + n;
-      row[e] = bn;
-      const Epoch s = epoch_sums(al, diag + bn * M, y + bn * M, M);
-      rA[e] = 1.0 / s.A; yt[e] = s.yt; gs[e] = g_s[bn]; gy[e] = g_y[bn];
-      if (invalid) gs[e] = gy[e] = __builtin_nan("");
-    }
-  }
-  for (int m = 0; m < M; ++m) {
-    double sum = 0.0;
-    const double am = al[m];
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (one trip up to 65535 series)
+    const double *al = alpha + b * alpha_bs;
+    const bool invalid = badflag[b] != 0;  // a band variance <= 0: every gradient of the series is NaN
+    double rA[kEpt], yt[kEpt], gs[kEpt], gy[kEpt];
+    int64_t row[kEpt];
 #pragma unroll
     for (int e = 0; e < kEpt; ++e) {
-      if (row[e] >= 0) {
-        const int64_t i = row[e] * M + m;
-        const double rd = 1.0 / diag[i], r = fma(-am, yt[e], y[i]);
-        const double arA = am * rA[e];
-        sum += (gy[e] * (r - am * yt[e]) * rA[e] - 2.0 * gs[e] * arA * rA[e] - arA + yt[e] * r) * rd;
-        bdiag[i] = ((-gy[e] * arA * r + gs[e] * arA * arA + 0.5 * am * arA + 0.5 * r * r) * rd - 0.5) * rd;
-        by[i] = (gy[e] * arA - r) * rd;
+      const int64_t n = (int64_t)blockIdx.x * kEpb + e * kThreads + threadIdx.x;
+      row[e] = -1;
+      rA[e] = yt[e] = gs[e] = gy[e] = 0.0;
+      if (n < N) {
+        const int64_t bn = b * N + n;
+        row[e] = bn;
+        const Epoch s = epoch_sums(al, diag + bn * M, y + bn * M, M);
+        rA[e] = 1.0 / s.A; yt[e] = s.yt; gs[e] = g_s[bn]; gy[e] = g_y[bn];
+        if (invalid) gs[e] = gy[e] = __builtin_nan("");
       }
     }
-    const double tot = block_sum(sum, red);
-    if (threadIdx.x == 0) part[(b * nch + blockIdx.x) * M + m] = tot;
+    for (int m = 0; m < M; ++m) {
+      double sum = 0.0;
+      const double am = al[m];
+#pragma unroll
+      for (int e = 0; e < kEpt; ++e) {
+        if (row[e] >= 0) {
+          const int64_t i = row[e] * M + m;
+          const double rd = 1.0 / diag[i], r = fma(-am, yt[e], y[i]);
+          const double arA = am * rA[e];
+          sum += (gy[e] * (r - am * yt[e]) * rA[e] - 2.0 * gs[e] * arA * rA[e] - arA + yt[e] * r) * rd;
+          bdiag[i] = ((-gy[e] * arA * r + gs[e] * arA * arA + 0.5 * am * arA + 0.5 * r * r) * rd - 0.5) * rd;
+          by[i] = (gy[e] * arA - r) * rd;
+        }
+      }
+      const double tot = block_sum(sum, red);
+      if (threadIdx.x == 0) part[(b * nch + blockIdx.x) * M + m] = tot;
+    }
   }
 }
 
@@ -261,30 +264,31 @@ __global__ __launch_bounds__(kThreads) void k_kron_collapse_b(int64_t B, int64_t
                                                               int32_t *__restrict__ badflag, int nch) {
   constexpr int EPS = kThreads / G;   // epochs per slab of kThreads elements
   __shared__ double red[kThreads / 64];
-  const int64_t b = blockIdx.y;
   const int m = threadIdx.x % G, eo = threadIdx.x / G;
-  const double al = alpha[b * alpha_bs + m];
-  double corr = 0.0;
-  int32_t bad = 0;
-  for (int e0 = 0; e0 < kEpb; e0 += EPS) {
-    const int64_t n = (int64_t)blockIdx.x * kEpb + e0 + eo;
-    const bool in = n < N;
-    const int64_t bn = b * N + (in ? n : N - 1), i = bn * G + m;
-    const double d = diag[i], yv = y[i], ay = al / d;
-    const double A = band_sum<G>(al * ay), bs = band_sum<G>(ay * yv), ld = band_sum<G>(log(d));
-    const double yt = bs / A, r = fma(-al, yt, yv);
-    const double R = band_sum<G>(r / d * r);
-    const bool ebad = band_sum<G>(d > 0.0 ? 0.0 : 1.0) != 0.0 || !(A > 0.0);
-    if (in && m == 0) {
-      a_eff[bn] = a[bn] + 1.0 / A;
-      y_eff[bn] = yt;
-      corr += -0.5 * ((double)(G - 1) * kLog2Pi + ld + log(A) + R);
-      if (ebad) bad = 1;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (one trip up to 65535 series)
+    const double al = alpha[b * alpha_bs + m];
+    double corr = 0.0;
+    int32_t bad = 0;
+    for (int e0 = 0; e0 < kEpb; e0 += EPS) {
+      const int64_t n = (int64_t)blockIdx.x * kEpb + e0 + eo;
+      const bool in = n < N;
+      const int64_t bn = b * N + (in ? n : N - 1), i = bn * G + m;
+      const double d = diag[i], yv = y[i], ay = al / d;
+      const double A = band_sum<G>(al * ay), bs = band_sum<G>(ay * yv), ld = band_sum<G>(log(d));
+      const double yt = bs / A, r = fma(-al, yt, yv);
+      const double R = band_sum<G>(r / d * r);
+      const bool ebad = band_sum<G>(d > 0.0 ? 0.0 : 1.0) != 0.0 || !(A > 0.0);
+      if (in && m == 0) {
+        a_eff[bn] = a[bn] + 1.0 / A;
+        y_eff[bn] = yt;
+        corr += -0.5 * ((double)(G - 1) * kLog2Pi + ld + log(A) + R);
+        if (ebad) bad = 1;
+      }
     }
+    const double tot = block_sum(corr, red);
+    if (threadIdx.x == 0) part[b * nch + blockIdx.x] = tot;
+    if (bad) atomicOr(reinterpret_cast<int *>(badflag + b), 1);
   }
-  const double tot = block_sum(corr, red);
-  if (threadIdx.x == 0) part[b * nch + blockIdx.x] = tot;
-  if (bad) atomicOr(reinterpret_cast<int *>(badflag + b), 1);
 }
 template <int G>
 __global__ __launch_bounds__(kThreads) void k_kron_collapse_rev_b(
@@ -294,33 +298,35 @@ __global__ __launch_bounds__(kThreads) void k_kron_collapse_rev_b(
     double *__restrict__ part /* (B, nch, M) */, int nch) {
   constexpr int EPS = kThreads / G;
   __shared__ double red[kThreads];
-  const int64_t b = blockIdx.y;
   const int m = threadIdx.x % G, eo = threadIdx.x / G;
-  const double am = alpha[b * alpha_bs + m];
-  const bool invalid = badflag[b] != 0;  // a band variance <= 0: every gradient of the series is NaN
-  double sum = 0.0;
-  for (int e0 = 0; e0 < kEpb; e0 += EPS) {
-    const int64_t n = (int64_t)blockIdx.x * kEpb + e0 + eo;
-    const bool in = n < N;
-    const int64_t bn = b * N + (in ? n : N - 1), i = bn * G + m;
-    const double d = diag[i], yv = y[i], rd = 1.0 / d, ay = am * rd;
-    const double A = band_sum<G>(am * ay), bs = band_sum<G>(ay * yv);
-    const double rA = 1.0 / A, yt = bs * rA, r = fma(-am, yt, yv), arA = am * rA;
-    double gs = g_s[bn], gy = g_y[bn];
-    if (invalid) gs = gy = __builtin_nan("");
-    if (in) {
-      sum += (gy * (r - am * yt) * rA - 2.0 * gs * arA * rA - arA + yt * r) * rd;
-      bdiag[i] = ((-gy * arA * r + gs * arA * arA + 0.5 * am * arA + 0.5 * r * r) * rd - 0.5) * rd;
-      by[i] = (gy * arA - r) * rd;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (one trip up to 65535 series)
+    const double am = alpha[b * alpha_bs + m];
+    const bool invalid = badflag[b] != 0;  // a band variance <= 0: every gradient of the series is NaN
+    double sum = 0.0;
+    for (int e0 = 0; e0 < kEpb; e0 += EPS) {
+      const int64_t n = (int64_t)blockIdx.x * kEpb + e0 + eo;
+      const bool in = n < N;
+      const int64_t bn = b * N + (in ? n : N - 1), i = bn * G + m;
+      const double d = diag[i], yv = y[i], rd = 1.0 / d, ay = am * rd;
+      const double A = band_sum<G>(am * ay), bs = band_sum<G>(ay * yv);
+      const double rA = 1.0 / A, yt = bs * rA, r = fma(-am, yt, yv), arA = am * rA;
+      double gs = g_s[bn], gy = g_y[bn];
+      if (invalid) gs = gy = __builtin_nan("");
+      if (in) {
+        sum += (gy * (r - am * yt) * rA - 2.0 * gs * arA * rA - arA + yt * r) * rd;
+        bdiag[i] = ((-gy * arA * r + gs * arA * arA + 0.5 * am * arA + 0.5 * r * r) * rd - 0.5) * rd;
+        by[i] = (gy * arA - r) * rd;
+      }
     }
-  }
-  // the band's sum over the block's epochs: the EPS threads that share m, in a fixed order
-  red[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x < G) {
-    double tot = 0.0;
-    for (int q = 0; q < EPS; ++q) tot += red[q * G + threadIdx.x];
-    part[(b * nch + blockIdx.x) * G + threadIdx.x] = tot;
+    // the band's sum over the block's epochs: the EPS threads that share m, in a fixed order
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x < G) {
+      double tot = 0.0;
+      for (int q = 0; q < EPS; ++q) tot += red[q * G + threadIdx.x];
+      part[(b * nch + blockIdx.x) * G + threadIdx.x] = tot;
+    }
+    if (b + gridDim.y < B) __syncthreads();   // (a further trip refills `red`)
   }
 }
 
@@ -335,13 +341,15 @@ __global__ void k_kron_balpha(int64_t B, int M, int nch, const double *__restric
   balpha[g] = s;
 }
 
+// The kernels with the series on blockIdx.y stride over the batch: gridDim.y stops at 65535.
+static unsigned grid_y(int64_t B) { return (unsigned)(B < 65535 ? B : 65535); }
 static bool use_banded() {
   return !(c2::opt::has(c2::opt::k_kron_banded) && c2::opt::ival(c2::opt::k_kron_banded) == 0);   // 0: the thread-per-epoch kernels for every M (A/B runs, tests)
 }
 static void launch_collapse(int64_t B, int64_t N, int64_t M, const double *a, const double *alpha, int64_t alpha_bs,
                             const double *diag, const double *y, double *a_eff, double *y_eff, double *part,
                             int32_t *badflag, int nch, hipStream_t s) {
-  const dim3 grid((unsigned)nch, (unsigned)B);
+  const dim3 grid((unsigned)nch, grid_y(B));
 #define C2K_C(G) hipLaunchKernelGGL((k_kron_collapse_b<G>), grid, dim3(kThreads), 0, s, B, N, a, alpha, alpha_bs, diag, y, a_eff, y_eff, part, badflag, nch)
   if (use_banded() && M == 2) C2K_C(2);
   else if (use_banded() && M == 4) C2K_C(4);
@@ -355,7 +363,7 @@ static void launch_collapse(int64_t B, int64_t N, int64_t M, const double *a, co
 static void launch_collapse_rev(int64_t B, int64_t N, int64_t M, const double *alpha, int64_t alpha_bs,
                                 const double *diag, const double *y, const double *g_s, const double *g_y,
                                 const int32_t *badflag, double *bdiag, double *by, double *part, int nch, hipStream_t s) {
-  const dim3 grid((unsigned)nch, (unsigned)B);
+  const dim3 grid((unsigned)nch, grid_y(B));
 #define C2K_R(G) hipLaunchKernelGGL((k_kron_collapse_rev_b<G>), grid, dim3(kThreads), 0, s, B, N, alpha, alpha_bs, diag, y, g_s, g_y, badflag, bdiag, by, part, nch)
   if (use_banded() && M == 2) C2K_R(2);
   else if (use_banded() && M == 4) C2K_R(4);
@@ -423,7 +431,7 @@ static int kron_check(int64_t B, int64_t N, int64_t M, int64_t J, int method) {
   if (B < 1 || N < 1 || M < 1 || J < 1) return C2_ERR_INVALID;
   if (J > C2_FAST_WIDTH) return C2_ERR_UNSUPPORTED;
   if (method != C2_KRON_COLLAPSED && method != C2_KRON_INTERLEAVED) return C2_ERR_INVALID;
-  if (M > INT32_MAX || B > 65535) return C2_ERR_UNSUPPORTED;  // grid.y
+  if (M > INT32_MAX) return C2_ERR_UNSUPPORTED;
   return C2_OK;
 }
 
@@ -478,7 +486,7 @@ int c2_kron_loglik_grad(int64_t B, int64_t N, int64_t M, int64_t J, const double
                                w + p.bt2, bc, w + p.ba2, w + p.bU2, w + p.bV2, by, flag, w + p.one_d,
                                c2_internal_loglik_grad_rows_workspace_bytes(B, R, J), stream))
       return e;
-    hipLaunchKernelGGL(k_kron_expand_rev, dim3((unsigned)p.nch, (unsigned)B), dim3(kThreads), 0, s, B, N, (int)M,
+    hipLaunchKernelGGL(k_kron_expand_rev, dim3((unsigned)p.nch, grid_y(B)), dim3(kThreads), 0, s, B, N, (int)M,
                        (int)J, a, U, V, alpha, alpha_bs, w + p.bt2, w + p.ba2, w + p.bU2, w + p.bV2, bt, ba, bU, bV,
                        bdiag, w + p.part, p.nch);
     if (int e = c2::launch_ok()) return e;

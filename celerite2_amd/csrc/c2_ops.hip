@@ -1302,27 +1302,30 @@ __global__ __launch_bounds__(256, 4) void k_kernel_values_tile(int64_t N, int64_
 // diag(Kxs K^-1 Kxs^T)_m = sum_n (L^-1 Kxs^T)_nm^2 / d_n (K = L D L^T; core.py:134-140 reaches the same number through
 // apply_inverse = both solves and a second pass over the two N x M arrays).  One pass over Z: grid (ceil(M / 64), B), the sixteen
 // wavefronts of a workgroup take interleaved rows.
-__global__ __launch_bounds__(1024) void k_colsumsq_over_d(int64_t N, int64_t M, const double *__restrict__ Z,
+__global__ __launch_bounds__(1024) void k_colsumsq_over_d(int64_t B, int64_t N, int64_t M, const double *__restrict__ Z,
                                                           const double *__restrict__ d, double *__restrict__ out) {
   __shared__ double part[16][64];
-  const int64_t b = blockIdx.y, m = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const int64_t m = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const int w = threadIdx.x >> 6;
-  const double *zb = Z + b * N * M + (m < M ? m : M - 1), *db = d + b * N;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // (four rows in flight per wavefront: the loop is bound by load latency)
-  int64_t n = w;
-  for (; n + 48 < N; n += 64) {
-    const double z0 = zb[n * M], z1 = zb[(n + 16) * M], z2 = zb[(n + 32) * M], z3 = zb[(n + 48) * M];
-    const double d0 = db[n], d1 = db[n + 16], d2 = db[n + 32], d3 = db[n + 48];
-    a0 = fma(z0, z0 / d0, a0); a1 = fma(z1, z1 / d1, a1); a2 = fma(z2, z2 / d2, a2); a3 = fma(z3, z3 / d3, a3);
-  }
-  for (; n < N; n += 16) { const double z = zb[n * M]; a0 = fma(z, z / db[n], a0); }
-  part[w][threadIdx.x & 63] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (w == 0 && m < M) {
-    double s = 0.0;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {   // (gridDim.y = min(B, 65535): one trip up to 65535 series)
+    const double *zb = Z + b * N * M + (m < M ? m : M - 1), *db = d + b * N;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // (four rows in flight per wavefront: the loop is bound by load latency)
+    int64_t n = w;
+    for (; n + 48 < N; n += 64) {
+      const double z0 = zb[n * M], z1 = zb[(n + 16) * M], z2 = zb[(n + 32) * M], z3 = zb[(n + 48) * M];
+      const double d0 = db[n], d1 = db[n + 16], d2 = db[n + 32], d3 = db[n + 48];
+      a0 = fma(z0, z0 / d0, a0); a1 = fma(z1, z1 / d1, a1); a2 = fma(z2, z2 / d2, a2); a3 = fma(z3, z3 / d3, a3);
+    }
+    for (; n < N; n += 16) { const double z = zb[n * M]; a0 = fma(z, z / db[n], a0); }
+    part[w][threadIdx.x & 63] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (w == 0 && m < M) {
+      double s = 0.0;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) s += part[q][threadIdx.x];
-    out[b * M + m] = s;
+      for (int q = 0; q < 16; ++q) s += part[q][threadIdx.x];
+      out[b * M + m] = s;
+    }
+    if (b + gridDim.y < B) __syncthreads();   // (a further trip refills `part`)
   }
 }
 
@@ -1901,9 +1904,9 @@ int c2_kernel_values(int64_t B, int64_t N, int64_t M, int64_t Jr, int64_t Jc, co
 
 int c2_colsumsq_over_d(int64_t B, int64_t N, int64_t M, const double *Z, const double *d, double *out, c2_stream_t stream) {
   if (B < 1 || N < 1 || M < 1 || !Z || !d || !out) return C2_ERR_INVALID;
-  if (B > 65535) return C2_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_colsumsq_over_d, dim3((unsigned)((M + 63) / 64), (unsigned)B), dim3(1024), 0, (hipStream_t)stream, N, M, Z, d,
-                     out);
+  // (the blocks stride over the batch: gridDim.y stops at 65535)
+  hipLaunchKernelGGL(k_colsumsq_over_d, dim3((unsigned)((M + 63) / 64), (unsigned)(B < 65535 ? B : 65535)), dim3(1024), 0,
+                     (hipStream_t)stream, B, N, M, Z, d, out);
   return launch_ok();
 }
 

@@ -219,7 +219,8 @@ int c2_kernel_values(int64_t B, int64_t N, int64_t M, int64_t Jr, int64_t Jc, co
 /* out[b, m] = sum_n Z[b, n, m]^2 / d[b, n]  (Z (B,N,M), d (B,N), out (B,M)): the quadratic form of the PREDICTIVE VARIANCE,
  * core.py:134-140 `kernel.get_value(0) - diagdot(KxsT, Kinv_KxsT)` (numpy.py:24-25), evaluated from the lower solve alone:
  * with K = L D L^T, diag(Kxs K^-1 Kxs^T)_m = sum_n (L^-1 KxsT)_nm^2 / d_n -- Z = c2_solve_lower(KxsT); the reference reaches
- * the same number through apply_inverse (both solves) and a second pass over the two N x M arrays. */
+ * the same number through apply_inverse (both solves) and a second pass over the two N x M arrays.  Any B: beyond 65535
+ * series the blocks stride over the batch. */
 int c2_colsumsq_over_d(int64_t B, int64_t N, int64_t M, const double *Z, const double *d, double *out, c2_stream_t stream);
 
 /* Fused log-likelihood -- the assembly the reference's callers perform around
@@ -289,7 +290,8 @@ int c2_condition(int64_t B, int64_t N, int64_t J, const double *t, int64_t t_bs,
  * flag[b]: first failing row in the method's own series (epoch index / interleaved row), -1 for a non-positive
  * band variance under the collapsed method -- or for alpha == 0 in every band (the collapse divides by A = sum alpha^2 /
  * D: an epoch whose bands carry no signal has no effective observation; the interleaved method has no such restriction).  Gradients: bt (B,N), bc (B,J), ba (B,N), bU, bV (B,N,J),
- * balpha (B,M) (per series, also when alpha is shared), bdiag (B,N,M), by (B,N,M). */
+ * balpha (B,M) (per series, also when alpha is shared), bdiag (B,N,M), by (B,N,M).  Any B: beyond 65535 series the
+ * blocks of the collapse and fold kernels stride over the batch. */
 #define C2_KRON_COLLAPSED 0
 #define C2_KRON_INTERLEAVED 1
 size_t c2_kron_loglik_workspace_bytes(int64_t B, int64_t N, int64_t M, int64_t J, int method, int grad);
