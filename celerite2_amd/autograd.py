@@ -18,7 +18,9 @@ likelihood with the linear coefficients profiled or marginalised out.
 
 `filter_append[_kernel]` is a streaming append (csrc/c2_filter.hip) with its reverse (csrc/c2_filter_rev.hip): the cotangent of
 a filter state is carried from one call to the previous one, so the predictive log density of each night's rows trains the
-hyper-parameters without revisiting the old rows.
+hyper-parameters without revisiting the old rows.  `filter_forecast[_kernel]` and `filter_absorb[_kernel]` are the other two
+streaming entry points with theirs (csrc/c2_filter_stream_rev.hip): the log density of what arrives h nights after a forecast
+is a training objective, and a filter warm-started from a factored archive sends its gradient back into the archive's rows.
 
 `factor`, `solve_lower`, `solve_upper`, `matmul_lower`, `matmul_upper` are the reference's five differentiable ops
 (python/celerite2/pymc/ops.py:61-141, jax/ops.py:33-172: forward = `backprop.<op>_fwd` with its workspace, gradient =
@@ -30,7 +32,7 @@ import torch
 
 from . import ops
 
-__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "whitened_gram", "gls", "marginal_log_likelihood_kernel", "filter_append", "filter_append_kernel", "LinearFit", "LinAlgError"]
+__all__ = ["log_likelihood", "log_likelihood_terms", "term_coefficients", "log_likelihood_kernel", "factor", "solve_lower", "solve_upper", "matmul_lower", "matmul_upper", "inverse_diag", "loo_log_predictive", "loo_log_predictive_kernel", "general_matmul_lower", "general_matmul_upper", "get_celerite_matrices", "predict_mean", "predict_mean_kernel", "explained_variance", "predict_variance", "predictive_log_density", "predict_variance_kernel", "predictive_log_density_kernel", "whitened_gram", "gls", "marginal_log_likelihood_kernel", "filter_append", "filter_append_kernel", "filter_forecast", "filter_absorb", "filter_forecast_kernel", "filter_absorb_kernel", "LinearFit", "LinAlgError"]
 
 
 class LinAlgError(RuntimeError):
@@ -828,3 +830,114 @@ def filter_append_kernel(kernel, state, t_new, y_new, *, yerr=None, diag=None, j
     c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
     a, U, V = get_celerite_matrices(ar, ac, bc, dc, t_new, D)
     return filter_append(state, t_new, c, a, U, V, r, count=count)
+
+
+def _filter_rows(name, kernel, B, t, like, yerr, diag, jitter, mean, *, noise_required=True):
+    """filter_append_kernel's conventions and refusals for the rows at t ((M,) | (B, M)) -> (c, a, U, V, jitter, mean) of the
+    coefficient-level chain term_coefficients -> get_celerite_matrices, the diagonal a = k(0) + noise + jitter^2 (without
+    noise, where that is allowed: a = k(0), and the jitter is not added)."""
+    if noise_required and (yerr is None) == (diag is None):
+        raise ValueError("exactly one of 'yerr' and 'diag' (B, M) is required")
+    if yerr is not None and diag is not None:
+        raise ValueError("only one of 'diag' and 'yerr' can be provided")
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != B):
+        raise ValueError("Invalid shape: t (must be (M,) or (B, M))")
+    if _has_convolution(kernel):
+        raise ValueError("%s does not take a kernel with a TermConvolution in it (not semiseparable inside the exposure "
+                         "window): use predict(y, t, return_var=True)" % name)
+    if not kernel._has_tensors():
+        raise TypeError("%s: the kernel has no tensor parameter (give its parameters as device tensors)" % name)
+    ar, cr, ac, bc, cc, dc, shift = term_coefficients(kernel.program, kernel.parameter_matrix(B), B, with_shift=True)
+    jitter, mean = _per_series(jitter, B, like), _per_series(mean, B, like)
+    if yerr is None and diag is None:
+        D = torch.zeros((B, t.shape[-1]), dtype=like.dtype, device=like.device)
+    else:
+        D = (yerr * yerr if diag is None else diag) + shift[:, None]
+        if jitter is not None:
+            D = D + (jitter * jitter)[:, None]
+    c = torch.cat([cr, cc.repeat_interleave(2, dim=1)], dim=1)   # (terms.py:171-173)
+    a, U, V = get_celerite_matrices(ar, ac, bc, dc, t, D)
+    return c, a, U, V, jitter, mean
+
+
+# ---- forecast and absorb (csrc/c2_filter.hip forward, csrc/c2_filter_stream_rev.hip backward) ----------------------------------
+class _FilterForecast(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, t, c, a, U, count):
+        args = [x.detach().contiguous() for x in (state, t, c, a, U)]
+        # (rows beyond count are not written by the kernel: zeros there)
+        mu, var = (None, None) if count is None else (torch.zeros_like(args[3]), torch.zeros_like(args[3]))
+        mu, var = ops.filter_forecast(*args, count=count, mu=mu, var=var)
+        ctx.count = count
+        ctx.save_for_backward(args[0], args[1], args[2], args[4])
+        return mu, var
+
+    @staticmethod
+    def backward(ctx, bmu, bvar):
+        state, t, c, U = ctx.saved_tensors
+        bs, bt, bc, ba, bU = ops.filter_forecast_rev(state, t, c, U, bmu.contiguous(), bvar.contiguous(), count=ctx.count)
+        return bs, _reduce(bt, t), _reduce(bc, c), ba, bU, None
+
+
+def filter_forecast(state, t, c, a, U, *, count=None):
+    """ops.filter_forecast -> (mu, var) (B, M), differentiable in state, t, c, a, U (c2_filter_forecast_rev; shared t / c
+    receive the batch sum).  The state is read and left: its cotangent adds to that of whatever else the state feeds, so the
+    log density of what arrives h nights after a forecast trains everything the state was built from.  Rows m >= count[b]
+    are zeros and receive no gradient.  J <= 32."""
+    return _FilterForecast.apply(state, t, c, a, U, count)
+
+
+class _FilterAbsorb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, t, c, W, d, z, count):
+        args = [x.detach().contiguous() for x in (state, t, c, W, d, z)]
+        out = ops.filter_absorb(*args, count=count)   # out of place: the entry state is what backward reads
+        ctx.count = count
+        ctx.save_for_backward(*args)
+        return out
+
+    @staticmethod
+    def backward(ctx, bstate):
+        state, t, c, W, d, z = ctx.saved_tensors
+        bsi, bt, bc, bW, bd, bz = ops.filter_absorb_rev(state, t, c, W, d, z, bstate.contiguous(), count=ctx.count)
+        return bsi, _reduce(bt, t), _reduce(bc, c), bW, bd, bz, None
+
+
+def filter_absorb(state, t, c, W, d, z, *, count=None):
+    """ops.filter_absorb out of place -> state_out, differentiable in state, t, c, W, d, z (c2_filter_absorb_rev; shared
+    t / c receive the batch sum): a filter warm-started from a factored archive sends its gradient back into the archive's
+    rows.  The state cotangent is carried as in `filter_append`.  Workspace of the backward call: 8 M (J + J^2) bytes per
+    series.  J <= 32."""
+    return _FilterAbsorb.apply(state, t, c, W, d, z, count)
+
+
+def filter_forecast_kernel(kernel, state, t, *, yerr=None, diag=None, jitter=None, mean=None, count=None):
+    """`filter_forecast` as a differentiable function of the HYPER-PARAMETERS, with `filter_append_kernel`'s conventions and
+    refusals: (mu, var) (B, M) at the times t (M,) | (B, M), each row independently from `state`.  Without noise `var` is
+    the latent variance and no jitter is added; with yerr | diag (B, M) it is the variance of a would-be observation,
+    jitter^2 included.  `mu` includes `mean`.  Differentiable in the parameters, jitter, mean, the state, t and the noise.
+    The chain term_coefficients -> get_celerite_matrices -> `filter_forecast`, c built in torch.  J <= 32."""
+    if state.dim() != 2:
+        raise ValueError("Invalid shape: state (must be (B, SW))")
+    B = state.shape[0]
+    c, a, U, _, _, mean = _filter_rows("filter_forecast_kernel", kernel, B, t, state, yerr, diag, jitter, mean,
+                                       noise_required=False)
+    mu, var = filter_forecast(state, t, c, a, U, count=count)
+    return (mu if mean is None else mu + mean[:, None]), var
+
+
+def filter_absorb_kernel(kernel, x, y, *, yerr=None, diag=None, jitter=None, mean=None):
+    """The filter state (B, SW) behind the whole series y (B, N) at x (N,) | (B, N) as a differentiable function of the
+    HYPER-PARAMETERS, `log_likelihood_kernel`'s arguments and conventions: the chain term_coefficients ->
+    get_celerite_matrices -> `factor` -> `solve_lower` -> `filter_absorb` from the empty state, so -(1/2) ([3] + [2] + n log 2 pi)
+    of its words is the log-likelihood of the series, and rows appended or forecast behind it send their gradient back
+    through it.  A failed factorisation raises LinAlgError.  A kernel with a TermConvolution anywhere in it is refused.
+    J <= 32."""
+    if y.dim() != 2:
+        raise ValueError("Invalid shape: y (must be (B, N))")
+    B = y.shape[0]
+    c, a, U, V, _, mean = _filter_rows("filter_absorb_kernel", kernel, B, x, y, yerr, diag, jitter, mean)
+    r = y if mean is None else y - mean[:, None]
+    d, W = factor(x, c, a, U, V)
+    z = solve_lower(x, c, U, W, r[..., None])[..., 0]
+    return filter_absorb(ops.filter_init(B, U.shape[-1], y.device), x, c, W, d, z)

@@ -314,6 +314,21 @@ class GaussianProcess:
         state.masked_fill_((self._flag != 0)[:, None], math.nan)
         return Filter(self.kernel, state, mean=self.mean)
 
+    def filter_kernel(self, y, *, jitter=None):
+        """A DIFFERENTIABLE stream.Filter that has absorbed the computed series and the data `y` (B, N), for a kernel with
+        tensor hyper-parameters: autograd.filter_absorb_kernel on this GP's t, diag and mean -- to `filter(y)` what
+        `log_likelihood_kernel` is to `log_likelihood` (the coefficient-level chain, not the matrices `compute` factored).
+        Its state carries the graph: `log_likelihood`, every later `append` and `forecast_log_density` send their gradient
+        back through the absorbed rows into the hyper-parameters, `jitter`, a tensor `mean` and `y`.  A failed factorisation
+        raises autograd.LinAlgError.  J <= 32."""
+        from . import autograd
+        from .stream import Filter
+
+        self._need()
+        self._check_vector(y)
+        state = autograd.filter_absorb_kernel(self.kernel, self._t, y, diag=self._diag, jitter=jitter, mean=self.mean)
+        return Filter(self.kernel, state, mean=self.mean, jitter=jitter)
+
     def predict_kernel(self, y, t, *, jitter=None):
         """The conditional mean (B, M) at the sorted times `t` ((M,) shared or (B, M)), mean included, as a differentiable
         function of the kernel's tensor hyper-parameters, of `jitter`, of a tensor `mean`, of `y` and of the times:

@@ -35,7 +35,8 @@ __all__ = [
 # include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS, and
 # `filter_state_words`, `filter_init`, `filter_append`, `filter_absorb` and `filter_forecast` of celerite2_amd_filter.h,
 # _lib.FILTER_SYMBOLS, and `filter_rev_workspace_words` and `filter_append_rev` of celerite2_amd_filter_rev.h,
-# _lib.FILTER_REV_SYMBOLS)
+# _lib.FILTER_REV_SYMBOLS, and `filter_forecast_rev` and `filter_absorb_rev` of celerite2_amd_filter_stream_rev.h,
+# _lib.FILTER_STREAM_REV_EXPORTS)
 
 
 def _p(x):
@@ -1583,4 +1584,55 @@ def filter_append_rev(state, t, c, U, W, d, z, flag, bstate, bd=None, bW=None, b
     rc = _lib.load().c2_filter_append_rev(B, M, J, state, t, _bs(t, M), c, _bs(c, J), U, W, d, z, count, flag, bstate, bd, bW, bz,
                                           ws, *out, _stream())
     _lib.check(rc, "filter_append_rev")
+    return out
+
+
+# ---- reverse of forecast and absorb (include/celerite2_amd_filter_stream_rev.h, csrc/c2_filter_stream_rev.hip;
+# _lib.FILTER_STREAM_REV_EXPORTS) -------------------------------------------------------------------------------------------
+_FILTER_FORECAST_REV_OUT = dict(bstate="BS", bt="BM", bc="BJ", ba="BM", bU="BMJ")                       # bt, bc: per series always
+_FILTER_ABSORB_REV_OUT = dict(bstate_in="BS", bt="BM", bc="BJ", bW="BMJ", bd="BM", bz="BM")
+
+
+def filter_forecast_rev(state, t, c, U, bmu, bvar, *, count=None, out=None):
+    """Reverse of filter_forecast (c2_filter_forecast_rev): state, t, c, U, count as given to it, cotangents bmu, bvar (B, M)
+    -> (bstate (B, SW), bt (B, M), bc (B, J), ba (B, M), bU (B, M, J)).  The forecast reads the state and leaves it, so
+    bstate is a cotangent to ADD to whatever else the state feeds: word [0] = -sum_m bt_m, words [1..3] zero, the S block
+    symmetric to the bit.  bt and bc come out PER SERIES also when t or c are shared.  Rows m >= count[b] get zeros, a series
+    with count 0 or an empty state (n == 0) zeros everywhere but ba = bvar in the rows it took.  `out`: the five outputs,
+    caller-owned (they may be uninitialised, and must not alias an input).  J <= 32."""
+    dims = _filter_dims(U, "U")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    out = _empty(U.device, dims, *_FILTER_FORECAST_REV_OUT.values()) if out is None else tuple(out)
+    if len(out) != len(_FILTER_FORECAST_REV_OUT):
+        raise ValueError("Invalid argument: out must be (bstate, bt, bc, ba, bU)")
+    ins = [("state", state, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("U", U, "BMJ"), ("bmu", bmu, "BM"),
+           ("bvar", bvar, "BM")]
+    _args(dims, ins, _named(_FILTER_FORECAST_REV_OUT, out))
+    _filter_count(count, dims, U.device)
+    rc = _lib.load().c2_filter_forecast_rev(B, M, J, state, t, _bs(t, M), c, _bs(c, J), U, count, bmu, bvar, *out, _stream())
+    _lib.check(rc, "filter_forecast_rev")
+    return out
+
+
+def filter_absorb_rev(state, t, c, W, d, z, bstate, *, count=None, ws=None, out=None):
+    """Reverse of filter_absorb (c2_filter_absorb_rev): `state` (B, SW) the state the forward call STARTED from, t, c, W, d,
+    z, count as given to it, bstate (B, SW) the cotangent of the state it left -> (bstate_in (B, SW), bt (B, M), bc (B, J),
+    bW (B, M, J), bd (B, M), bz (B, M)).  The conventions of filter_append_rev: the S block of a state cotangent is the
+    symmetric representative (the incoming one is replaced by (B + B^T) / 2), word [0] of bstate is added to bt of the last
+    taken row, words [1..3] pass through, bt and bc come out PER SERIES; rows m >= count[b] get zeros, a series with count 0
+    gets bstate_in = bstate and zeros.  `ws` (B, M, J + J^2), filter_rev_workspace_words(J) doubles per row: scratch of this
+    call (allocated when None); `out`: the six outputs, caller-owned.  J <= 32."""
+    dims = _filter_dims(W, "W")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    dims["X"] = J + J * J
+    ws = _empty(W.device, dims, "BMX")[0] if ws is None else ws
+    out = _empty(W.device, dims, *_FILTER_ABSORB_REV_OUT.values()) if out is None else tuple(out)
+    if len(out) != len(_FILTER_ABSORB_REV_OUT):
+        raise ValueError("Invalid argument: out must be (bstate_in, bt, bc, bW, bd, bz)")
+    ins = [("state", state, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("W", W, "BMJ"), ("d", d, "BM"), ("z", z, "BM"),
+           ("bstate", bstate, "BS")]
+    _args(dims, ins, [("ws", ws, "BMX")] + _named(_FILTER_ABSORB_REV_OUT, out))
+    _filter_count(count, dims, W.device)
+    rc = _lib.load().c2_filter_absorb_rev(B, M, J, state, t, _bs(t, M), c, _bs(c, J), W, d, z, count, bstate, ws, *out, _stream())
+    _lib.check(rc, "filter_absorb_rev")
     return out

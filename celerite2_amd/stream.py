@@ -23,8 +23,16 @@ the graph holds -- `flt.detach()` cuts it at the present state, for truncated ba
         (before - flt.log_likelihood).sum().backward()        # minus tonight's predictive log density
         optimiser.step(); optimiser.zero_grad(); flt.detach()
 
-`forecast` works on such a filter but returns detached values (its reverse is not written).  A filter on a plain kernel
-behaves as before: in place, no graph."""
+`forecast` works on such a filter but returns detached values; `forecast_kernel` is the forecast that carries the graph
+(autograd.filter_forecast_kernel, reverse: csrc/c2_filter_stream_rev.hip), and `forecast_log_density` the log density of
+what arrived at the forecast times -- forecast skill h nights ahead as a training objective:
+
+    skill = flt.forecast_log_density(t_later, y_later, yerr=e_later)   # (B,), before those rows are appended
+    (-skill.sum()).backward()
+
+`gp.filter_kernel(y)` builds a differentiable filter from a computed GP (autograd.filter_absorb_kernel): what is appended or
+forecast behind it sends its gradient back through the absorbed series.  A filter on a plain kernel behaves as before: in
+place, no graph."""
 import collections
 import math
 
@@ -173,3 +181,53 @@ class Filter:
         c, a, U, _ = self._rows(t, diag, "t")
         mu, var = ops.filter_forecast(state, t.contiguous(), c, a, U)
         return (mu + mean if include_mean else mu), var
+
+    def _check_forecast(self, t, count=None):
+        tq = t if t.dim() == 2 else t[None, :]
+        early = (tq < self.t_last[:, None]) & (self.state[:, 1:2] > 0)
+        if count is not None:
+            early = early & (torch.arange(tq.shape[-1], device=tq.device)[None, :] < count[:, None])
+        if bool(early.any()):
+            raise ValueError("The forecast coordinates must not be before the last absorbed time")
+
+    def forecast_kernel(self, t, *, yerr=None, diag=None, include_mean=True, count=None):
+        """`forecast` with its graph, on a filter whose kernel has tensor hyper-parameters: (mu, var) (B, M) at the times t
+        (M,) | (B, M), differentiable in the hyper-parameters, the mean, the jitter, the times, the noise and the state --
+        and through the state in every append (or gp.filter_kernel) the graph still holds.  Without noise `var` is the
+        latent variance; with `yerr` or `diag` (B, M) it is the variance of a would-be observation, jitter^2 included.
+        `count` (B,) int32: rows m >= count[b] are not read, their mu and var are 0.  Times before t_last are refused."""
+        from . import autograd
+
+        if not self.differentiable:
+            raise TypeError("forecast_kernel: the kernel has no tensor parameter (use forecast)")
+        self._check_forecast(t, count)
+        mean = self.mean if include_mean and (torch.is_tensor(self.mean) or self.mean != 0.0) else None
+        return autograd.filter_forecast_kernel(self.kernel, self.state, t, yerr=yerr, diag=diag, jitter=self.jitter, mean=mean,
+                                               count=count)
+
+    def forecast_log_density(self, t, y, *, yerr=None, diag=None, count=None):
+        """(B,) = sum over the taken rows of log N(y_m | mean + mu_m, var_m): the log density, under the forecast from the
+        present state, of the values y (B, M) that arrived at the times t (M,) | (B, M) -- each row on its own (the marginal
+        densities, not the joint one).  The noise `yerr` or `diag` (B, M) of those values is required; the filter's jitter
+        is added in quadrature.  On a filter with tensor hyper-parameters the result carries the graph (forecast_kernel);
+        on a plain one it goes through ops.filter_forecast.  `count` (B,) int32: how many of the M rows each series takes
+        (0: that series gives 0).  Times before t_last are refused."""
+        if yerr is not None and diag is not None:
+            raise ValueError("only one of 'diag' and 'yerr' can be provided")
+        if yerr is None and diag is None:
+            raise ValueError("'diag' or 'yerr' (B, M) is required")
+        B, M = self.state.shape[0], t.shape[-1]
+        if tuple(y.shape) != (B, M):
+            raise ValueError("Invalid shape: y %s, expected %s" % (tuple(y.shape), (B, M)))
+        if self.differentiable:
+            mu, var = self.forecast_kernel(t, yerr=yerr, diag=diag, count=count)
+        else:
+            self._check_forecast(t, count)
+            c, a, U, _ = self._rows(t, yerr**2 if diag is None else diag, "t")
+            mu, var = ops.filter_forecast(self.state, t.contiguous(), c, a, U, count=count)
+            mu = mu + (self.mean[:, None] if torch.is_tensor(self.mean) and self.mean.dim() == 1 else self.mean)
+        if count is not None:   # the rows not taken: a unit normal at its mean, then dropped from the sum
+            taken = torch.arange(M, device=y.device)[None, :] < count[:, None]
+            mu, var = torch.where(taken, mu, y.detach()), torch.where(taken, var, torch.ones_like(var))
+        dens = -0.5 * ((y - mu) ** 2 / var + torch.log(var) + math.log(2.0 * math.pi))
+        return (dens if count is None else torch.where(taken, dens, torch.zeros_like(dens))).sum(dim=1)
