@@ -1,8 +1,8 @@
 # -*- coding: utf-8 -*-
 """ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
 celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h, celerite2_amd_shapes.h,
-celerite2_amd_harmonics.h, celerite2_amd_harmonic_trials.h, celerite2_amd_filter.h, celerite2_amd_filter_rev.h and
-celerite2_amd_filter_stream_rev.h).
+celerite2_amd_harmonics.h, celerite2_amd_harmonic_trials.h, celerite2_amd_filter.h, celerite2_amd_filter_rev.h,
+celerite2_amd_filter_stream_rev.h and celerite2_amd_filter_draw.h).
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
@@ -26,6 +26,7 @@ HARMONIC_TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celeri
 FILTER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter.h")   # streaming updates
 FILTER_REV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_rev.h")   # ... and their reverse
 FILTER_STREAM_REV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_stream_rev.h")   # ... of absorb and forecast
+FILTER_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_draw.h")   # forecast sample paths
 
 
 class BackendError(RuntimeError):
@@ -139,6 +140,10 @@ FILTER_REV_SYMBOLS = ["c2_filter_rev_workspace_words", "c2_filter_append_rev"]
 # 70000 series itself.)
 FILTER_STREAM_REV_EXPORTS = ["c2_filter_forecast_rev", "c2_filter_absorb_rev"]
 
+# Every symbol include/celerite2_amd_filter_draw.h declares (checked by tests/test_filter_draw.py).  (Not a *SYMBOLS list
+# either: tests/test_gpu_filter_draw.py runs the draw at 70000 series itself.)
+FILTER_DRAW_EXPORTS = ["c2_filter_draw_chunk", "c2_filter_draw"]
+
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
 _env_seen = None     # their values when the table was last (re)loaded
@@ -213,6 +218,7 @@ def load():
     protos.update(_prototypes(_header(FILTER_HEADER)))
     protos.update(_prototypes(_header(FILTER_REV_HEADER)))
     protos.update(_prototypes(_header(FILTER_STREAM_REV_HEADER)))
+    protos.update(_prototypes(_header(FILTER_DRAW_HEADER)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

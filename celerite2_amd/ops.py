@@ -36,7 +36,8 @@ __all__ = [
 # `filter_state_words`, `filter_init`, `filter_append`, `filter_absorb` and `filter_forecast` of celerite2_amd_filter.h,
 # _lib.FILTER_SYMBOLS, and `filter_rev_workspace_words` and `filter_append_rev` of celerite2_amd_filter_rev.h,
 # _lib.FILTER_REV_SYMBOLS, and `filter_forecast_rev` and `filter_absorb_rev` of celerite2_amd_filter_stream_rev.h,
-# _lib.FILTER_STREAM_REV_EXPORTS)
+# _lib.FILTER_STREAM_REV_EXPORTS, and `filter_draw_chunk` and `filter_draw` of celerite2_amd_filter_draw.h,
+# _lib.FILTER_DRAW_EXPORTS)
 
 
 def _p(x):
@@ -1636,3 +1637,38 @@ def filter_absorb_rev(state, t, c, W, d, z, bstate, *, count=None, ws=None, out=
     rc = _lib.load().c2_filter_absorb_rev(B, M, J, state, t, _bs(t, M), c, _bs(c, J), W, d, z, count, bstate, ws, *out, _stream())
     _lib.check(rc, "filter_absorb_rev")
     return out
+
+
+# ---- forecast sample paths (include/celerite2_amd_filter_draw.h, csrc/c2_filter_draw.hip; _lib.FILTER_DRAW_EXPORTS) ---------
+def filter_draw_chunk(J):
+    """Draws one pass of the draw kernel carries at width J (further draws go to further blocks, each repeating the O(J^2)
+    part of a row); 0 beyond J = 32."""
+    return int(_lib.load().c2_filter_draw_chunk(int(J)))
+
+
+def filter_draw(state, t, c, a, U, V, eps, *, count=None, paths=None, d=None):
+    """K joint draws at M query rows per series from a filter state, in O(M (J^2 + J K)) (c2_filter_draw): state (B, SW),
+    t (M,) | (B, M), c (J,) | (B, J), a (B, M), U, V (B, M, J) the celerite matrices of the query rows, eps (B, M, K) standard
+    normals, draw-fastest -> (paths (B, M, K), d (B, M), flag (B,) int32).  Row by row, the append run backwards in y:
+    z_k = sqrt(d) eps_k, y_k = u^T F_k + z_k, F_k <- F_k + w z_k, with the S, d and w of the append shared by the draws -- so
+    paths = mu_c + chol(Sigma_c) eps for the dense conditional mean and covariance of the M rows given every absorbed row,
+    and d, flag have filter_append's bits.  a = k(0) + diag: draws of would-be observations; a = k(0): of the latent process.
+    The state is read and not written.  `count` (B,) int32: rows m >= count[b] are neither read nor written.  flag: the
+    1-based row with d <= 0 (the rows before it are written, the failing row's d, nothing behind it), else 0.  Caller-owned
+    `paths`, `d` are accepted and must not alias an input.  J <= 32.  The times must be sorted and not before the state's
+    t_last: not checked here (celerite2_amd.stream.Filter.sample_forecast does)."""
+    dims = _filter_dims(U, "U")
+    B, M, J = dims["B"], dims["M"], dims["J"]
+    if eps.dim() != 3:
+        raise ValueError("Invalid shape: eps (must be (B, M, K))")
+    dims["K"] = K = eps.shape[2]
+    paths = torch.empty_like(eps) if paths is None else paths
+    d = torch.empty_like(a) if d is None else d
+    ins = [("state", state, "BS"), ("t", t, _FILTER_ROWS["t"]), ("c", c, _C), ("a", a, "BM"), ("U", U, "BMJ"), ("V", V, "BMJ"),
+           ("eps", eps, "BMK")]
+    _args(dims, ins, [("paths", paths, "BMK"), ("d", d, "BM")])
+    _filter_count(count, dims, U.device)
+    flag = _flag(B, U.device)
+    rc = _lib.load().c2_filter_draw(B, M, J, K, state, t, _bs(t, M), c, _bs(c, J), a, U, V, eps, count, paths, d, flag, _stream())
+    _lib.check(rc, "filter_draw")
+    return paths, d, flag

@@ -30,6 +30,14 @@ what arrived at the forecast times -- forecast skill h nights ahead as a trainin
     skill = flt.forecast_log_density(t_later, y_later, yerr=e_later)   # (B,), before those rows are appended
     (-skill.sum()).backward()
 
+The future of a correlated process is a path: `sample_forecast` draws the M query times JOINTLY from the state (kernel:
+csrc/c2_filter_draw.hip, ops.filter_draw -- the append run backwards in y, the S, d and w of a row shared by all draws), and
+`forecast_joint_log_density` is the log density of M arrived rows taken together (an append that does not advance the filter):
+
+    paths = flt.sample_forecast(t_next, size=256)              # (B, 256, M): latent paths; with yerr=...: would-be observations
+    share = (paths > threshold).any(dim=2).double().mean(dim=1)   # in what share of futures does a source cross it?
+    joint = flt.forecast_joint_log_density(t_later, y_later, yerr=e_later)   # (B,), carries the graph on a differentiable filter
+
 `gp.filter_kernel(y)` builds a differentiable filter from a computed GP (autograd.filter_absorb_kernel): what is appended or
 forecast behind it sends its gradient back through the absorbed series.  A filter on a plain kernel behaves as before: in
 place, no graph."""
@@ -208,7 +216,8 @@ class Filter:
     def forecast_log_density(self, t, y, *, yerr=None, diag=None, count=None):
         """(B,) = sum over the taken rows of log N(y_m | mean + mu_m, var_m): the log density, under the forecast from the
         present state, of the values y (B, M) that arrived at the times t (M,) | (B, M) -- each row on its own (the marginal
-        densities, not the joint one).  The noise `yerr` or `diag` (B, M) of those values is required; the filter's jitter
+        densities; forecast_joint_log_density is that of the rows taken together, and equals this one for M = 1).  The
+        noise `yerr` or `diag` (B, M) of those values is required; the filter's jitter
         is added in quadrature.  On a filter with tensor hyper-parameters the result carries the graph (forecast_kernel);
         on a plain one it goes through ops.filter_forecast.  `count` (B,) int32: how many of the M rows each series takes
         (0: that series gives 0).  Times before t_last are refused."""
@@ -231,3 +240,91 @@ class Filter:
             mu, var = torch.where(taken, mu, y.detach()), torch.where(taken, var, torch.ones_like(var))
         dens = -0.5 * ((y - mu) ** 2 / var + torch.log(var) + math.log(2.0 * math.pi))
         return (dens if count is None else torch.where(taken, dens, torch.zeros_like(dens))).sum(dim=1)
+
+    def forecast_joint_log_density(self, t, y, *, yerr=None, diag=None, count=None):
+        """(B,) = log N(y | mean + mu_c, Sigma_c): the log density, under the forecast from the present state, of the values
+        y (B, M) at the times t (M,) | (B, M) TAKEN TOGETHER -- mu_c and Sigma_c the conditional mean and covariance of the
+        M rows given every absorbed row.  It is -(1/2) sum (z^2 / d + log d + log 2 pi) over the taken rows of an append
+        that does not advance the filter (formed from that append's d and z, not from the states' running sums, which lose
+        digits behind thousands of absorbed rows); the filter is left bit for bit as it was.  The noise `yerr` or `diag`
+        (B, M) is required, the filter's jitter is added in quadrature.  On a filter with tensor hyper-parameters the
+        result carries the graph (autograd.filter_append_kernel); on a plain one it goes through ops.filter_append.
+        `count` (B,) int32: how many of the M rows each series takes (0: that series gives 0).  The times must be sorted
+        and not before t_last.  NaN where a row's predictive variance came out <= 0."""
+        if yerr is not None and diag is not None:
+            raise ValueError("only one of 'diag' and 'yerr' can be provided")
+        if yerr is None and diag is None:
+            raise ValueError("'diag' or 'yerr' (B, M) is required")
+        B, M = self.state.shape[0], t.shape[-1]
+        if tuple(y.shape) != (B, M):
+            raise ValueError("Invalid shape: y %s, expected %s" % (tuple(y.shape), (B, M)))
+        self._check_sorted(t, count)
+        if self.differentiable:
+            from . import autograd
+
+            mean = self.mean if torch.is_tensor(self.mean) or self.mean != 0.0 else None
+            _, d, _, z, flag = autograd.filter_append_kernel(self.kernel, self.state, t, y, yerr=yerr, diag=diag,
+                                                             jitter=self.jitter, mean=mean, count=count)
+        else:
+            c, a, U, V = self._rows(t, yerr**2 if diag is None else diag, "t")
+            mean = self.mean[:, None] if torch.is_tensor(self.mean) and self.mean.dim() == 1 else self.mean
+            _, d, _, z, flag = ops.filter_append(self.state, t.contiguous(), c, a, U, V, (y - mean).contiguous(), count=count)
+        # the rows not taken, and every row of a failed series: a unit normal at its mean, then dropped from the sum
+        taken = (flag == 0)[:, None].expand(B, M)
+        if count is not None:
+            taken = taken & (torch.arange(M, device=y.device)[None, :] < count[:, None])
+        d, z = torch.where(taken, d, torch.ones_like(d)), torch.where(taken, z, torch.zeros_like(z))
+        dens = torch.where(taken, -0.5 * (z * z / d + torch.log(d) + math.log(2.0 * math.pi)), torch.zeros_like(d)).sum(dim=1)
+        return torch.where(flag == 0, dens, torch.full_like(dens, math.nan))
+
+    # -- sample paths ----------------------------------------------------------------------------------------------------
+    def sample_forecast(self, t, *, size=None, yerr=None, diag=None, include_mean=True, count=None, generator=None,
+                        normals=None, check_sorted=True):
+        """Joint draws (B, M) -- (B, size, M) when `size` is given, gp.sample_at's convention -- of the future at the sorted
+        times t (M,) | (B, M), none before t_last, given every absorbed row: sample PATHS, where `forecast` gives a mean and
+        a variance per time.  One kernel call (ops.filter_draw), O(M (J^2 + J size)) a series, without the old rows: the
+        append run backwards in y, y_m = u^T F + sqrt(d_m) eps_m followed by the append of y_m, the S, d and w of a row
+        shared by the draws.  The draws equal mu_c + chol(Sigma_c) eps for the conditional mean and covariance of the M rows.
+
+        Without noise arguments the draws are of the LATENT process; with `yerr` or `diag` (B, M) they are of would-be
+        observations, the filter's jitter added in quadrature where there is one.  A latent draw at a repeated query time
+        (or at t_last itself) has d = 0 there: the row is flagged and the series comes back as NaN (where rounding leaves
+        d a few ulps of k(0) above zero instead, the row repeats the value before it) -- give such rows a noise, or
+        drop the repeat.  `normals` (B, M, K), K = size (1 for None): the standard normals, for reproducibility;
+        otherwise torch.randn(..., generator=generator).  `count` (B,) int32: how many of the M rows each series takes.
+        NaN in every row of a series whose predictive variance came out <= 0 somewhere and in the rows beyond `count`.
+        The filter is not changed.  On a filter with tensor hyper-parameters the values are detached, as forecast's."""
+        if yerr is not None and diag is not None:
+            raise ValueError("only one of 'diag' and 'yerr' can be provided")
+        B, M, dev = self.state.shape[0], t.shape[-1], self.state.device
+        K = 1 if size is None else int(size)
+        if K < 1:
+            raise ValueError("'size' must be at least 1")
+        if normals is not None and tuple(normals.shape) != (B, M, K):
+            raise ValueError("Invalid shape: normals %s, expected %s" % (tuple(normals.shape), (B, M, K)))
+        noise = diag if yerr is None else yerr**2
+        state, mean = self.state, self.mean
+        if self.differentiable:   # detached values: the reverse of the draw is not written
+            t, state = t.detach(), state.detach()
+            if torch.is_tensor(mean):
+                mean = mean.detach()
+            if noise is not None:
+                noise = noise.detach()
+                if self.jitter is not None:
+                    jit = torch.as_tensor(self.jitter, dtype=torch.float64, device=dev).detach()
+                    noise = noise + (jit * jit if jit.dim() == 0 else (jit * jit)[:, None])
+        if noise is None:
+            noise = torch.zeros((B, M), dtype=torch.float64, device=dev)
+        c, a, U, V = (x.detach().contiguous() for x in self._rows(t, noise, "t"))   # (refuses a t or a noise of another shape)
+        self._check_forecast(t, count)
+        if check_sorted:
+            self._check_sorted(t, count)
+        if normals is None:
+            normals = torch.randn((B, M, K), dtype=torch.float64, device=dev, generator=generator)
+        paths = torch.full((B, M, K), math.nan, dtype=torch.float64, device=dev)
+        paths, _, flag = ops.filter_draw(state, t.contiguous(), c, a, U, V, normals.contiguous(), count=count, paths=paths)
+        out = paths.transpose(1, 2)   # (B, K, M)
+        if include_mean:
+            out = out + (mean[:, None, None] if torch.is_tensor(mean) and mean.dim() == 1 else mean)
+        out = torch.where((flag != 0)[:, None, None], torch.full_like(out, math.nan), out)
+        return out[:, 0] if size is None else out
