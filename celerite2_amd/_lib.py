@@ -1,36 +1,83 @@
 # -*- coding: utf-8 -*-
-"""ctypes binding of the C-ABI (include/celerite2_amd.h, celerite2_amd_linear.h, celerite2_amd_periodogram.h,
-celerite2_amd_transit.h, celerite2_amd_kepler.h, celerite2_amd_trials.h, celerite2_amd_shapes.h,
-celerite2_amd_harmonics.h, celerite2_amd_harmonic_trials.h, celerite2_amd_filter.h, celerite2_amd_filter_rev.h,
-celerite2_amd_filter_stream_rev.h and celerite2_amd_filter_draw.h).
+"""ctypes binding of the C-ABI: every public header under include/ has one record in HEADERS below, and the binding, the
+build's staleness list, the ABI tests (tests/test_abi.py) and the census of entry points (tests/test_large_batch_table.py)
+all read that table.  A new public header is one more record.
 
 There is NO CPU fallback: if libcelerite2_amd.so is missing or no HIP device is
 visible, the product path raises -- it never routes through oracle/.
 """
+import collections
 import ctypes
 import os
 import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# override: A/B builds.  Whatever library is chosen, it is bound with THIS tree's header (the ABI of an A/B pair is one).
+# override: A/B builds.  Whatever library is chosen, it is bound with THIS tree's headers (the ABI of an A/B pair is one).
 LIB_PATH = os.environ.get("C2_LIB_PATH", os.path.join(_HERE, "libcelerite2_amd.so"))
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd.h")   # = build.INCLUDE: the build is in-tree
-LINEAR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_linear.h")   # linear mean models
-PERIODOGRAM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_periodogram.h")   # the periodogram
-TRANSIT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_transit.h")   # the transit search
-KEPLER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_kepler.h")   # the Keplerian search
-TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_trials.h")   # projections on trial columns
-SHAPES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_shapes.h")   # the tabulated-shape search
-HARMONICS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_harmonics.h")   # the multi-harmonic periodogram
-HARMONIC_TRIALS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_harmonic_trials.h")   # ... and its null draws
-FILTER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter.h")   # streaming updates
-FILTER_REV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_rev.h")   # ... and their reverse
-FILTER_STREAM_REV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_stream_rev.h")   # ... of absorb and forecast
-FILTER_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "celerite2_amd_filter_draw.h")   # forecast sample paths
+
+# One public header: its file under include/, the C symbols it declares in the header's order (hand-written: the pin the
+# header is compared against) and the public names of ops.py that belong to it (None: ops.__all__).
+Header = collections.namedtuple("Header", "file symbols ops")
+
+HEADERS = {
+    "main": Header("celerite2_amd.h", [
+        "c2_version", "c2_device_count", "c2_last_error",
+        "c2_set_option", "c2_get_option", "c2_option_count", "c2_option_info", "c2_options_reload_env",
+        "c2_factor", "c2_solve_lower", "c2_solve_upper", "c2_matmul_lower", "c2_matmul_upper",
+        "c2_general_matmul_lower", "c2_general_matmul_upper", "c2_factor_rev",
+        "c2_solve_lower_rev", "c2_solve_upper_rev", "c2_matmul_lower_rev", "c2_matmul_upper_rev",
+        "c2_get_celerite_matrices", "c2_kernel_values", "c2_colsumsq_over_d", "c2_loglik", "c2_loglik_grad_workspace_bytes",
+        "c2_loglik_grad", "c2_condition",
+        "c2_kron_loglik_workspace_bytes", "c2_kron_loglik", "c2_kron_loglik_grad",
+        "c2_loglik_terms_workspace_bytes", "c2_loglik_terms", "c2_loglik_terms_grad",
+        "c2_term_coefficients", "c2_term_coefficients_rev", "c2_noise_mean_apply", "c2_noise_mean_rev",
+        "c2_term_expr_workspace_bytes", "c2_term_expr_coefficients", "c2_term_expr_coefficients_rev",
+        "c2_noise_mean_shift_apply", "c2_noise_mean_shift_rev", "c2_dot_tril",
+        "c2_inverse_diag", "c2_inverse_diag_fwd", "c2_inverse_diag_rev",
+        "c2_get_celerite_matrices_rev_workspace_bytes", "c2_get_celerite_matrices_rev",
+        "c2_explained_variance", "c2_explained_variance_fwd", "c2_explained_variance_rev", "c2_prior_draw",
+        "c2_general_matmul_lower_rev", "c2_general_matmul_upper_rev",
+        "c2h_factor", "c2h_solve_lower", "c2h_solve_upper", "c2h_matmul_lower", "c2h_matmul_upper",
+        "c2h_general_matmul_lower", "c2h_general_matmul_upper", "c2h_factor_rev",
+        "c2h_solve_lower_rev", "c2h_solve_upper_rev", "c2h_matmul_lower_rev", "c2h_matmul_upper_rev",
+        "c2h_get_celerite_matrices", "c2h_release_thread_cache",
+    ], None),
+    "linear": Header("celerite2_amd_linear.h", ["c2_whitened_gram"], ["whitened_gram"]),   # linear mean models
+    "periodogram": Header("celerite2_amd_periodogram.h", ["c2_whitened_sinusoids"], ["whitened_sinusoids"]),
+    "transit": Header("celerite2_amd_transit.h", ["c2_whitened_transits"], ["whitened_transits"]),   # the transit search
+    "kepler": Header("celerite2_amd_kepler.h", ["c2_whitened_keplerians"], ["whitened_keplerians"]),   # the Keplerian search
+    "trials": Header("celerite2_amd_trials.h", ["c2_trial_projections"], ["trial_projections"]),   # projections on trial columns
+    "shapes": Header("celerite2_amd_shapes.h", ["c2_whitened_shapes", "c2_shape_projections"],   # the tabulated-shape search
+                     ["whitened_shapes", "shape_projections"]),
+    "harmonics": Header("celerite2_amd_harmonics.h", ["c2_whitened_harmonics"], ["whitened_harmonics"]),   # the multi-harmonic periodogram
+    "harmonic_trials": Header("celerite2_amd_harmonic_trials.h", ["c2_harmonic_projections", "c2_harmonic_null_chi2"],   # ... and its null draws
+                              ["harmonic_projections", "harmonic_null_chi2"]),
+    "filter": Header("celerite2_amd_filter.h",   # streaming updates
+                     ["c2_filter_state_words", "c2_filter_append", "c2_filter_absorb", "c2_filter_forecast"],
+                     ["filter_state_words", "filter_init", "filter_append", "filter_absorb", "filter_forecast"]),
+    "filter_rev": Header("celerite2_amd_filter_rev.h", ["c2_filter_rev_workspace_words", "c2_filter_append_rev"],   # ... and their reverse
+                         ["filter_rev_workspace_words", "filter_append_rev"]),
+    "filter_stream_rev": Header("celerite2_amd_filter_stream_rev.h", ["c2_filter_forecast_rev", "c2_filter_absorb_rev"],   # ... of absorb and forecast
+                                ["filter_forecast_rev", "filter_absorb_rev"]),
+    "filter_draw": Header("celerite2_amd_filter_draw.h", ["c2_filter_draw_chunk", "c2_filter_draw"],   # forecast sample paths
+                          ["filter_draw_chunk", "filter_draw"]),
+}
+
+
+def header_path(key):
+    return os.path.join(os.path.dirname(_HERE), "include", HEADERS[key].file)   # (the build is in-tree)
 
 
 class BackendError(RuntimeError):
     pass
+
+
+def header_text(key):
+    """A public header without its comments."""
+    path = header_path(key)
+    if not os.path.exists(path):
+        raise BackendError("celerite2_amd: %s not found -- the Python binding takes its prototypes from it" % path)
+    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
 
 
 class Pointer(ctypes.c_void_p):
@@ -55,14 +102,6 @@ _CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const 
                               "c2_stream_t", "const char **", "const c2_term_program *", "const c2_term_expr *"), Pointer))
 
 
-def _header(path=None):
-    """A public header (default: include/celerite2_amd.h) without its comments."""
-    path = HEADER if path is None else path
-    if not os.path.exists(path):
-        raise BackendError("celerite2_amd: %s not found -- the Python binding takes its prototypes from it" % path)
-    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-
-
 def _ctype(text, name):
     text = " ".join(text.replace("*", " * ").split()).replace("* *", "**")
     if text not in _CTYPES:
@@ -80,69 +119,7 @@ def _prototypes(header):
 
 
 globals().update({k: int(v) for k, v in re.findall(r"^#define\s+(C2_(?:OK|ERR_\w+|MAX_WIDTH|FAST_WIDTH))\s+\(?(-?\d+)\)?\s*$",
-                                                     _header(), flags=re.M)})
-
-# Every symbol include/celerite2_amd.h declares (checked by tests/test_abi.py).
-SYMBOLS = [
-    "c2_version", "c2_device_count", "c2_last_error",
-    "c2_factor", "c2_solve_lower", "c2_solve_upper", "c2_matmul_lower", "c2_matmul_upper",
-    "c2_general_matmul_lower", "c2_general_matmul_upper", "c2_factor_rev",
-    "c2_solve_lower_rev", "c2_solve_upper_rev", "c2_matmul_lower_rev", "c2_matmul_upper_rev",
-    "c2_get_celerite_matrices", "c2_kernel_values", "c2_colsumsq_over_d", "c2_loglik", "c2_loglik_grad_workspace_bytes", "c2_loglik_grad", "c2_condition", "c2_dot_tril",
-    "c2_kron_loglik_workspace_bytes", "c2_kron_loglik", "c2_kron_loglik_grad",
-    "c2_loglik_terms_workspace_bytes", "c2_loglik_terms", "c2_loglik_terms_grad",
-    "c2_term_coefficients", "c2_term_coefficients_rev", "c2_noise_mean_apply", "c2_noise_mean_rev",
-    "c2_term_expr_workspace_bytes", "c2_term_expr_coefficients", "c2_term_expr_coefficients_rev",
-    "c2_noise_mean_shift_apply", "c2_noise_mean_shift_rev", "c2_inverse_diag", "c2_explained_variance",
-    "c2_prior_draw", "c2_inverse_diag_fwd", "c2_inverse_diag_rev",
-    "c2_get_celerite_matrices_rev_workspace_bytes", "c2_get_celerite_matrices_rev",
-    "c2_general_matmul_lower_rev", "c2_general_matmul_upper_rev",
-    "c2_explained_variance_fwd", "c2_explained_variance_rev",
-    "c2h_factor", "c2h_solve_lower", "c2h_solve_upper", "c2h_matmul_lower", "c2h_matmul_upper",
-    "c2h_general_matmul_lower", "c2h_general_matmul_upper", "c2h_factor_rev",
-    "c2h_solve_lower_rev", "c2h_solve_upper_rev", "c2h_matmul_lower_rev", "c2h_matmul_upper_rev",
-    "c2h_get_celerite_matrices", "c2h_release_thread_cache",
-    "c2_set_option", "c2_get_option", "c2_option_count", "c2_option_info", "c2_options_reload_env",
-]
-
-# Every symbol include/celerite2_amd_linear.h declares (checked by tests/test_linear_model.py).
-LINEAR_SYMBOLS = ["c2_whitened_gram"]
-
-# Every symbol include/celerite2_amd_periodogram.h declares (checked by tests/test_periodogram.py).
-PERIODOGRAM_SYMBOLS = ["c2_whitened_sinusoids"]
-
-# Every symbol include/celerite2_amd_transit.h declares (checked by tests/test_transit.py).
-TRANSIT_SYMBOLS = ["c2_whitened_transits"]
-
-# Every symbol include/celerite2_amd_kepler.h declares (checked by tests/test_kepler.py).
-KEPLER_SYMBOLS = ["c2_whitened_keplerians"]
-
-# Every symbol include/celerite2_amd_trials.h declares (checked by tests/test_significance.py).
-TRIALS_SYMBOLS = ["c2_trial_projections"]
-
-# Every symbol include/celerite2_amd_shapes.h declares (checked by tests/test_shapes.py).
-SHAPES_SYMBOLS = ["c2_whitened_shapes", "c2_shape_projections"]
-
-# Every symbol include/celerite2_amd_harmonics.h declares (checked by tests/test_harmonics.py).
-HARMONICS_SYMBOLS = ["c2_whitened_harmonics"]
-
-# Every symbol include/celerite2_amd_harmonic_trials.h declares (checked by tests/test_harmonic_significance.py).
-HARMONIC_TRIALS_SYMBOLS = ["c2_harmonic_projections", "c2_harmonic_null_chi2"]
-
-# Every symbol include/celerite2_amd_filter.h declares (checked by tests/test_filter.py).
-FILTER_SYMBOLS = ["c2_filter_state_words", "c2_filter_append", "c2_filter_absorb", "c2_filter_forecast"]
-
-# Every symbol include/celerite2_amd_filter_rev.h declares (checked by tests/test_filter_rev.py).
-FILTER_REV_SYMBOLS = ["c2_filter_rev_workspace_words", "c2_filter_append_rev"]
-
-# Every symbol include/celerite2_amd_filter_stream_rev.h declares (checked by tests/test_filter_stream_rev.py).  (Not a
-# *SYMBOLS list: those are the census of tests/large_batch_cases.py; tests/test_gpu_filter_stream_rev.py runs these two at
-# 70000 series itself.)
-FILTER_STREAM_REV_EXPORTS = ["c2_filter_forecast_rev", "c2_filter_absorb_rev"]
-
-# Every symbol include/celerite2_amd_filter_draw.h declares (checked by tests/test_filter_draw.py).  (Not a *SYMBOLS list
-# either: tests/test_gpu_filter_draw.py runs the draw at 70000 series itself.)
-FILTER_DRAW_EXPORTS = ["c2_filter_draw_chunk", "c2_filter_draw"]
+                                                     header_text("main"), flags=re.M)})
 
 _lib = None
 _env_names = ()      # environment variables of the option table (c2_option_info)
@@ -206,19 +183,9 @@ def load():
     except Exception:  # pragma: no cover - torch is plumbing, not required for the C-ABI itself
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    protos = _prototypes(_header())
-    protos.update(_prototypes(_header(LINEAR_HEADER)))
-    protos.update(_prototypes(_header(PERIODOGRAM_HEADER)))
-    protos.update(_prototypes(_header(TRANSIT_HEADER)))
-    protos.update(_prototypes(_header(KEPLER_HEADER)))
-    protos.update(_prototypes(_header(TRIALS_HEADER)))
-    protos.update(_prototypes(_header(SHAPES_HEADER)))
-    protos.update(_prototypes(_header(HARMONICS_HEADER)))
-    protos.update(_prototypes(_header(HARMONIC_TRIALS_HEADER)))
-    protos.update(_prototypes(_header(FILTER_HEADER)))
-    protos.update(_prototypes(_header(FILTER_REV_HEADER)))
-    protos.update(_prototypes(_header(FILTER_STREAM_REV_HEADER)))
-    protos.update(_prototypes(_header(FILTER_DRAW_HEADER)))
+    protos = {}
+    for key in HEADERS:
+        protos.update(_prototypes(header_text(key)))
     for name, (restype, argtypes) in protos.items():
         # (built with parameter flags, "input" each: a call then takes EXACTLY that many arguments -- argtypes alone let a
         # cdecl function take more)

@@ -15,25 +15,14 @@ import subprocess
 import sys
 import sysconfig
 
+from . import _lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libcelerite2_amd.so")
 HIP_SOURCES = ["c2_dispatch.hip", "c2_ops.hip", "c2_fused.hip", "c2_loglik.hip", "c2_loglik4.hip", "c2_loglik_q4.hip", "c2_loglik_t.hip", "c2_loglik_k2.hip", "c2_loglik_t6.hip", "c2_loglik_t4.hip", "c2_loglik_t2.hip", "c2_timepar.hip", "c2_timepar_grad.hip", "c2_timepar_grad32.hip", "c2_timepar_grad16.hip", "c2_sweep.hip", "c2_sweep_rev.hip", "c2_sweep_small.hip", "c2_sweep_small_rev.hip", "c2_solve_cols.hip", "c2_sweep_cols.hip", "c2_scan.hip", "c2_general.hip", "c2_general_tile.hip", "c2_general_rev.hip", "c2_mfma.hip", "c2_wide.hip", "c2_kron.hip", "c2_terms.hip", "c2_term_params.hip", "c2_term_expr.hip", "c2_invdiag.hip", "c2_invdiag_rev.hip", "c2_predvar.hip", "c2_predvar_rev.hip", "c2_priordraw.hip", "c2_gram.hip", "c2_periodogram.hip", "c2_harmonics.hip", "c2_transit.hip", "c2_kepler.hip", "c2_trial_project.hip", "c2_harmonic_trials.hip", "c2_shapes.hip", "c2_filter.hip", "c2_filter_rev.hip", "c2_filter_stream_rev.hip", "c2_filter_draw.hip", "c2_host.hip"]
 # every header of csrc/ makes every object stale (py_common.hpp among them: harmless), and so do the public headers
-HIP_HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(INCLUDE, "celerite2_amd.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_linear.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_periodogram.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_transit.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_kepler.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_trials.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_shapes.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_harmonics.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_harmonic_trials.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_filter.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_filter_rev.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_filter_stream_rev.h"),
-                                                               os.path.join(INCLUDE, "celerite2_amd_filter_draw.h")]
+HIP_HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [_lib.header_path(key) for key in _lib.HEADERS]
 # sources that are #included by other sources (one compilation per width / chunk length): extra dependencies of those only
 HIP_INCLUDED = {"c2_loglik_t.hip": ["c2_loglik_t2.hip", "c2_loglik_t4.hip", "c2_loglik_t6.hip"],
                 "c2_timepar_grad.hip": ["c2_timepar_grad16.hip", "c2_timepar_grad32.hip"]}
@@ -92,7 +81,7 @@ def build_pybind(force=False):
     for name in ("driver", "backprop"):
         src = os.path.join(CSRC, "py_%s.cpp" % name)
         target = ext_path(name)
-        deps = [src, os.path.join(CSRC, "py_common.hpp"), os.path.join(INCLUDE, "celerite2_amd.h"), LIB]
+        deps = [src, os.path.join(CSRC, "py_common.hpp"), _lib.header_path("main"), LIB]
         if force or _stale(target, deps):
             _run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden",
                   "-I" + pybind11.get_include(), "-I" + sysconfig.get_paths()["include"], src,

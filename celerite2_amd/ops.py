@@ -27,17 +27,7 @@ __all__ = [
     "noise_mean_shift_apply", "noise_mean_shift_rev",
     "loglik_kernel_workspace", "loglik_kernel_grad",
 ]
-# (`whitened_gram`, `whitened_sinusoids`, `whitened_transits`, `whitened_keplerians` and `trial_projections`, the ops of
-# include/celerite2_amd_linear.h, celerite2_amd_periodogram.h, celerite2_amd_transit.h, celerite2_amd_kepler.h and
-# celerite2_amd_trials.h, are public as well, and so is `whitened_harmonics` of celerite2_amd_harmonics.h
-# (_lib.HARMONICS_SYMBOLS); they are listed with their headers' symbols, _lib.LINEAR_SYMBOLS,
-# _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS and _lib.TRIALS_SYMBOLS, and this list stays the ops of
-# include/celerite2_amd.h; so are `whitened_shapes` and `shape_projections` of celerite2_amd_shapes.h, _lib.SHAPES_SYMBOLS, and
-# `filter_state_words`, `filter_init`, `filter_append`, `filter_absorb` and `filter_forecast` of celerite2_amd_filter.h,
-# _lib.FILTER_SYMBOLS, and `filter_rev_workspace_words` and `filter_append_rev` of celerite2_amd_filter_rev.h,
-# _lib.FILTER_REV_SYMBOLS, and `filter_forecast_rev` and `filter_absorb_rev` of celerite2_amd_filter_stream_rev.h,
-# _lib.FILTER_STREAM_REV_EXPORTS, and `filter_draw_chunk` and `filter_draw` of celerite2_amd_filter_draw.h,
-# _lib.FILTER_DRAW_EXPORTS)
+# (the ops of include/celerite2_amd.h; the public ops of the later headers stand with their headers in _lib.HEADERS)
 
 
 def _p(x):
@@ -545,7 +535,7 @@ def whitened_sinusoids(t, c, U, W, d, Z0, freq, *, t_ref=0.0, out=None):
 
 
 # C2_HARMONICS_MAX of include/celerite2_amd_harmonics.h
-HARMONICS_MAX = int(re.search(r"^#define\s+C2_HARMONICS_MAX\s+(\d+)", open(_lib.HARMONICS_HEADER).read(), flags=re.M).group(1))
+HARMONICS_MAX = int(re.search(r"^#define\s+C2_HARMONICS_MAX\s+(\d+)", _lib.header_text("harmonics"), flags=re.M).group(1))
 
 
 def whitened_harmonics(t, c, U, W, d, Z0, freq, nterms, *, t_ref=0.0, out=None):
@@ -569,7 +559,7 @@ def whitened_harmonics(t, c, U, W, d, Z0, freq, nterms, *, t_ref=0.0, out=None):
 
 # H -> C2_HARMONIC_DRAWS_H of include/celerite2_amd_harmonic_trials.h: the draws a wavefront takes
 HARMONIC_DRAWS = {int(h): int(v) for h, v in re.findall(r"^#define\s+C2_HARMONIC_DRAWS_(\d+)\s+(\d+)",
-                                                         open(_lib.HARMONIC_TRIALS_HEADER).read(), flags=re.M)}
+                                                         _lib.header_text("harmonic_trials"), flags=re.M)}
 _HARMONIC_MAX_P0 = 7
 
 
@@ -1454,7 +1444,7 @@ def loglik_kernel_grad(program, P, x, yerr, jitter, mean, y, *, yerr_is_sigma=Tr
     return ll, (bP, bj, bm, bx, bdiag, by), flag
 
 
-# ---- streaming updates (include/celerite2_amd_filter.h, csrc/c2_filter.hip; _lib.FILTER_SYMBOLS) ----------------------------
+# ---- streaming updates (include/celerite2_amd_filter.h, csrc/c2_filter.hip; _lib.HEADERS["filter"]) ------------------------
 _FILTER_ROWS = dict(t="M|BM", c=_C)   # the new rows' times and the rates; everything else of a row is per series
 
 
@@ -1552,7 +1542,7 @@ def filter_forecast(state, t, c, a, U, *, count=None, mu=None, var=None):
     return mu, var
 
 
-# ---- reverse of the append (include/celerite2_amd_filter_rev.h, csrc/c2_filter_rev.hip; _lib.FILTER_REV_SYMBOLS) -----------
+# ---- reverse of the append (include/celerite2_amd_filter_rev.h, csrc/c2_filter_rev.hip; _lib.HEADERS["filter_rev"]) --------
 _FILTER_REV_OUT = dict(bstate_in="BS", bt="BM", bc="BJ", ba="BM", bU="BMJ", bV="BMJ", by="BM")   # bt, bc: per series always
 
 
@@ -1589,7 +1579,7 @@ def filter_append_rev(state, t, c, U, W, d, z, flag, bstate, bd=None, bW=None, b
 
 
 # ---- reverse of forecast and absorb (include/celerite2_amd_filter_stream_rev.h, csrc/c2_filter_stream_rev.hip;
-# _lib.FILTER_STREAM_REV_EXPORTS) -------------------------------------------------------------------------------------------
+# _lib.HEADERS["filter_stream_rev"]) ----------------------------------------------------------------------------------------
 _FILTER_FORECAST_REV_OUT = dict(bstate="BS", bt="BM", bc="BJ", ba="BM", bU="BMJ")                       # bt, bc: per series always
 _FILTER_ABSORB_REV_OUT = dict(bstate_in="BS", bt="BM", bc="BJ", bW="BMJ", bd="BM", bz="BM")
 
@@ -1639,7 +1629,7 @@ def filter_absorb_rev(state, t, c, W, d, z, bstate, *, count=None, ws=None, out=
     return out
 
 
-# ---- forecast sample paths (include/celerite2_amd_filter_draw.h, csrc/c2_filter_draw.hip; _lib.FILTER_DRAW_EXPORTS) ---------
+# ---- forecast sample paths (include/celerite2_amd_filter_draw.h, csrc/c2_filter_draw.hip; _lib.HEADERS["filter_draw"]) -----
 def filter_draw_chunk(J):
     """Draws one pass of the draw kernel carries at width J (further draws go to further blocks, each repeating the O(J^2)
     part of a row); 0 beyond J = 32."""

@@ -1003,6 +1003,12 @@ COVERED_ELSEWHERE = {
     "c2_noise_mean_shift_apply": "test_gpu_term_algebra.py::test_noise_mean_shift_kernels",
     "noise_mean_shift_rev": "test_gpu_term_algebra.py::test_noise_mean_shift_kernels",
     "c2_noise_mean_shift_rev": "test_gpu_term_algebra.py::test_noise_mean_shift_kernels",
+    "filter_forecast_rev": "test_gpu_filter_stream_rev.py::test_large_batch",
+    "c2_filter_forecast_rev": "test_gpu_filter_stream_rev.py::test_large_batch",
+    "filter_absorb_rev": "test_gpu_filter_stream_rev.py::test_large_batch",
+    "c2_filter_absorb_rev": "test_gpu_filter_stream_rev.py::test_large_batch",
+    "filter_draw": "test_gpu_filter_draw.py::test_large_batch",
+    "c2_filter_draw": "test_gpu_filter_draw.py::test_large_batch",
 }
 
 # name -> why it has no batch axis to take beyond 65535
@@ -1014,6 +1020,8 @@ NO_BATCH_AXIS = {
     "c2_loglik_terms_workspace_bytes": "a workspace-size query", "c2_term_expr_workspace_bytes": "a workspace-size query",
     "c2_get_celerite_matrices_rev_workspace_bytes": "a workspace-size query",
     "c2_filter_state_words": "a size query", "c2_filter_rev_workspace_words": "a size query",
+    "filter_state_words": "a size query", "filter_rev_workspace_words": "a size query",
+    "filter_draw_chunk": "a size query", "c2_filter_draw_chunk": "a size query",
     "c2_set_option": "the option table", "c2_get_option": "the option table", "c2_option_count": "the option table",
     "c2_option_info": "the option table", "c2_options_reload_env": "the option table",
     "c2h_release_thread_cache": "the host layer's staging cache",

@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
-"""CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
-include/celerite2_amd.h declares, the pybind11 modules expose the reference's surface
-(python/celerite2/driver.cpp:482-499, backprop.cpp:906-926) and its argument validation, and the
+"""CPU-side checks of the drop-in boundary: the C-ABI library loads and every public header stands against its record
+in celerite2_amd._lib.HEADERS (declared, exported, typed, in the build, its ops), the pybind11 modules expose the
+reference's surface (python/celerite2/driver.cpp:482-499, backprop.cpp:906-926) and its argument validation, and the
 product path fails loudly (no CPU fallback) when no GPU is present."""
 import ctypes
 import os
@@ -22,17 +22,59 @@ def built():
     return build
 
 
-def test_header_symbols_exported(built):
+def _header_keys():
     from celerite2_amd import _lib
 
-    header = open(os.path.join(ROOT, "include", "celerite2_amd.h")).read()
-    declared = set(re.findall(r"\b(c2h?_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), name
-    lib.c2_version.restype = ctypes.c_char_p
-    assert b"gfx950" in lib.c2_version()
+    return list(_lib.HEADERS)
+
+
+@pytest.fixture(scope="module")
+def table(built):
+    """What holds of _lib.HEADERS as a whole, checked once: (the table, the library as the linker sees it, as load() types it)."""
+    import glob
+
+    from celerite2_amd import _lib
+
+    records = list(_lib.HEADERS.values())
+    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(r.file for r in records) and len(records) == 13
+    symbols = [s for r in records for s in r.symbols]
+    ops_names = [n for r in records if r.ops is not None for n in r.ops]
+    assert len(symbols) == len(set(symbols)) == 88 and len(ops_names) == len(set(ops_names))
+    main = [k for k, r in _lib.HEADERS.items() if r.ops is None]
+    assert main == ["main"] and len(_lib.HEADERS["main"].symbols) == 68
+    sources = {os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "celerite2_amd", "csrc", "*.hip"))}
+    assert sources and sources == set(built.HIP_SOURCES), sources ^ set(built.HIP_SOURCES)
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    so.c2_version.restype = ctypes.c_char_p
+    assert b"gfx950" in so.c2_version()
+    return _lib.HEADERS, so, _lib.load()
+
+
+@pytest.mark.parametrize("key", _header_keys())
+def test_public_header(table, built, key):
+    """One public header against its record: the prototypes it declares are the record's symbols in order, nothing that looks
+    like a c2_ call hides outside a prototype, every symbol is exported and typed from its prototype by load(), the header
+    makes the build stale, and the record's ops exist on ops (in ops.__all__ exactly for the main header)."""
+    from celerite2_amd import _lib, ops
+
+    headers, so, lib = table
+    record, text = headers[key], _lib.header_text(key)
+    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", text)
+    assert [name for _, name, _ in declared] == list(_lib._prototypes(text)) == record.symbols
+    loose = set(re.findall(r"\b(c2h?_[a-z0-9_]+)\s*\(", text))
+    assert loose == set(record.symbols), loose ^ set(record.symbols)
+    restypes = {"size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "void": None, "int64_t": ctypes.c_int64}
+    for ret, name, params in declared:
+        assert hasattr(so, name), name
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, name
+        assert len(fn.argtypes) == (0 if params.strip() == "void" else len(params.split(","))), name
+        assert fn.restype is restypes.get(" ".join(ret.split()), ctypes.c_int), name
+    assert _lib.header_path(key) in built.HIP_HEADERS
+    assert os.path.samefile(_lib.header_path(key), os.path.join(ROOT, "include", record.file))
+    for name in ops.__all__ if record.ops is None else record.ops:
+        assert callable(getattr(ops, name)), name
+        assert (name in ops.__all__) == (record.ops is None), name
 
 
 def test_gfx950_code_object(built):

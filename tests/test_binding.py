@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
-"""The Python binding takes its prototypes from include/celerite2_amd.h (celerite2_amd/_lib.py): every declared symbol is
-typed, a call that does not fit its prototype is refused before C is entered, every kind of pointer argument the tests and
-tools pass still works, the constants are the header's, and the shape helper of ops.py says what _shape said.  No GPU."""
+"""The Python binding takes its prototypes from include/celerite2_amd.h (celerite2_amd/_lib.py): a call that does not fit
+its prototype is refused before C is entered, every kind of pointer argument the tests and tools pass still works, the
+constants are the header's, and the shape helper of ops.py says what _shape said.  (That every declared symbol is typed:
+tests/test_abi.py::test_public_header.)  No GPU."""
 import ctypes
 import os
 import re
@@ -23,19 +24,6 @@ def lib():
 @pytest.fixture(scope="module")
 def header():
     return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "celerite2_amd.h")).read(), flags=re.S)
-
-
-def test_every_declared_symbol_is_typed(lib, header):
-    from celerite2_amd import _lib
-
-    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", header)
-    assert len(declared) == 68 and {name for _, name, _ in declared} == set(_lib.SYMBOLS)
-    restypes = {"size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "void": None}
-    for ret, name, params in declared:
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None, name
-        assert len(fn.argtypes) == (0 if params.strip() == "void" else len(params.split(","))), name
-        assert fn.restype is restypes.get(" ".join(ret.split()), ctypes.c_int), name
 
 
 def loglik_args(B=0, J=2, p=None):

@@ -154,7 +154,7 @@ def test_abi_argument_errors():
     i64, null = ctypes.c_int64, ctypes.c_void_p(0)
     one = ctypes.c_void_p(8)   # a non-null address that is never dereferenced: the checks come first
     for name, nptr in (("c2_explained_variance_fwd", 12), ("c2_explained_variance_rev", 20)):
-        assert name in _lib.SYMBOLS
+        assert name in _lib.HEADERS["main"].symbols
         fn = getattr(lib, name)
 
         def call(B, N, M, J, ptrs):

@@ -263,32 +263,16 @@ def null_args(B=1, N=4, F=3, H=2, R=2, P0=1, p=None, D=None, Lm="p", Xt="p", V="
 
 
 def test_header_is_exported_and_typed(lib):
-    from celerite2_amd import _lib, build, ops, significance as sg
+    """What is this header's own (what holds of every public header: tests/test_abi.py::test_public_header)."""
+    from celerite2_amd import _lib, ops, significance as sg
 
-    path = os.path.join(ROOT, "include", "celerite2_amd_harmonic_trials.h")
-    assert _lib.HARMONIC_TRIALS_HEADER == path
-    text = open(path).read()
-    header = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", header)
-    assert [name for _, name, _ in declared] == _lib.HARMONIC_TRIALS_SYMBOLS == ["c2_harmonic_projections", "c2_harmonic_null_chi2"]
-    counts = {"c2_harmonic_projections": (13, 5), "c2_harmonic_null_chi2": (17, 6)}
-    for _, name, params in declared:
-        fn = getattr(lib, name)      # (exported: CFUNCTYPE((name, lib)) resolved it at load)
-        n, ints = counts[name]
-        assert len(fn.argtypes) == len(params.split(",")) == n and fn.restype is ctypes.c_int, name
+    text = open(_lib.header_path("harmonic_trials")).read()
+    for name, n, ints in (("c2_harmonic_projections", 13, 5), ("c2_harmonic_null_chi2", 17, 6)):
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == n and fn.restype is ctypes.c_int, name
         assert fn.argtypes[:ints] == (ctypes.c_int64,) * ints and fn.argtypes[ints] is _lib.Pointer, name
         assert fn.argtypes[ints + 1] is fn.argtypes[ints + 3] is ctypes.c_int64 and fn.argtypes[ints + 4] is ctypes.c_double, name
         assert all(a is _lib.Pointer for a in fn.argtypes[ints + 5:]), name
-    # the main header stays at 68 symbols and the eighth header at its single entry point
-    assert len(_lib.SYMBOLS) == 68 and _lib.HARMONICS_SYMBOLS == ["c2_whitened_harmonics"]
-    eighth = re.sub(r"/\*.*?\*/", " ", open(_lib.HARMONICS_HEADER).read(), flags=re.S)
-    assert re.findall(r"\b(c2h?_\w+)\s*\(", eighth) == ["c2_whitened_harmonics"]
-    others = (_lib.SYMBOLS + _lib.LINEAR_SYMBOLS + _lib.PERIODOGRAM_SYMBOLS + _lib.TRANSIT_SYMBOLS + _lib.KEPLER_SYMBOLS
-              + _lib.TRIALS_SYMBOLS + _lib.SHAPES_SYMBOLS + _lib.HARMONICS_SYMBOLS)
-    assert not set(_lib.HARMONIC_TRIALS_SYMBOLS) & set(others)
-    assert path in build.HIP_HEADERS and "c2_harmonic_trials.hip" in build.HIP_SOURCES
-    for name in ("harmonic_projections", "harmonic_null_chi2"):
-        assert name not in ops.__all__ and callable(getattr(ops, name))
     # the draws a wavefront: one value per H, multiples of 16, the header's
     defs = {int(h): int(v) for h, v in re.findall(r"^#define\s+C2_HARMONIC_DRAWS_(\d+)\s+(\d+)", text, flags=re.M)}
     assert ops.HARMONIC_DRAWS == defs and sorted(defs) == list(range(1, ops.HARMONICS_MAX + 1))

@@ -6,7 +6,6 @@ the models, an injected two-harmonic signal, the NaN rules, and the binding of t
 (include/celerite2_amd_harmonics.h), which needs no device.  Criterion: the standing one,
 |x - x_o| <= 1e-10 |x_o| + 1e-12 max |x_o| per element; NaN positions must coincide exactly."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -16,7 +15,6 @@ import torch
 import harmonics_ref as R
 import periodogram_ref as PR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDTHS = [1, 2, 3, 5, 8, 16, 32]
 LENGTHS = [1, 2, 17, 33, 150]
 TERMS = [1, 2, 3, 4]
@@ -232,25 +230,14 @@ def har_args(B=1, N=4, J=2, Q0=1, F=3, H=2, p=None, T=None, t_ref=0.0):
 
 
 def test_harmonics_header_is_exported_and_typed(lib):
-    from celerite2_amd import _lib, build, ops
+    """What is this header's own (what holds of every public header: tests/test_abi.py::test_public_header)."""
+    from celerite2_amd import _lib, ops
 
-    text = open(os.path.join(ROOT, "include", "celerite2_amd_harmonics.h")).read()
-    assert _lib.HARMONICS_HEADER == os.path.join(ROOT, "include", "celerite2_amd_harmonics.h")
-    header = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", header)
-    assert [name for _, name, _ in declared] == _lib.HARMONICS_SYMBOLS == ["c2_whitened_harmonics"]
-    for ret, name, params in declared:
-        fn = getattr(lib, name)      # (exported: CFUNCTYPE((name, lib)) resolved it at load)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(params.split(",")) == 19, name
-        assert fn.restype is ctypes.c_int, name
-        assert fn.argtypes[:6] == (ctypes.c_int64,) * 6 and fn.argtypes[6] is _lib.Pointer and fn.argtypes[15] is ctypes.c_int64
-        assert fn.argtypes[16] is ctypes.c_double and fn.argtypes[17] is _lib.Pointer
-    others = (_lib.SYMBOLS + _lib.LINEAR_SYMBOLS + _lib.PERIODOGRAM_SYMBOLS + _lib.TRANSIT_SYMBOLS + _lib.KEPLER_SYMBOLS
-              + _lib.TRIALS_SYMBOLS + _lib.SHAPES_SYMBOLS)
-    assert len(others) == 68 + 1 + 1 + 1 + 1 + 1 + 2 and not set(_lib.HARMONICS_SYMBOLS) & set(others)
-    assert os.path.join(build.INCLUDE, "celerite2_amd_harmonics.h") in build.HIP_HEADERS
-    assert "c2_harmonics.hip" in build.HIP_SOURCES
-    assert "whitened_harmonics" not in ops.__all__ and callable(ops.whitened_harmonics)
+    text = open(_lib.header_path("harmonics")).read()
+    fn = lib.c2_whitened_harmonics
+    assert len(fn.argtypes) == 19 and fn.restype is ctypes.c_int
+    assert fn.argtypes[:6] == (ctypes.c_int64,) * 6 and fn.argtypes[6] is _lib.Pointer and fn.argtypes[15] is ctypes.c_int64
+    assert fn.argtypes[16] is ctypes.c_double and fn.argtypes[17] is _lib.Pointer
     assert int(re.search(r"^#define\s+C2_HARMONICS_MAX\s+(\d+)", text, flags=re.M).group(1)) == ops.HARMONICS_MAX == 4
     # the pinned tables of the searches are as they were
     assert set(ops._TRIAL_TABLE) == {"periodogram", "transit", "keplerian", "shape"}

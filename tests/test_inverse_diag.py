@@ -113,7 +113,7 @@ def test_abi_argument_errors():
     from celerite2_amd import _lib, build
 
     build.build_all()
-    assert "c2_inverse_diag" in _lib.SYMBOLS
+    assert "c2_inverse_diag" in _lib.HEADERS["main"].symbols
     lib = _lib.load()
     i64, null = ctypes.c_int64, ctypes.c_void_p(0)
     one = ctypes.c_void_p(8)   # a non-null address that is never dereferenced: the checks come first

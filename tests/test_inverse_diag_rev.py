@@ -144,7 +144,7 @@ def test_abi_argument_errors():
 
     build.build_all()
     for name in ("c2_inverse_diag_fwd", "c2_inverse_diag_rev", "c2_get_celerite_matrices_rev"):
-        assert name in _lib.SYMBOLS
+        assert name in _lib.HEADERS["main"].symbols
     lib = _lib.load()
     i64, null = ctypes.c_int64, ctypes.c_void_p(0)
     one = ctypes.c_void_p(8)   # a non-null address that is never dereferenced: the checks come first

@@ -280,27 +280,15 @@ def kp_args(B=1, N=4, J=2, Q0=1, K=3, p=None, T=None):
 
 
 def test_kepler_header_is_exported_and_typed(lib):
+    """What is this header's own (what holds of every public header: tests/test_abi.py::test_public_header)."""
     from celerite2_amd import _lib
 
-    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "celerite2_amd_kepler.h")).read(), flags=re.S)
-    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", header)
-    assert [name for _, name, _ in declared] == _lib.KEPLER_SYMBOLS == ["c2_whitened_keplerians"]
-    for ret, name, params in declared:
-        fn = getattr(lib, name)      # (exported: CFUNCTYPE((name, lib)) resolved it at load)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(params.split(",")) == 17, name
-        assert fn.restype is ctypes.c_int, name
-        assert fn.argtypes[:5] == (ctypes.c_int64,) * 5 and fn.argtypes[5] is _lib.Pointer and fn.argtypes[6] is ctypes.c_int64
-        assert fn.argtypes[13] is _lib.Pointer and fn.argtypes[14] is ctypes.c_int64 and fn.argtypes[15] is _lib.Pointer
-    assert len(_lib.SYMBOLS) == 68 and _lib.LINEAR_SYMBOLS == ["c2_whitened_gram"] and _lib.PERIODOGRAM_SYMBOLS == ["c2_whitened_sinusoids"]
-    assert _lib.TRANSIT_SYMBOLS == ["c2_whitened_transits"]
-    assert not set(_lib.KEPLER_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.LINEAR_SYMBOLS) | set(_lib.PERIODOGRAM_SYMBOLS)
-                                           | set(_lib.TRANSIT_SYMBOLS))
-    from celerite2_amd import build, ops
-    assert os.path.join(build.INCLUDE, "celerite2_amd_kepler.h") in build.HIP_HEADERS
-    assert "c2_kepler.hip" in build.HIP_SOURCES
-    assert "whitened_keplerians" not in ops.__all__ and callable(ops.whitened_keplerians)
+    fn = lib.c2_whitened_keplerians
+    assert len(fn.argtypes) == 17 and fn.restype is ctypes.c_int
+    assert fn.argtypes[:5] == (ctypes.c_int64,) * 5 and fn.argtypes[5] is _lib.Pointer and fn.argtypes[6] is ctypes.c_int64
+    assert fn.argtypes[13] is _lib.Pointer and fn.argtypes[14] is ctypes.c_int64 and fn.argtypes[15] is _lib.Pointer
     # the constants of the header's rule are the ones the restatement uses
-    text = open(os.path.join(ROOT, "include", "celerite2_amd_kepler.h")).read()
+    text = open(_lib.header_path("kepler")).read()
     assert float.fromhex(re.search(r"TWO_PI = fl\(2 pi\) = (\S+);", text).group(1)) == R.TWO_PI
     assert float.fromhex(re.search(r"INV_2PI = fl\(1 / fl\(2 pi\)\) = (\S+);", text).group(1)) == R.INV_2PI
 

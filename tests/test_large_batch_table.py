@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
-"""Every public entry point stands beyond 65535 series somewhere: each name of ops.__all__ and of the _lib.*_SYMBOLS lists is in
-exactly one of large_batch_cases.ROWS (run by tests/test_gpu_large_batch.py at B = 70000), COVERED_ELSEWHERE (an existing test
-that runs it there) and NO_BATCH_AXIS.  An entry point added later fails here, on the CPU, until it has its case.
+"""Every public entry point stands beyond 65535 series somewhere: each name of ops.__all__ and every op and C symbol of every
+record of _lib.HEADERS is in exactly one of large_batch_cases.ROWS (run by tests/test_gpu_large_batch.py at B = 70000),
+COVERED_ELSEWHERE (an existing test that runs it there) and NO_BATCH_AXIS.  An entry point added later fails here, on the
+CPU, until it has its case.
 
 Every row's builder and host reference also run here on the seven distinct series: the inputs are valid and the references
 finite without a GPU, and in a `fail` row the chosen series, and only that one, fails in the oracle."""
@@ -28,9 +29,8 @@ def public_names():
     from celerite2_amd import _lib, ops
 
     names = list(ops.__all__)
-    for attr in sorted(dir(_lib)):
-        if attr == "SYMBOLS" or attr.endswith("_SYMBOLS"):
-            names += getattr(_lib, attr)
+    for record in _lib.HEADERS.values():
+        names += (record.ops or []) + record.symbols
     return names
 
 
@@ -41,11 +41,8 @@ def test_every_entry_point_has_a_case_beyond_65535(built):
     for name in names:
         where = [name in p for p in places]
         assert sum(where) == 1, "%r is in %d of ROWS / COVERED_ELSEWHERE / NO_BATCH_AXIS (exactly one wanted)" % (name, sum(where))
-    listed = places[0] | places[1] | places[2]
-    from celerite2_amd import ops
-    extra = listed - set(names)
-    # (public ops of the later headers are not in ops.__all__: they are listed with their symbols, and must exist)
-    assert all(hasattr(ops, n) for n in extra), sorted(n for n in extra if not hasattr(ops, n))
+    extra = (places[0] | places[1] | places[2]) - set(names)
+    assert not extra, sorted(extra)   # (nothing is listed that the table does not name)
     for name, reason in L.NO_BATCH_AXIS.items():
         assert reason.strip(), name
 

@@ -6,7 +6,6 @@ finish and the builders (celerite2_amd/shapes.py), an injected limb-darkened tra
 header (include/celerite2_amd_shapes.h), which needs no device.  Criterion: the standing one,
 |x - x_o| <= 1e-10 |x_o| + 1e-12 max |x_o| per element; NaN positions must coincide exactly."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -16,7 +15,6 @@ import torch
 import shapes_ref as R
 import transit_ref as TR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWEEP_ARGS = ("t", "c", "U", "W", "d", "Z0", "trials", "shapes")
 WORST = {}
 
@@ -399,25 +397,14 @@ def pr_args(B=1, N=4, K=3, R=2, NS=1, S=2, p=None, P=None, sh_bs=0):
 
 
 def test_shapes_header_is_exported_and_typed(lib):
-    from celerite2_amd import _lib, build, ops
+    """What is this header's own (what holds of every public header: tests/test_abi.py::test_public_header)."""
+    from celerite2_amd import _lib, ops
 
-    text = open(os.path.join(ROOT, "include", "celerite2_amd_shapes.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    declared = re.findall(r"([\w \t*]+?)\b(c2h?_\w+)\s*\(([^)]*)\)\s*;", header)
-    assert [name for _, name, _ in declared] == _lib.SHAPES_SYMBOLS == ["c2_whitened_shapes", "c2_shape_projections"]
-    counts = {"c2_whitened_shapes": 21, "c2_shape_projections": 15}
-    for ret, name, params in declared:
-        fn = getattr(lib, name)      # (exported: CFUNCTYPE((name, lib)) resolved it at load)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(params.split(",")) == counts[name], name
-        assert fn.restype is ctypes.c_int, name
+    text = open(_lib.header_path("shapes")).read()
+    for name, count in (("c2_whitened_shapes", 21), ("c2_shape_projections", 15)):
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == count and fn.restype is ctypes.c_int, name
         assert fn.argtypes[-1] is _lib.Pointer and fn.argtypes[-5] is _lib.Pointer and fn.argtypes[-4:-1] == (ctypes.c_int64,) * 3
-    others = [_lib.SYMBOLS, _lib.LINEAR_SYMBOLS, _lib.PERIODOGRAM_SYMBOLS, _lib.TRANSIT_SYMBOLS, _lib.KEPLER_SYMBOLS, _lib.TRIALS_SYMBOLS]
-    assert len(_lib.SYMBOLS) == 68
-    assert not set(_lib.SHAPES_SYMBOLS) & set().union(*others)
-    assert os.path.join(build.INCLUDE, "celerite2_amd_shapes.h") in build.HIP_HEADERS
-    assert "c2_shapes.hip" in build.HIP_SOURCES and "c2_trial_project.hip" in build.HIP_SOURCES   # (both entry points' sources)
-    assert all(n not in ops.__all__ for n in ("whitened_shapes", "shape_projections"))
-    assert callable(ops.whitened_shapes) and callable(ops.shape_projections)
     defines = dict(re.findall(r"^#define\s+(C2_SHAPE_\w+)\s+(\d+)\s*$", text, flags=re.M))
     assert int(defines["C2_SHAPE_MAX_NODES"]) == ops.SHAPE_MAX_NODES == 1024
     assert int(defines["C2_SHAPE_DRAWS"]) == ops.SHAPE_DRAWS and ops.SHAPE_DRAWS % 16 == 0
