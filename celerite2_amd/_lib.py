@@ -98,7 +98,7 @@ class Pointer(ctypes.c_void_p):
 
 # The C types of the header's prototypes (parameters and return values).  A prototype that uses another one fails at load.
 _CTYPES = {"void": None, "int": ctypes.c_int, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
-_CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const int32_t *", "int *", "int64_t *", "void *",
+_CTYPES.update(dict.fromkeys(("double *", "const double *", "int32_t *", "const int32_t *", "int *", "int64_t *", "const int64_t *", "void *",
                               "c2_stream_t", "const char **", "const c2_term_program *", "const c2_term_expr *"), Pointer))
 
 

@@ -20,9 +20,11 @@ from . import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcelerite2_amd.so")
-HIP_SOURCES = ["c2_dispatch.hip", "c2_ops.hip", "c2_fused.hip", "c2_loglik.hip", "c2_loglik4.hip", "c2_loglik_q4.hip", "c2_loglik_t.hip", "c2_loglik_k2.hip", "c2_loglik_t6.hip", "c2_loglik_t4.hip", "c2_loglik_t2.hip", "c2_timepar.hip", "c2_timepar_grad.hip", "c2_timepar_grad32.hip", "c2_timepar_grad16.hip", "c2_sweep.hip", "c2_sweep_rev.hip", "c2_sweep_small.hip", "c2_sweep_small_rev.hip", "c2_solve_cols.hip", "c2_sweep_cols.hip", "c2_scan.hip", "c2_general.hip", "c2_general_tile.hip", "c2_general_rev.hip", "c2_mfma.hip", "c2_wide.hip", "c2_kron.hip", "c2_terms.hip", "c2_term_params.hip", "c2_term_expr.hip", "c2_invdiag.hip", "c2_invdiag_rev.hip", "c2_predvar.hip", "c2_predvar_rev.hip", "c2_priordraw.hip", "c2_gram.hip", "c2_periodogram.hip", "c2_harmonics.hip", "c2_transit.hip", "c2_kepler.hip", "c2_trial_project.hip", "c2_harmonic_trials.hip", "c2_shapes.hip", "c2_filter.hip", "c2_filter_rev.hip", "c2_filter_stream_rev.hip", "c2_filter_draw.hip", "c2_host.hip"]
+HIP_SOURCES = ["c2_dispatch.hip", "c2_ops.hip", "c2_fused.hip", "c2_loglik.hip", "c2_loglik4.hip", "c2_loglik_q4.hip", "c2_loglik_t.hip", "c2_loglik_k2.hip", "c2_loglik_t6.hip", "c2_loglik_t4.hip", "c2_loglik_t2.hip", "c2_timepar.hip", "c2_timepar_grad.hip", "c2_timepar_grad32.hip", "c2_timepar_grad16.hip", "c2_sweep.hip", "c2_sweep_rev.hip", "c2_sweep_small.hip", "c2_sweep_small_rev.hip", "c2_solve_cols.hip", "c2_sweep_cols.hip", "c2_scan.hip", "c2_general.hip", "c2_general_tile.hip", "c2_general_rev.hip", "c2_mfma.hip", "c2_wide.hip", "c2_kron.hip", "c2_terms.hip", "c2_term_params.hip", "c2_term_expr.hip", "c2_invdiag.hip", "c2_invdiag_rev.hip", "c2_predvar.hip", "c2_predvar_rev.hip", "c2_priordraw.hip", "c2_gram.hip", "c2_periodogram.hip", "c2_harmonics.hip", "c2_transit.hip", "c2_kepler.hip", "c2_trial_project.hip", "c2_harmonic_trials.hip", "c2_shapes.hip", "c2_filter.hip", "c2_filter_rev.hip", "c2_filter_stream_rev.hip", "c2_filter_draw.hip", "c2_packed.hip", "c2_host.hip"]
 # every header of csrc/ makes every object stale (py_common.hpp among them: harmless), and so do the public headers
-HIP_HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [_lib.header_path(key) for key in _lib.HEADERS]
+# ... and the provisional interface of the ragged batches, which is declared next to its source (celerite2_amd/packed.py)
+HIP_HEADERS = (sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [_lib.header_path(key) for key in _lib.HEADERS]
+               + [os.path.join(CSRC, "c2_packed_api.h")])
 # sources that are #included by other sources (one compilation per width / chunk length): extra dependencies of those only
 HIP_INCLUDED = {"c2_loglik_t.hip": ["c2_loglik_t2.hip", "c2_loglik_t4.hip", "c2_loglik_t6.hip"],
                 "c2_timepar_grad.hip": ["c2_timepar_grad16.hip", "c2_timepar_grad32.hip"]}
